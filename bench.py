@@ -11,9 +11,16 @@ rows on the host, plus -- for N > 1 -- the per-step gather of rows to rank 0) ov
 per-GPU batch is fixed.  Rank 0 prints ONE JSON line (see the contract in the task statement).
 
 The headline (`value`) is BASELINE.json's metric on configs[1]'s model and size at the batch that fills the chip (512 per GPU).
-At N = 1 the same line carries `configs`: every BASELINE configuration as stated (batch 1 / 32 / 8 and 64 / 1280-half 2 and
-16), each with its own throughput and conv-stack roofline fraction, and `host_fed_value`: the headline workload fed from
-pinned host memory (PCIe-inclusive; never `value`).
+A plain run does only what that figure needs: set-up, warm-up, the timed steps, the outputs (`--dump-outputs DIR`) and the
+line.  `--full` adds everything else: the conv-stack roofline from profiled steps of their own, the CPU baseline with its
+parity figures, and at N = 1 on the default workload `configs` (every BASELINE configuration as stated: batch 1 / 32 / 8 and
+64 / 1280-half 2 and 16, each with its own throughput and roofline fraction), `track_pipeline` and `host_fed_value` (the
+headline workload fed from pinned host memory, PCIe-inclusive; never `value`).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (rank 0: the rows of every GPU), decoded per row:
+boxes.npy [rows, 5] x1 y1 x2 y2 conf (float32, original-image pixels), classes.npy and anchor_idx.npy [rows] (float64),
+keypoints.npy [rows, nkpt * kdim] (float32, pose models only), counts.npy [frames] rows per frame and frame_index.npy
+[frames] the global frame number of each count (float64).  The inputs are seeded: the same arguments give the same frames.
 """
 from __future__ import annotations
 
@@ -50,6 +57,7 @@ EXTRA_CONFIGS = [
     ("yolov8n", 640, 512, False, 12, 3, 0.0, True),
 ]
 HEADLINE_CPU_BUDGET_S = 18.0
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all (a seeded sample of frames beyond it)
 
 
 def make_frames(n: int, size: int, seed: int):
@@ -365,6 +373,29 @@ def config_cpu_and_parity(out: dict, model_name: str, size: int, batch: int, hal
     torch.cuda.empty_cache()
 
 
+def dump_outputs(dirname: str, rows: np.ndarray, counts: np.ndarray, nk: int) -> None:
+    """--dump-outputs: the packed post-NMS rows of one step ([sum(counts), >= 7 + nk] 32-bit words: x1 y1 x2 y2 conf as float,
+    cls and anchor index as int32, then nk keypoint floats) and the rows per frame, as float32 / float64 .npy files.  Beyond
+    DUMP_LIMIT_BYTES (at max_det rows per frame) a fixed, seeded sample of frames is written, chosen before any output is seen."""
+    counts = np.asarray(counts, dtype=np.int64)
+    n = len(counts)
+    per_frame = 300 * (4 * 5 + 8 + 8 + 4 * nk) + 16                      # worst case of one frame in the files below
+    frame_index = np.arange(n)
+    if n * per_frame > DUMP_LIMIT_BYTES:
+        frame_index = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // per_frame, replace=False))
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    sel = np.concatenate([np.arange(starts[i], starts[i] + counts[i]) for i in frame_index]) if len(frame_index) else np.zeros(0, np.int64)
+    r = np.ascontiguousarray(rows[sel.astype(np.int64)])
+    os.makedirs(dirname, exist_ok=True)
+    out = {"boxes": r[:, :5].astype(np.float32), "classes": r[:, 5].view(np.int32).astype(np.float64),
+           "anchor_idx": r[:, 6].view(np.int32).astype(np.float64), "counts": counts[frame_index].astype(np.float64),
+           "frame_index": frame_index.astype(np.float64)}
+    if nk:
+        out["keypoints"] = r[:, 7:7 + nk].astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def launch_ranks(n: int, argv: list) -> int:
     """``python bench.py --gpus N`` without a launcher: start N FRESH child processes of this script, one per GPU, with
     RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, relay rank 0's single JSON line and return the first non-zero child exit
@@ -432,11 +463,18 @@ def main() -> None:
     ap.add_argument("--half", action="store_true",
                     help="BASELINE config 5 mode: the half=True engine (fp16 storage, fp32 accumulate); the line then says "
                          "dtype f16 and prices the convs against the dense f16 MFMA peak.  Never the default headline.")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the conv-stack roofline (profiled steps of their own), the CPU "
+                         "baseline and parity figures, and on the default workload host_fed_value, every BASELINE config and the track loop")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rows the last step returned as DIR/<name>.npy (rank 0, every GPU's rows)")
     args = ap.parse_args()
     if args.chunk <= 0:
         args.chunk = args.batch
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher (no torch, no HIP call before or after)
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -510,8 +548,9 @@ def main() -> None:
 
     def finish():
         if gath is not None:
-            gath.flush()
+            last = gath.flush()
             model.sync()
+            return last
 
     def barrier():
         torch.cuda.synchronize()
@@ -529,18 +568,21 @@ def main() -> None:
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
-    finish()
+        last = step()
+    flushed = finish()
     barrier()
     dt = time.perf_counter() - t0
+    if gath is not None:
+        last = flushed                      # the gather runs one step behind: the flush delivers the last step's rows
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if dry else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    # ---- roofline of the dominant kernel (implicit-GEMM conv), HIP events on the engine's stream ----
-    PROF_STEPS = 3
-    conv_ms, launches, kinds = profile_convs(model, frames, args.size, PROF_STEPS)
+    if args.full:
+        # ---- roofline of the dominant kernel (implicit-GEMM conv), HIP events on the engine's stream ----
+        PROF_STEPS = 3
+        conv_ms, launches, kinds = profile_convs(model, frames, args.size, PROF_STEPS)
     # the world size the collective library itself reports (RCCL's communicator when backend == "nccl")
     comm_world = dist.get_world_size() if world > 1 else 1
     if world > 1:
@@ -551,15 +593,41 @@ def main() -> None:
             dist.destroy_process_group()
         return
 
-    conv_flops_frame = conv_flops_per_frame(args.model, args.size)
+    if args.dump_outputs:
+        if world == 1:                      # (rows [B, max_det, words], counts [B], frame shape): keep rows[i, :counts[i], :ncols]
+            rows, counts, _ = last
+            rows = rows[np.arange(rows.shape[1])[None, :] < counts[:, None]][:, :ncols]
+        else:                               # rank 0's gather: (per-rank packed row blocks, per-rank counts), in global frame order
+            rows, counts = np.concatenate(last[0]), np.concatenate(last[1])
+        dump_outputs(args.dump_outputs, rows, counts, model.kpt_shape[0] * model.kpt_shape[1])
+
     scale = (args.size / 640.0) ** 2
-    achieved = conv_flops_frame * B / (conv_ms * 1e-3) / 1e12
     fps = world * B * args.steps / dt
+    plan = model.plan_info()
+    line = {
+        "metric": f"frames/s @{args.size}x{args.size}" + (" (half=True engine: diagnostic)" if args.half else "") + (" (HOST frames, PCIe-inclusive: diagnostic)" if args.host_frames else ""), "value": round(fps, 1), "unit": "frames/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16" if args.half else "f32", "data": "synthetic",
+        "config": {"workload": f"{args.model} {args.size}x{args.size} synthetic BGR frames ({B} distinct frames per GPU), batch {B}/GPU/step, "
+                               f"predict conf=0.25 iou=0.7 max_det=300 (letterbox+stem, conv graph, decode, NMS, rows to host)",
+                   "global_batch": B * world, "params": params, "gflop_per_frame": round(gflops * scale, 3),
+                   "parallelism": f"frame-sharded dp{world}", "collectives_backend": backend, "ranks": world,
+                   "collective_world_size": comm_world,
+                   "collectives_per_step": 0 if world == 1 else 2,
+                   "activation_bytes_per_gpu": plan["activation_bytes"]},
+    }
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    conv_flops_frame = conv_flops_per_frame(args.model, args.size)
+    achieved = conv_flops_frame * B / (conv_ms * 1e-3) / 1e12
     # HBM traffic per conv launch cannot be measured inside this process (rocprofv3 PMC passes are separate runs: the guide's
     # HBM section); the figure collected on this exact workload is kept under profiles/ and quoted ONLY with its source
     # named and only while the launch sequence it was collected on has the same length as this run's -- else null.
     traffic, traffic_source = None, None
-    plan = model.plan_info()
     tag = "cfg5" if (args.half and args.model == "yolov8m" and args.size == 1280 and B == 16) else "v1" if (args.model == "yolov8n" and args.size == 640 and B == 512 and not args.half) else None
     tpath = os.path.join(ROOT, "profiles", f"r04_{tag}_conv_traffic.json") if tag and args.chunk == B else None
     if tpath and os.path.exists(tpath):
@@ -572,27 +640,15 @@ def main() -> None:
         else:
             traffic_source = f"profiles/r04_{tag}_conv_traffic.json not quoted: collected on plan_hash {tj.get('plan_hash')}, this run has {plan['plan_hash']}"
     peak = F16_PEAK_TFLOPS if args.half else FP32_PEAK_TFLOPS
-    line = {
-        "metric": f"frames/s @{args.size}x{args.size}" + (" (half=True engine: diagnostic)" if args.half else "") + (" (HOST frames, PCIe-inclusive: diagnostic)" if args.host_frames else ""), "value": round(fps, 1), "unit": "frames/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16" if args.half else "f32", "data": "synthetic",
-        "config": {"workload": f"{args.model} {args.size}x{args.size} synthetic BGR frames ({B} distinct frames per GPU), batch {B}/GPU/step, "
-                               f"predict conf=0.25 iou=0.7 max_det=300 (letterbox+stem, conv graph, decode, NMS, rows to host)",
-                   "global_batch": B * world, "params": params, "gflop_per_frame": round(gflops * scale, 3),
-                   "parallelism": f"frame-sharded dp{world}", "collectives_backend": backend, "ranks": world,
-                   "collective_world_size": comm_world,
-                   "collectives_per_step": 0 if world == 1 else 2},
-        "roofline": {"bound": "mfma", "kernel": ("conv_igemm_f16 + conv3x3_lw_f16 + conv1x1_lwx_f16 + conv1x1_pipe_f16" if args.half else "conv_igemm_f32 + conv1x1_pipe_f32 + conv1x1_stream_f32") + " (every conv launch of a step)",
-                     "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                     "traffic": traffic, "traffic_source": traffic_source, "avg_launch_us": round(conv_ms * 1e3 / max(launches, 1), 2),
-                     **{k: v for k, v in roofline_fractions(args.model, args.size, B, args.half, conv_ms).items() if k != "bound"},
-                     "launches_per_step": launches,
-                     "flop_per_launch_avg": conv_flops_frame * B / max(launches, 1)},
-        "device_ms_per_step": {k: round(v, 3) for k, v in kinds.items()},
-    }
+    line["roofline"] = {"bound": "mfma", "kernel": ("conv_igemm_f16 + conv3x3_lw_f16 + conv1x1_lwx_f16 + conv1x1_pipe_f16" if args.half else "conv_igemm_f32 + conv1x1_pipe_f32 + conv1x1_stream_f32") + " (every conv launch of a step)",
+                        "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                        "traffic": traffic, "traffic_source": traffic_source, "avg_launch_us": round(conv_ms * 1e3 / max(launches, 1), 2),
+                        **{k: v for k, v in roofline_fractions(args.model, args.size, B, args.half, conv_ms).items() if k != "bound"},
+                        "launches_per_step": launches,
+                        "flop_per_launch_avg": conv_flops_frame * B / max(launches, 1)}
+    line["device_ms_per_step"] = {k: round(v, 3) for k, v in kinds.items()}
     headline_default = (args.model == "yolov8n" and args.size == 640 and B == 512 and not args.half and not args.host_frames)
     line["roofline"]["plan_hash"], line["roofline"]["plan_source"] = plan["plan_hash"], plan["plan_source"]
-    line["config"]["activation_bytes_per_gpu"] = plan["activation_bytes"]
     want_cpu = world == 1 and not args.no_cpu_baseline and not args.half
     if want_cpu and not (world == 1 and headline_default and not args.no_configs):
         line["cpu_baseline"] = cpu_baseline(args, sd, frames_np, model)

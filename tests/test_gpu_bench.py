@@ -18,7 +18,7 @@ def _last_json(out: str) -> dict:
 
 def test_bench_line_single_gpu():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "8", "--chunk", "8", "--steps", "2", "--warmup", "1",
-                        "--cpu-frames", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--cpu-frames", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _last_json(p.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -46,15 +46,56 @@ def test_bench_line_single_gpu():
     assert "configs" not in d and "host_fed_value" not in d   # those ride on the default headline workload only
 
 
-def test_bench_two_ranks_rehearsed_on_one_gpu():
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """without --full: the headline fields only (no profiled steps, no CPU work), and --dump-outputs writes the rows of the last
+    timed step -- the same rows the engine returns for the same seeded frames"""
+    import numpy as np
+    out = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", "yolov8n-pose", "--batch", "8", "--chunk", "8",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _last_json(p.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["dtype"] == "f32" and d["higher_is_better"] is True and d["ms_per_step"] > 0 and d["value"] > 0
+    assert abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    for k in ("roofline", "device_ms_per_step", "cpu_baseline", "configs", "host_fed_value", "track_pipeline"):
+        assert k not in d, k
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(got) == {"boxes", "classes", "anchor_idx", "keypoints", "counts", "frame_index"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    import torch
+    import bench
+    from cvsd_amd import YOLO
+    from tools import synth
+    _, sd = synth.synthetic_checkpoint("yolov8n-pose", seed=0)
+    m = YOLO.from_state_dict("yolov8n-pose", sd, batch_chunk=8)
+    frames, _ = bench.make_frames(8, 640, seed=1000)                # rank 0's frames
+    rows, counts, _ = m._infer_rows(frames, 0.25, 0.7, None, 300, 640)
+    np.testing.assert_array_equal(got["frame_index"], np.arange(8))
+    np.testing.assert_array_equal(got["counts"], counts)
+    want = np.concatenate([rows[i, :counts[i]] for i in range(8)])
+    assert len(want) > 0
+    np.testing.assert_array_equal(got["boxes"], want[:, :5])
+    np.testing.assert_array_equal(got["classes"], want[:, 5].view(np.int32))
+    np.testing.assert_array_equal(got["anchor_idx"], want[:, 6].view(np.int32))
+    np.testing.assert_array_equal(got["keypoints"], want[:, 7:7 + 51])
+    del m, frames
+    torch.cuda.empty_cache()
+
+
+def test_bench_two_ranks_rehearsed_on_one_gpu(tmp_path):
     env = dict(os.environ, BENCH_DRYRUN_ONE_GPU="1", MASTER_ADDR="127.0.0.1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29537", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "8", "--chunk", "8",
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _last_json(p.stdout)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0 and "cpu_baseline" not in d
     assert d["config"]["global_batch"] == 16
+    import numpy as np
+    counts = np.load(tmp_path / "counts.npy")                     # rank 0 writes the rows of both ranks, in global frame order
+    assert counts.shape == (16,) and np.load(tmp_path / "boxes.npy").shape == (int(counts.sum()), 5)
 
 
 def test_bench_gpus_2_as_one_plain_command_self_launches_its_ranks():

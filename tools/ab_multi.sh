@@ -7,7 +7,7 @@ for name in product "$@"; do
   if [ $name = product ]; then unset MI355_YOLO_LIB; else export MI355_YOLO_LIB=$PWD/computer-vision-shoplifting-detection_amd/libmi355yolo_$name.so; fi
   echo "== $name"
   for args in "--steps 10 --warmup 3" "--model yolov8n-pose --batch 32 --steps 60 --warmup 10" "--model yolov8s-pose --batch 64 --steps 20 --warmup 5" "--model yolov8s-pose --batch 8 --steps 100 --warmup 20"; do
-    python bench.py --no-cpu-baseline --no-configs $args 2>/dev/null | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], 'fps', d['roofline']['achieved'], d['roofline']['unit'], end='   ')"
+    python bench.py --full --no-cpu-baseline --no-configs $args 2>/dev/null | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], 'fps', d['roofline']['achieved'], d['roofline']['unit'], end='   ')"
   done
   echo
 done

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT"
 export MI355_PLAN_CACHE=0
 EXP=$PWD/computer-vision-shoplifting-detection_amd/libmi355yolo_${AB_NAME:-exp}.so
-run() { echo "== $*"; env "$@" python bench.py --no-cpu-baseline --no-configs $ARGS 2>/dev/null | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], 'fps', d['ms_per_step'], 'ms/step', d['roofline']['achieved'], d['roofline']['unit'])"; }
+run() { echo "== $*"; env "$@" python bench.py --full --no-cpu-baseline --no-configs $ARGS 2>/dev/null | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], 'fps', d['ms_per_step'], 'ms/step', d['roofline']['achieved'], d['roofline']['unit'])"; }
 ARGS="--steps 10 --warmup 3"
 run A=1
 run MI355_YOLO_LIB=$EXP "$@"

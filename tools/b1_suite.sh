@@ -1,7 +1,7 @@
 #!/bin/bash
 # Small-batch latency experiments (run ON THE GPU BOX via gpurun): batch-1 / batch-32 throughput under the engine's knobs.
 cd "$GRAFT_REPO_ROOT"
-run() { echo "== $*"; env "$@" python bench.py --no-cpu-baseline $ARGS 2>/dev/null | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], 'fps', d['ms_per_step'], 'ms/step', d['roofline']['achieved'], 'TF', d['device_ms_per_step'])"; }
+run() { echo "== $*"; env "$@" python bench.py --full --no-cpu-baseline $ARGS 2>/dev/null | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], 'fps', d['ms_per_step'], 'ms/step', d['roofline']['achieved'], 'TF', d['device_ms_per_step'])"; }
 ARGS="--model yolov8n --batch 1 --chunk 1 --steps 400 --warmup 30"
 run MI355_SMALL_PT=0
 run MI355_SMALL_PT=1

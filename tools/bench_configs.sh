@@ -1,6 +1,6 @@
 #!/bin/bash
 # BASELINE.json's configurations on one GPU: bench.py with other --model / --size / --batch.
-run() { python bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$*', '|', d['value'], 'fps', d['ms_per_step'], 'ms/step', d['roofline']['achieved'], 'TF', d['roofline']['frac'])"; }
+run() { python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$*', '|', d['value'], 'fps', d['ms_per_step'], 'ms/step', d['roofline']['achieved'], 'TF', d['roofline']['frac'])"; }
 run --model yolov8n --batch 1 --chunk 1 --steps 300 --warmup 20
 run --model yolov8n --batch 512 --chunk 512
 run --model yolov8n --batch 512 --chunk 512 --half

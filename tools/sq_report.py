@@ -1,13 +1,14 @@
 """Per-kernel SQ counters of one bench pass from the four rocprofv3 --pmc passes of tools/collect_sq.sh.
-usage: sq_report.py [TAG=sq] [GHz=2.1]   (reads gpurun_out/TAG_{1..4}/*/*counter_collection.csv, last real pass of each run)"""
+usage: sq_report.py [TAG=sq] [GHz=2.1]   (reads $OUT/TAG_{1..4}/*/*counter_collection.csv, OUT defaulting to tools_out/; last real pass of each run)"""
 import collections, csv, glob, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("OUT") or os.path.join(ROOT, "tools_out")      # where tools/collect_sq.sh wrote
 tag = sys.argv[1] if len(sys.argv) > 1 else "sq"
 ghz = float(sys.argv[2]) if len(sys.argv) > 2 else 2.1
 data = collections.defaultdict(lambda: collections.defaultdict(float))
 dur, cnt = collections.defaultdict(float), collections.defaultdict(int)
 for i in range(1, 5):
-    f = glob.glob(os.path.join(ROOT, "gpurun_out", f"{tag}_{i}", "*", "*counter_collection.csv"))[0]
+    f = glob.glob(os.path.join(OUT, f"{tag}_{i}", "*", "*counter_collection.csv"))[0]
     rows = list(csv.DictReader(open(f)))
     start = max(int(r["Dispatch_Id"]) for r in rows if "::stem" in r["Kernel_Name"])      # last pass of the run
     seen = set()

@@ -1,20 +1,21 @@
-"""Turn the raw rocprofv3 output of tools/collect_profiles.sh (under gpurun_out/) into the committed profiles/ files.
+"""Turn the raw rocprofv3 output of tools/collect_profiles.sh (under $OUT, default tools_out/) into the committed profiles/ files.
 
 usage: summarize_profiles.py TAG BATCH [MODEL [SIZE [half]]]   (defaults: r01_v3 256 yolov8n 640)"""
 import collections, csv, glob, json, os, shutil, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("OUT") or os.path.join(ROOT, "tools_out")      # where the collection scripts wrote
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01_v3"
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 model = sys.argv[3] if len(sys.argv) > 3 else "yolov8n"
 size = int(sys.argv[4]) if len(sys.argv) > 4 else 640
 half = len(sys.argv) > 5 and sys.argv[5] == "half"
 es = 2 if half else 4
-g = lambda pat: max(glob.glob(os.path.join(ROOT, "gpurun_out", pat)), key=os.path.getmtime)   # newest run if stale ones linger
+g = lambda pat: max(glob.glob(os.path.join(OUT, pat)), key=os.path.getmtime)   # newest run if stale ones linger
 shutil.copy(g(f"{tag}_trace/*/*kernel_stats.csv"), os.path.join(ROOT, "profiles", f"{tag}_kernel_stats.csv"))
 with open(os.path.join(ROOT, "profiles", f"{tag}_bench_under_rocprof.json"), "w") as f:
-    f.write([l for l in open(os.path.join(ROOT, "gpurun_out", f"{tag}_trace.log")) if l.startswith('{"metric')][-1])
+    f.write([l for l in open(os.path.join(OUT, f"{tag}_trace.log")) if l.startswith('{"metric')][-1])
 rep = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "layer_report.py"), g(f"{tag}_trace/*/*kernel_trace.csv"), model, str(batch),
-                      str(size), str(es), os.path.join(ROOT, "gpurun_out", f"{tag}_trace.log")], capture_output=True, text=True)
+                      str(size), str(es), os.path.join(OUT, f"{tag}_trace.log")], capture_output=True, text=True)
 open(os.path.join(ROOT, "profiles", f"{tag}_layer_report.txt"), "w").write(rep.stdout)
 print(rep.stdout[-600:], rep.stderr[-2000:])
 
@@ -23,10 +24,10 @@ from cvsd_amd.graph import build_program, parse_model_name
 pg = build_program(*parse_model_name(model))
 # conv launches of one step: fewer than the module's convs (sibling convs merged, Conv3x3 -> Conv1x1 pairs fused where the
 # autotuner found that faster); bench.py reports the count it measured in the same process
-_fetch_line = json.loads([l for l in open(os.path.join(ROOT, "gpurun_out", f"{tag}_fetch.log")) if l.startswith('{"metric')][-1])
+_fetch_line = json.loads([l for l in open(os.path.join(OUT, f"{tag}_fetch.log")) if l.startswith('{"metric')][-1])
 n_conv = _fetch_line["roofline"]["launches_per_step"]
-plan_hashes = {k: json.loads([l for l in open(os.path.join(ROOT, "gpurun_out", f"{tag}_{k}.log")) if l.startswith('{"metric')][-1])["roofline"].get("plan_hash")
-               for k in ("trace", "fetch", "write") if os.path.exists(os.path.join(ROOT, "gpurun_out", f"{tag}_{k}.log"))}
+plan_hashes = {k: json.loads([l for l in open(os.path.join(OUT, f"{tag}_{k}.log")) if l.startswith('{"metric')][-1])["roofline"].get("plan_hash")
+               for k in ("trace", "fetch", "write") if os.path.exists(os.path.join(OUT, f"{tag}_{k}.log"))}
 is_conv = lambda name: "conv_igemm" in name or "conv1x1_" in name or "conv_splitk" in name or "conv_group" in name or "conv3x3_lw" in name
 
 
