@@ -65,6 +65,10 @@ SIGNATURES = {
                                           _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
     "mi355_yolo_infer_device_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                                 _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi355_yolo_infer_multi": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_float, C.c_float,
+                                         _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
+    "mi355_yolo_raw_head_multi": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            _i32p, _i32p]),
     "mi355_yolo_stream": (C.c_void_p, [C.c_void_p]),
     "mi355_yolo_sync": (C.c_int, [C.c_void_p]),
     "mi355_yolo_raw_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -135,6 +139,8 @@ SIGNATURES = {
                                     C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mi355_letterbox_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
     "mi355_op_letterbox": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mi355_letterbox_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _P(C.c_double)]),
+    "mi355_op_letterbox_multi": (C.c_int, [C.c_int, C.c_void_p, _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_void_p]),
     "mi355_op_nms": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,
                                C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
 }

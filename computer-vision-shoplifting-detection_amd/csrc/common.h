@@ -151,6 +151,19 @@ struct LetterboxArgs {
     int B;
 };
 const char* launch_letterbox(const LetterboxArgs& a, hipStream_t st);
+// Per-frame letterbox (a batch of frames of different sizes, engine_multi.hip): one descriptor per frame in device memory, every
+// frame letterboxed into the same dense [B][Hd][Wd][3] canvas.  The resize tables of all frames sit in ONE int buffer (x table at
+// xoff, y table at yoff, 3 ints per destination index as in LetterboxArgs).
+struct LetterboxFrame {
+    const uint8_t* src; int H, W, row_stride;   // source frame (rows row_stride bytes apart)
+    int Hr, Wr, top, left;                      // resized region size / placement inside the canvas
+    int xoff, yoff, resize, pad_;               // table offsets (ints) into `tabs`; 0 = plain copy of the source
+};
+struct LetterboxMultiArgs {
+    const LetterboxFrame* frames; const int* tabs;   // device
+    uint8_t* dst; int Hd, Wd, B;                     // canvas; Wd % 4 == 0
+};
+const char* launch_letterbox_multi(const LetterboxMultiArgs& a, hipStream_t st);
 
 // ---- head decode + NMS, post_kernels.hip ----------------------------------------------------------------
 struct HeadLevelArgs { const float* buf; int cs; int box_off, cls_off, kpt_off; int H, W, stride, anchor0; };
@@ -180,6 +193,8 @@ struct NmsArgs {
     int Apow2;
     // scale-back (A.6); identity when scale_back == 0
     int scale_back; float gain; float pad_x, pad_y, kpad_x, kpad_y; float orig_w, orig_h;
+    const float* frame_geom = nullptr;         // device [B][7] gain, pad_x, pad_y, kpad_x, kpad_y, orig_w, orig_h per frame (mixed batches),
+                                               // read instead of the scalars above when non-null
     void* out_rows;                            // device mi355_det [B][max_det]
     int* out_counts;                           // device [B] (+ [B, 3B): scratch of the sort kernels)
     int* host_counts = nullptr;                // optional: pinned host [B], written by the greedy kernel beside out_counts

@@ -57,6 +57,8 @@ struct DevConv { float* wpk = nullptr; float* bias = nullptr; float* w_raw = nul
 
 // LetterBox geometry (data/augment.py:LetterBox, auto=True, scaleup=True, center=True, stride 32) and the
 // scale-back constants of utils/ops.py:scale_boxes / scale_coords, in the same double arithmetic as Python.
+// auto_pad = false: LetterBox((imgsz, imgsz), auto=False), the square canvas BasePredictor.pre_transform uses when the frames of
+// one call do not all have the same shape (Hl = Wl = imgsz, the padding is not reduced modulo 32).
 struct Geometry {
     int h0, w0, Hl, Wl;          // original and letterboxed size
     int Hr, Wr, top, left;       // resized region
@@ -67,13 +69,13 @@ struct Geometry {
 inline double py_round(double x) { return std::nearbyint(x); }   // round-half-even, like Python's round()
 inline size_t round_up_sz(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
-inline Geometry make_geometry(int h0, int w0, int imgsz) {
+inline Geometry make_geometry(int h0, int w0, int imgsz, bool auto_pad = true) {
     Geometry g{};
     g.h0 = h0; g.w0 = w0;
     const double r = std::min((double)imgsz / h0, (double)imgsz / w0);
     g.Wr = (int)py_round(w0 * r); g.Hr = (int)py_round(h0 * r);
     double dw = imgsz - g.Wr, dh = imgsz - g.Hr;
-    dw = std::fmod(dw, 32.0); dh = std::fmod(dh, 32.0);
+    if (auto_pad) { dw = std::fmod(dw, 32.0); dh = std::fmod(dh, 32.0); }
     dw /= 2; dh /= 2;
     const int top = (int)py_round(dh - 0.1), bottom = (int)py_round(dh + 0.1);
     const int left = (int)py_round(dw - 0.1), right = (int)py_round(dw + 0.1);
@@ -204,6 +206,11 @@ struct mi355_yolo {
     unsigned* d_cmask = nullptr; unsigned* h_cmask = nullptr; int cmask_words = 0;
     int* d_xtab = nullptr; int* d_ytab = nullptr; int tab_h0 = -1, tab_w0 = -1, tab_imgsz = -1;
     float* d_rawhead = nullptr; size_t rawhead_floats = 0;
+    // batches of frames of different sizes (engine_multi.hip): pinned staging of host frames (two chunk slots), and ONE device buffer
+    // holding the per-frame letterbox descriptors, the per-frame scale-back constants and the resize tables, uploaded from a pinned
+    // image of it (h_multi) -- only when that image changed since the last upload (the same cameras call after call)
+    uint8_t* h_stage = nullptr; size_t h_stage_bytes = 0;
+    char* d_multi = nullptr; char* h_multi = nullptr; size_t multi_cap = 0, multi_bytes = 0;
     unsigned long long plan_hash = 0;   // fingerprint of the candidate lists + the chosen indices of the current shape
     int plan_source = 0, plan_launches = 0;   // 0 static guess (autotune off), 1 memory, 2 this machine's plan cache, 3 tuned now, 4 shipped plan file; launches of one pass (stem..last conv)
     bool async_pending = false;         // mi355_yolo_infer_device_async work may still be in flight on `stream`
@@ -255,9 +262,30 @@ int ensure_shape(mi355_yolo* h, int nb, int Hl, int Wl);
 int launch_net(mi355_yolo* h, Prof& pf, const uint8_t* stem_in, int nb, const Geometry& g, bool full_pred);
 int run_chunk(mi355_yolo* h, Prof& pf, const uint8_t* frames_dev, int nb, const Geometry& g, bool full_pred);
 int prepare_geometry(mi355_yolo* h, const Geometry& g, int imgsz);
+struct MultiFrames;
 int infer_impl(mi355_yolo* h, const uint8_t* src, bool src_on_device, int n, int height, int width, int row_stride,
                float conf, float iou, const int* classes, int n_classes, int max_det, int imgsz,
                mi355_det* out_rows, int cap, int* out_counts, mi355_det* dev_rows = nullptr, int* dev_counts = nullptr,
-               int* dev_total = nullptr);
+               int* dev_total = nullptr, const MultiFrames* mf = nullptr);
+
+// engine_multi.hip: one call over frames of different sizes (mi355_yolo_infer_multi).  All frames the same shape: the rect
+// geometry of make_geometry (what mi355_yolo_infer does with them stacked); otherwise every frame is letterboxed into the square
+// imgsz x imgsz canvas (auto_pad = false) -- Ultralytics' BasePredictor.pre_transform rule.
+struct MultiFrames {
+    const uint8_t* const* frames; const int* heights; const int* widths; const int* row_strides;   // row_strides may be NULL (w*3)
+    bool on_device;
+};
+struct MultiCall {
+    int Hd = 0, Wd = 0;                       // canvas: rect letterbox size of the common shape, or imgsz x imgsz
+    std::vector<Geometry> g;                  // per frame
+    std::vector<size_t> stage_off;            // host frames: byte offset of frame i inside its chunk's staging slot (rows w*3 apart)
+    size_t slot_bytes = 0;                    // host frames: bytes of the largest chunk
+    const LetterboxFrame* d_desc = nullptr; const float* d_geom = nullptr; const int* d_tabs = nullptr;
+};
+int multi_check(const MultiFrames& mf, int n);
+void multi_prepare(const MultiFrames& mf, int n, int nb, int imgsz, MultiCall& mc);
+int multi_upload(mi355_yolo* h, const MultiFrames& mf, int n, int nb, MultiCall& mc);
+int multi_stage_chunk(mi355_yolo* h, const MultiFrames& mf, const MultiCall& mc, int s0, int m, int nb, int slot);
+int run_chunk_multi(mi355_yolo* h, Prof& pf, const MultiCall& mc, int s0, int m, bool full_pred);
 
 }  // namespace mi355

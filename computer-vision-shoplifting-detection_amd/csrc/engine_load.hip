@@ -34,6 +34,8 @@ mi355_yolo::~mi355_yolo() {
     if (d_cmask) (void)hipFree(d_cmask); if (h_cmask) (void)hipHostFree(h_cmask);
     if (d_xtab) (void)hipFree(d_xtab); if (d_ytab) (void)hipFree(d_ytab);
     if (d_rawhead) (void)hipFree(d_rawhead);
+    if (h_stage) (void)hipHostFree(h_stage);
+    if (d_multi) (void)hipFree(d_multi); if (h_multi) (void)hipHostFree(h_multi);
     if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1);
     for (auto e : pev) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) { if (ev_copied[i]) (void)hipEventDestroy(ev_copied[i]); if (ev_consumed[i]) (void)hipEventDestroy(ev_consumed[i]); }

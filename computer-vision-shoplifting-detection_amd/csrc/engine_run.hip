@@ -205,10 +205,15 @@ static int collect_timing(mi355_yolo* h, Prof& pf, int frames) {
 // DEVICE buffers; nothing is copied to the host and the call returns with the work enqueued on the engine's stream)
 int infer_impl(mi355_yolo* h, const uint8_t* src, bool src_on_device, int n, int height, int width, int row_stride,
                       float conf, float iou, const int* classes, int n_classes, int max_det, int imgsz,
-                      mi355_det* out_rows, int cap, int* out_counts, mi355_det* dev_rows, int* dev_counts, int* dev_total) {
+                      mi355_det* out_rows, int cap, int* out_counts, mi355_det* dev_rows, int* dev_counts, int* dev_total,
+                      const MultiFrames* mf) {
     const bool async_out = dev_rows != nullptr;
-    if (!h || !src || (!async_out && (!out_rows || !out_counts)) || (async_out && (!dev_counts || !dev_total)))
+    if (!h || !(src || mf) || (!async_out && (!out_rows || !out_counts)) || (async_out && (!dev_counts || !dev_total)))
         return fail(MI355_EINVAL, "null argument");
+    if (mf) {                           // frames of different sizes: the size arguments are per frame (mi355_yolo_infer_multi)
+        const int rc0 = multi_check(*mf, n); if (rc0) return rc0;
+        src_on_device = mf->on_device; height = width = 1; row_stride = 0;
+    }
     if (n <= 0 || height <= 0 || width <= 0) return fail(MI355_EINVAL, "n, height and width must be positive");
     if (max_det <= 0) max_det = 300;
     if (max_det > 1024) return fail(MI355_EINVAL, "max_det must be <= 1024");
@@ -225,26 +230,38 @@ int infer_impl(mi355_yolo* h, const uint8_t* src, bool src_on_device, int n, int
     }
     const Geometry g = make_geometry(height, width, imgsz);
     const int nb = std::min(n, h->chunk);
-    int rc = ensure_shape(h, nb, g.Hl, g.Wl); if (rc) return rc;
-    rc = prepare_geometry(h, g, imgsz); if (rc) return rc;
+    MultiCall mc;
+    int rc = 0;
+    if (mf) {
+        multi_prepare(*mf, n, nb, imgsz, mc);
+        rc = ensure_shape(h, nb, mc.Hd, mc.Wd); if (rc) return rc;
+    } else {
+        rc = ensure_shape(h, nb, g.Hl, g.Wl); if (rc) return rc;
+        rc = prepare_geometry(h, g, imgsz); if (rc) return rc;
+    }
 
-    const size_t frame_bytes = (size_t)height * width * 3;
+    const size_t frame_bytes = mf ? mc.slot_bytes : (size_t)height * width * 3;   // mf: slot = the largest chunk's frames, packed
     const uint8_t* dev_frames = src;
     // Host frames: a double-buffered staging area of two chunks.  Chunk k+1 is copied (on copy_stream) while chunk k's
     // kernels run; a slot is only overwritten after the kernels that read it (letterbox / stem) have been passed.
     auto copy_chunk = [&](int s0, int m, int slot) -> int {
+        if (mf) return multi_stage_chunk(h, *mf, mc, s0, m, nb, slot);
         HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_consumed[slot], 0));
         HIPCHK(hipMemcpy2DAsync(h->d_in + (size_t)slot * nb * frame_bytes, (size_t)width * 3, src + (size_t)s0 * height * row_stride,
                                 (size_t)row_stride, (size_t)width * 3, (size_t)height * m, hipMemcpyHostToDevice, h->copy_stream));
         HIPCHK(hipEventRecord(h->ev_copied[slot], h->copy_stream));
         return MI355_OK;
     };
+    const size_t slot_frames = mf ? 1 : (size_t)nb;         // frame_bytes units per staging slot
     if (!src_on_device) {
-        if (h->d_in_bytes < frame_bytes * nb * 2) {
+        if (h->d_in_bytes < frame_bytes * slot_frames * 2) {
             if (h->d_in) (void)hipFree(h->d_in);
             h->d_in = nullptr; h->d_in_bytes = 0;
-            HIPCHK(hipMalloc(&h->d_in, frame_bytes * nb * 2)); h->d_in_bytes = frame_bytes * nb * 2;
+            HIPCHK(hipMalloc(&h->d_in, frame_bytes * slot_frames * 2)); h->d_in_bytes = frame_bytes * slot_frames * 2;
         }
+    }
+    if (mf) { rc = multi_upload(h, *mf, n, nb, mc); if (rc) return rc; }    // descriptors point into d_in (host frames)
+    if (!src_on_device) {
         HIPCHK(hipEventRecord(h->ev_consumed[0], h->stream));
         HIPCHK(hipEventRecord(h->ev_consumed[1], h->stream));
         rc = copy_chunk(0, std::min(nb, n), 0); if (rc) return rc;
@@ -303,13 +320,13 @@ int infer_impl(mi355_yolo* h, const uint8_t* src, bool src_on_device, int n, int
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     for (int s = 0, ci = 0; s < n; s += nb, ++ci) {
         const int m = std::min(nb, n - s);
-        const uint8_t* chunk_frames = dev_frames + (size_t)s * frame_bytes;
+        const uint8_t* chunk_frames = mf ? nullptr : dev_frames + (size_t)s * frame_bytes;
         if (!src_on_device) {
             const int slot = ci & 1;
             HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copied[slot], 0));
-            chunk_frames = h->d_in + (size_t)slot * nb * frame_bytes;
+            chunk_frames = h->d_in + (size_t)slot * slot_frames * frame_bytes;
         }
-        rc = run_chunk(h, pf, chunk_frames, m, g, false); if (rc) return rc;
+        rc = mf ? run_chunk_multi(h, pf, mc, s, m, false) : run_chunk(h, pf, chunk_frames, m, g, false); if (rc) return rc;
         if (!src_on_device) {
             // the frames of this slot have been consumed once the net's kernels are enqueued behind this event; the
             // (host-blocking) copy of the next chunk is issued AFTER this chunk's launches so that it overlaps them
@@ -323,6 +340,7 @@ int infer_impl(mi355_yolo* h, const uint8_t* src, bool src_on_device, int n, int
         na.class_mask = cmask; na.keys = h->keys; na.Apow2 = h->Apow2;
         na.scale_back = 1; na.gain = (float)g.gain; na.pad_x = (float)g.pad_x; na.pad_y = (float)g.pad_y;
         na.kpad_x = (float)g.kpad_x; na.kpad_y = (float)g.kpad_y; na.orig_w = (float)width; na.orig_h = (float)height;
+        if (mf) na.frame_geom = mc.d_geom + (size_t)s * 7;      // this chunk's frames' rows of [n][7]
         na.out_rows = h->d_rows + (size_t)s * max_det;
         if (direct_host) {                       // rows and counts straight into the pinned host buffers (slot layout: frame i at i * max_det)
             na.out_rows = host_rows_dev;

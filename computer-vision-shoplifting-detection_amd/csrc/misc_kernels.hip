@@ -945,4 +945,62 @@ const char* launch_letterbox(const LetterboxArgs& a, hipStream_t st) {
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 
+// Per-frame letterbox of a batch whose frames differ in size: frame b's geometry comes from its descriptor, the arithmetic is
+// letterbox_kernel's (same integer INTER_LINEAR, same 114 border), so every byte equals what the oracle computes for that frame.
+// One thread emits 4 consecutive pixels of a canvas row (Wd % 4 == 0): 12 bytes = three dword stores at a 4-byte aligned offset.
+__device__ __forceinline__ unsigned letterbox_px(const LetterboxFrame& f, const int* tabs, int x, int y) {
+    const int rx = x - f.left, ry = y - f.top;
+    if ((unsigned)rx >= (unsigned)f.Wr || (unsigned)ry >= (unsigned)f.Hr) return 0x727272u;   // 114, 114, 114
+    if (!f.resize) {
+        const uint8_t* p = f.src + (size_t)ry * f.row_stride + (size_t)rx * 3;
+        return (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+    }
+    const int* xt = tabs + f.xoff + rx * 3;
+    const int* yt = tabs + f.yoff + ry * 3;
+    const int x0 = xt[0], ax0 = xt[1], ax1 = xt[2];
+    const int y0 = yt[0], by0 = yt[1], by1 = yt[2];
+    const int x1 = x0 + 1 < f.W ? x0 + 1 : f.W - 1;
+    const int y1 = y0 + 1 < f.H ? y0 + 1 : f.H - 1;
+    const uint8_t* r0 = f.src + (size_t)y0 * f.row_stride;
+    const uint8_t* r1 = f.src + (size_t)y1 * f.row_stride;
+    unsigned px = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int s0 = r0[x0 * 3 + c] * ax0 + r0[x1 * 3 + c] * ax1;
+        const int s1 = r1[x0 * 3 + c] * ax0 + r1[x1 * 3 + c] * ax1;
+        int v = (((by0 * (s0 >> 4)) >> 16) + ((by1 * (s1 >> 4)) >> 16) + 2) >> 2;
+        v = v < 0 ? 0 : (v > 255 ? 255 : v);
+        px |= (unsigned)v << (8 * c);
+    }
+    return px;
+}
+
+__global__ __launch_bounds__(256) void letterbox_multi_kernel(LetterboxMultiArgs a) {
+    const int q4 = a.Wd >> 2;                              // 4-pixel groups per canvas row
+    const long per_frame = (long)a.Hd * q4;
+    const long total = (long)a.B * per_frame;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / per_frame);
+        const long r = i - (long)b * per_frame;
+        const int y = (int)(r / q4);
+        const int x = (int)(r - (long)y * q4) * 4;
+        const LetterboxFrame f = a.frames[b];
+        const unsigned p0 = letterbox_px(f, a.tabs, x, y), p1 = letterbox_px(f, a.tabs, x + 1, y);
+        const unsigned p2 = letterbox_px(f, a.tabs, x + 2, y), p3 = letterbox_px(f, a.tabs, x + 3, y);
+        unsigned* d = (unsigned*)(a.dst + (size_t)i * 12);
+        d[0] = p0 | (p1 << 24);
+        d[1] = (p1 >> 8) | (p2 << 16);
+        d[2] = (p2 >> 16) | (p3 << 8);
+    }
+}
+
+const char* launch_letterbox_multi(const LetterboxMultiArgs& a, hipStream_t st) {
+    if (a.Wd & 3) return "letterbox_multi: canvas width must be a multiple of 4";
+    const long total = (long)a.B * a.Hd * (a.Wd / 4);
+    const unsigned grid = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    hipLaunchKernelGGL(letterbox_multi_kernel, dim3(grid), dim3(256), 0, st, a);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
 }  // namespace mi355

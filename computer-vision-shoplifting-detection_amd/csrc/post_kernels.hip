@@ -466,6 +466,12 @@ __device__ __forceinline__ void nms_greedy_body(const NmsArgs& a, const int b, c
     unsigned* rows_w = (unsigned*)((mi355_det*)a.out_rows + (size_t)b * a.max_det);
     const int nkf = a.nk < MI355_MAX_KPT_FLOATS ? a.nk : MI355_MAX_KPT_FLOATS;
     const int kd = a.kdim > 0 ? a.kdim : 1;
+    // scale-back constants: the call's scalars, or frame b's row of a mixed batch (same expressions, per-frame values)
+    float gain = a.gain, pad_x = a.pad_x, pad_y = a.pad_y, kpad_x = a.kpad_x, kpad_y = a.kpad_y, orig_w = a.orig_w, orig_h = a.orig_h;
+    if (a.frame_geom) {
+        const float* fg = a.frame_geom + (size_t)b * 7;
+        gain = fg[0]; pad_x = fg[1]; pad_y = fg[2]; kpad_x = fg[3]; kpad_y = fg[4]; orig_w = fg[5]; orig_h = fg[6];
+    }
     for (int idx = threadIdx.x; idx < nk * RW; idx += 64 * NMS_WAVES) {
         const int k = idx / RW, q = idx - k * RW;
         const int an = kan[k];
@@ -477,9 +483,9 @@ __device__ __forceinline__ void nms_greedy_body(const NmsArgs& a, const int b, c
             const float c = isx ? p[0] : p[1];
             float v = q < 2 ? c - half_ext : c + half_ext;
             if (a.scale_back) {
-                v -= isx ? a.pad_x : a.pad_y;
-                v /= a.gain;
-                v = fminf(fmaxf(v, 0.f), isx ? a.orig_w : a.orig_h);
+                v -= isx ? pad_x : pad_y;
+                v /= gain;
+                v = fminf(fmaxf(v, 0.f), isx ? orig_w : orig_h);
             }
             w = __float_as_uint(v);
         } else if (q == 4) {
@@ -493,9 +499,9 @@ __device__ __forceinline__ void nms_greedy_body(const NmsArgs& a, const int b, c
             float v = p[4 + a.nc + j];
             if (a.scale_back && (j % kd) < 2) {
                 const bool isx = (j % kd) == 0;
-                v -= isx ? a.kpad_x : a.kpad_y;
-                v /= a.gain;
-                v = fminf(fmaxf(v, 0.f), isx ? a.orig_w : a.orig_h);
+                v -= isx ? kpad_x : kpad_y;
+                v /= gain;
+                v = fminf(fmaxf(v, 0.f), isx ? orig_w : orig_h);
             }
             w = __float_as_uint(v);
         }

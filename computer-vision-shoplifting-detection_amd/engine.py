@@ -126,9 +126,42 @@ class YOLO:
         return i.n_convs, int(i.n_params), 0, 2.0 * i.macs_640 / 1e9     # (layers, params, gradients, GFLOPs)
 
     # ------------------------------------------------------------------------------------------ inference
+    class _Ragged:
+        """Frames of different (h, w) in one call (several cameras): host arrays or CUDA tensors on the engine's GPU, each passed to
+        ``mi355_yolo_infer_multi`` by pointer with its own row stride.  The engine letterboxes them to the square ``imgsz x imgsz``
+        canvas, as Ultralytics' ``BasePredictor.pre_transform`` does for a batch whose shapes differ."""
+        def __init__(self, frames, on_device: bool):
+            self.on_device = bool(on_device)
+            self.frames = []
+            for f in frames:
+                if on_device:
+                    if f.dtype != torch.uint8 or f.ndim != 3 or f.shape[-1] != 3:
+                        raise ValueError("tensor frames must be uint8 [H,W,3] BGR")
+                    if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.shape[1]:
+                        f = f.contiguous()
+                else:
+                    f = np.asarray(f)
+                    if f.dtype != np.uint8 or f.ndim != 3 or f.shape[-1] != 3:
+                        raise ValueError("frames must be uint8 arrays of shape [H,W,3] (BGR, as cv2 delivers them)")
+                    if f.strides[2] != 1 or f.strides[1] != 3 or f.strides[0] < 3 * f.shape[1]:
+                        f = np.ascontiguousarray(f)
+                self.frames.append(f)                       # kept alive for the call: the engine reads them by pointer
+            n = len(self.frames)
+            self.shape = (n,)
+            self.shapes = [(int(f.shape[0]), int(f.shape[1])) for f in self.frames]
+            self.heights = np.array([s[0] for s in self.shapes], np.int32)
+            self.widths = np.array([s[1] for s in self.shapes], np.int32)
+            self.row_strides = np.array([f.stride(0) if on_device else f.strides[0] for f in self.frames], np.int32)
+            self.ptrs = (C.c_void_p * n)(*[f.data_ptr() if on_device else f.ctypes.data for f in self.frames])
+
+        def args(self):
+            i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+            return self.ptrs, i32(self.heights), i32(self.widths), i32(self.row_strides), int(self.on_device), len(self.frames)
+
     @staticmethod
     def _as_batch(source):
-        """-> (array-or-tensor [N,H,W,3] uint8, list of originals or None)"""
+        """-> (array-or-tensor [N,H,W,3] uint8, list of originals or None); a list of frames of different shapes -> (_Ragged, list of
+        originals or None)"""
         if isinstance(source, torch.Tensor):
             if source.dtype != torch.uint8 or source.ndim != 4 or source.shape[-1] != 3:
                 raise ValueError("tensor sources must be uint8 [N,H,W,3] BGR frames")
@@ -143,8 +176,15 @@ class YOLO:
             if not source:
                 raise ValueError("empty source")
             shapes = {tuple(np.shape(f)) for f in source}
+            on_dev = [isinstance(f, torch.Tensor) and f.is_cuda for f in source]
+            if any(on_dev):
+                if not all(on_dev):
+                    raise ValueError("a list of frames must be all host arrays or all CUDA tensors")
+                if len(shapes) == 1:
+                    return YOLO._as_batch(torch.stack(list(source)))
+                return YOLO._Ragged(source, True), None
             if len(shapes) != 1:
-                raise ValueError("frames of different shapes in one call are not supported; call once per shape")
+                return YOLO._Ragged(source, False), list(source)
             arr = np.ascontiguousarray(np.stack([np.asarray(f) for f in source]))
             return YOLO._as_batch(arr)[0], list(source)
         raise TypeError(f"unsupported source type {type(source).__name__}: pass decoded BGR uint8 frames "
@@ -160,7 +200,8 @@ class YOLO:
         lib = _lib.lib()
         hnd = self._handle(half)
         self._last_handle = hnd
-        n, h, w = int(batch.shape[0]), int(batch.shape[1]), int(batch.shape[2])
+        n = int(batch.shape[0])
+        h, w = (0, 0) if isinstance(batch, YOLO._Ragged) else (int(batch.shape[1]), int(batch.shape[2]))
         rows = np.empty((n, max_det, _lib.DET_WORDS), dtype=np.float32)    # only rows[i, :counts[i]] are written / meaningful
         counts = np.zeros(n, dtype=np.int32)
         cls_arr = None
@@ -171,6 +212,14 @@ class YOLO:
             ncls = len(cl)
         cp = counts.ctypes.data_as(C.POINTER(C.c_int))
         with self._lock:
+            if isinstance(batch, YOLO._Ragged):
+                if batch.on_device:
+                    if any(f.device.index != self.device for f in batch.frames):
+                        raise ValueError("frames live on a different GPU than the engine")
+                    torch.cuda.current_stream(batch.frames[0].device).synchronize()   # engine runs on its own stream
+                _lib.check(lib.mi355_yolo_infer_multi(hnd, *batch.args(), conf, iou, cls_arr, ncls, max_det, imgsz, rows.ctypes.data,
+                                                      max_det, cp))
+                return rows, counts, batch.shapes
             if isinstance(batch, YOLO._DeviceFrames):
                 _lib.check(lib.mi355_yolo_infer_device(hnd, batch.ptr, n, h, w, conf, iou, cls_arr, ncls, max_det, imgsz, rows.ctypes.data, max_det, cp))
                 return rows, counts, (h, w)
@@ -250,7 +299,8 @@ class YOLO:
     def detect_rows(self, batch, conf: float = 0.25, iou: float = 0.7, classes=None, max_det: int = 300, imgsz: int = 640, half=None):
         """``Results.boxes.data`` of every frame of ``batch`` -- float32 [M, 6] rows x1, y1, x2, y2, conf, cls -- and the frames' (h, w),
         without building the Results objects (a sweep reads nothing else: cvsd_amd/sweep.py).  ``batch``: what :meth:`predict` takes
-        after stacking, or frames already on the engine's GPU (:class:`_DeviceFrames`)."""
+        after stacking, or frames already on the engine's GPU (:class:`_DeviceFrames`).  For frames of different shapes
+        (:class:`_Ragged`) the second value is the list of every frame's (h, w)."""
         rows, counts, shape = self._infer_rows(batch, float(conf), float(iou), classes, int(max_det), int(imgsz), half)
         out = []
         for i in range(len(counts)):
@@ -276,7 +326,8 @@ class YOLO:
                 nk = self.kpt_shape[0] * self.kpt_shape[1]
                 kp = torch.from_numpy(r[:, 7:7 + nk].reshape(len(r), *self.kpt_shape).copy())
             res = Results(originals[i] if originals is not None else None, f"image{i}.jpg", self.names,
-                          boxes=torch.from_numpy(data), keypoints=kp.clone() if kp is not None else None, orig_shape=shape,
+                          boxes=torch.from_numpy(data), keypoints=kp.clone() if kp is not None else None,
+                          orig_shape=shape[i] if isinstance(shape, list) else shape,
                           speed={"preprocess": 0.0, "inference": per_img_ms, "postprocess": 0.0},
                           anchor_idx=ints[:, 1].copy())
             if kp is not None:
@@ -297,6 +348,8 @@ class YOLO:
             # the frame preparation and the optical flow of its motion compensation run on the engine's GPU (csrc/gmc_kernels.hip)
             self._tracker = BYTETracker(gmc_device=getattr(self, "device", None))
         batch, originals = self._as_batch(source)
+        if isinstance(batch, YOLO._Ragged):
+            raise ValueError("frames of different shapes in one call are not supported; call once per shape")
         results = []
         for i in range(int(batch.shape[0])):
             frame = originals[i] if originals is not None else batch[i].cpu().numpy()
@@ -329,10 +382,20 @@ class YOLO:
 
     # ------------------------------------------------------------------------------------------ test hooks
     def raw_head(self, source, imgsz: int = 640, half: Optional[bool] = None) -> np.ndarray:
-        """Pre-NMS head tensor ``[N, 4+nc+nk, A]`` exactly as ``Detect/Pose.forward`` returns it."""
+        """Pre-NMS head tensor ``[N, 4+nc+nk, A]`` exactly as ``Detect/Pose.forward`` returns it (a list of frames of different
+        shapes: the square ``imgsz x imgsz`` canvas, A = its anchors)."""
         lib = _lib.lib()
         hnd = self._handle(half)
         batch, _ = self._as_batch(source)
+        if isinstance(batch, YOLO._Ragged):
+            ch, an = C.c_int(), C.c_int()
+            _lib.check(lib.mi355_yolo_raw_head_multi(hnd, *batch.args(), imgsz, None, C.byref(ch), C.byref(an)))
+            out = np.empty((len(batch.frames), ch.value, an.value), dtype=np.float32)
+            with self._lock:
+                if batch.on_device:
+                    torch.cuda.current_stream(batch.frames[0].device).synchronize()
+                _lib.check(lib.mi355_yolo_raw_head_multi(hnd, *batch.args(), imgsz, out.ctypes.data, C.byref(ch), C.byref(an)))
+            return out
         if isinstance(batch, torch.Tensor):
             batch = batch.cpu().numpy()
         n, h, w = batch.shape[:3]

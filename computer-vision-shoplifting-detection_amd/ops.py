@@ -122,6 +122,16 @@ def letterbox(bgr_u8: np.ndarray, imgsz: int = 640, device: int = 0) -> np.ndarr
     return out
 
 
+def letterbox_multi(frames: Sequence[np.ndarray], imgsz: int = 640, device: int = 0) -> np.ndarray:
+    """Frames of any (h, w) (row strides honoured) -> the square [n, imgsz, imgsz, 3] canvas of a mixed batch (LetterBox auto=False)."""
+    from .engine import YOLO
+    rb = YOLO._Ragged(frames, False)
+    ptrs, hs, ws, rs, _, n = rb.args()
+    out = np.empty((n, imgsz, imgsz, 3), dtype=np.uint8)
+    _lib.check(_lib.lib().mi355_op_letterbox_multi(device, ptrs, hs, ws, rs, n, imgsz, out.ctypes.data))
+    return out
+
+
 def nms(pred: np.ndarray, nc: int, conf: float = 0.25, iou: float = 0.7, classes: Optional[Sequence[int]] = None,
         max_det: int = 300, device: int = 0):
     """non_max_suppression on pred [N, 4+nc+extra, A] -> list of (rows [n,6+extra], anchor_idx [n])."""

@@ -136,6 +136,18 @@ int  mi355_yolo_info(const mi355_yolo* h, mi355_model_info* info);
 int  mi355_yolo_infer(mi355_yolo* h, const uint8_t* bgr_nhwc, int n, int height, int width, int row_stride_bytes,
                       float conf, float iou, const int* classes, int n_classes, int max_det, int imgsz,
                       mi355_det* out_rows, int out_capacity_per_image, int* out_counts);
+/* One call over n frames that need not share a size (several cameras at different resolutions) -- BasePredictor.pre_transform:
+ * when every frame has the same (h, w) the rect letterbox of mi355_yolo_infer is used (same rows as that call on the stacked
+ * frames); otherwise every frame is letterboxed to the square imgsz x imgsz canvas (LetterBox auto=False) and its rows are scaled
+ * back against its own shape (utils/ops.py:scale_boxes / scale_coords).
+ *   frames[i]          frame i, heights[i] x widths[i] x 3 uint8 BGR; rows row_strides[i] bytes apart (row_strides NULL or
+ *                      row_strides[i] == 0: widths[i]*3).  frames_on_device = 0: HOST memory (packed chunk by chunk into pinned
+ *                      staging, one host-to-device copy per chunk); 1: memory of the engine's device.
+ *   other arguments    as mi355_yolo_infer; out_rows / out_counts in frame order. */
+int  mi355_yolo_infer_multi(mi355_yolo* h, const uint8_t* const* frames, const int* heights, const int* widths,
+                            const int* row_strides, int frames_on_device, int n, float conf, float iou, const int* classes,
+                            int n_classes, int max_det, int imgsz, mi355_det* out_rows, int out_capacity_per_image,
+                            int* out_counts);
 /* Same with the frames already resident in DEVICE memory (dense n x h x w x 3); outputs still go to host. */
 int  mi355_yolo_infer_device(mi355_yolo* h, const uint8_t* bgr_nhwc_dev, int n, int height, int width,
                              float conf, float iou, const int* classes, int n_classes, int max_det, int imgsz,
@@ -161,6 +173,12 @@ int  mi355_yolo_sync(mi355_yolo* h);
  * out may be NULL to query *out_channels / *out_anchors for the given frame size. */
 int  mi355_yolo_raw_head(mi355_yolo* h, const uint8_t* bgr_nhwc, int n, int height, int width, int row_stride_bytes,
                          int imgsz, float* out, int* out_channels, int* out_anchors);
+
+/* mi355_yolo_raw_head for the frames of mi355_yolo_infer_multi: out[n][4+nc+nk][A] with A the anchors of the canvas (imgsz x imgsz
+ * for frames of different sizes).  out may be NULL to query *out_channels / *out_anchors. */
+int  mi355_yolo_raw_head_multi(mi355_yolo* h, const uint8_t* const* frames, const int* heights, const int* widths,
+                               const int* row_strides, int frames_on_device, int n, int imgsz, float* out, int* out_channels,
+                               int* out_anchors);
 
 /* Launch plans of the shape last run: plan_hash identifies the candidate lists AND the choice per conv (two runs with the same
  * hash launch the same kernels with the same grids); source 0 = static guess (autotune off), 1 = this process's memory,
@@ -351,6 +369,14 @@ int  mi355_op_stem_f16(int device_id, const uint8_t* bgr, int n, int h, int w, c
  * out must hold n * out_h * out_w * 3 bytes where (out_h,out_w) = mi355_letterbox_shape(). */
 int  mi355_letterbox_shape(int height, int width, int imgsz, int* out_h, int* out_w);
 int  mi355_op_letterbox(int device_id, const uint8_t* bgr, int n, int height, int width, int imgsz, uint8_t* out);
+/* Host-only: the letterbox geometry the engine uses for one frame.  auto_pad = 1: LetterBox auto=True (rect, padding modulo 32);
+ * 0: auto=False (square imgsz x imgsz).  i6 = Hl, Wl, Hr, Wr, top, left; d5 = the scale_boxes / scale_coords constants
+ * gain, pad_x, pad_y (rounded, boxes), kpad_x, kpad_y (unrounded, keypoints), in double. */
+int  mi355_letterbox_geometry(int height, int width, int imgsz, int auto_pad, int* i6, double* d5);
+/* The per-frame letterbox of a batch of frames of different sizes (the kernel mi355_yolo_infer_multi runs): HOST frames as in
+ * mi355_yolo_infer_multi, every one letterboxed to the square imgsz x imgsz canvas; out[n][imgsz][imgsz][3]. */
+int  mi355_op_letterbox_multi(int device_id, const uint8_t* const* frames, const int* heights, const int* widths,
+                              const int* row_strides, int n, int imgsz, uint8_t* out);
 /* utils/nms.py:non_max_suppression on a decoded head tensor pred[n][4+nc+extra][A] (Ultralytics layout).
  * Rows come back in letterboxed pixels (no scale-back): x1,y1,x2,y2,conf,cls,anchor_idx, kpt = the `extra` columns. */
 int  mi355_op_nms(int device_id, const float* pred, int n, int nc, int extra, int anchors, float conf, float iou,
