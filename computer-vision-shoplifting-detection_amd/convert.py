@@ -83,26 +83,35 @@ def read_checkpoint(path: str) -> Tuple[Dict[str, np.ndarray], dict]:
     return sd, info
 
 
+def _head_index(name: str) -> int:
+    return 24 if name.startswith("yolov5") else 23 if name.startswith("yolo11") else 22
+
+
 def infer_model_name(sd: Dict[str, np.ndarray], info: dict) -> str:
-    """Family from the block type of layer 2 (C2f has ``m.0.cv1`` with 3x3, C3 has ``cv3``), scale from the stem
-    width, task from the presence of the keypoint branch."""
+    """Family from the block types (YOLO11: C2PSA attention at layer 10 and a head at layer 23; else C2f has ``m.0.cv1``
+    with 3x3, C3 has ``cv3``), scale from the stem width, task from the presence of the keypoint branch."""
     c0 = sd["model.0.conv.weight"].shape[0]
-    family = "v5u" if "model.2.cv3.conv.weight" in sd else "v8"
-    scale = {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}.get(c0)
+    if "model.10.m.0.attn.qkv.conv.weight" in sd and any(k.startswith("model.23.") for k in sd):
+        family = "v11"
+        # yolo11m and yolo11l share the 64-wide stem (width 1.00, max 512); l repeats each C3k2 block twice
+        scale = {16: "n", 32: "s", 96: "x"}.get(c0) or ({64: "l" if any(k.startswith("model.2.m.1.") for k in sd) else "m"}).get(c0)
+    else:
+        family = "v5u" if "model.2.cv3.conv.weight" in sd else "v8"
+        scale = {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}.get(c0)
     if scale is None:
         raise ValueError(f"unsupported stem width {c0}")
-    head = 24 if family == "v5u" else 22
+    head = {"v5u": 24, "v8": 22, "v11": 23}[family]
     pose = f"model.{head}.cv4.0.0.conv.weight" in sd
     if any(k.startswith(f"model.{head}.") and (".proto." in k or ".cv4." in k and not pose) for k in sd):
         raise ValueError("segmentation / OBB checkpoints are not supported (detect and pose only)")
-    base = f"yolov5{scale}u" if family == "v5u" else f"yolov8{scale}"
+    base = {"v5u": f"yolov5{scale}u", "v8": f"yolov8{scale}", "v11": f"yolo11{scale}"}[family]
     return base + ("-pose" if pose else "")
 
 
 def convert_pt(path: str) -> bytes:
     sd, info = read_checkpoint(path)
     name = infer_model_name(sd, info)
-    head = 24 if name.startswith("yolov5") else 22
+    head = _head_index(name)
     nc = int(sd[f"model.{head}.cv3.0.2.weight"].shape[0])
     names = info.get("names")
     meta = {"source": path}

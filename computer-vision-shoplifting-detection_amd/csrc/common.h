@@ -141,6 +141,25 @@ const char* launch_sppf_pools(const float* src, int src_cs, float* dst, int dst_
 // fp16 buffers (strides / C in halfs, C % 8 == 0); max is exact in any precision
 const char* launch_sppf_pools_f16(const void* src, int src_cs, void* dst, int dst_cs, int B, int H, int W, int C,
                                   hipStream_t st);
+// Depthwise 3x3 conv (stride 1, pad 1) on channel views: dst = act(dwconv(src) + bias) (+ res), fp32 (dw_attn_kernels.hip).
+struct DwConvArgs {
+    const float* src; int src_cs;      // view base (first channel) and pixel stride of the NHWC buffers, in floats
+    float* dst; int dst_cs;
+    const float* res; int res_cs;      // residual view or nullptr
+    const float* w;                    // device [k*k][c_pad]: tap-major weights, channels zero-padded to c_pad (multiple of 4)
+    const float* bias;                 // device [c_pad]
+    int B, H, W, C, k, act, c_pad;
+};
+const char* launch_dwconv(const DwConvArgs& a, hipStream_t st);
+// PSA attention (Ultralytics Attention between qkv and pe), fp32: qkv view [q of every head | k of every head | v of every head]
+// (key_dim, key_dim, head_dim per head); dst view: heads x head_dim channels, softmax_j(q_i . k_j * scale) v_j per frame and head.
+struct PsaAttnArgs {
+    const float* qkv; int qkv_cs;
+    float* dst; int dst_cs;
+    int B, N, heads, key_dim, head_dim;
+    float scale;                       // key_dim ** -0.5
+};
+const char* launch_psa_attention(const PsaAttnArgs& a, hipStream_t st);
 struct LetterboxArgs {
     const uint8_t* src; int H, W; long long frame_stride; int row_stride;   // source frames
     uint8_t* dst; int Hd, Wd;                                               // letterboxed output (dense)

@@ -36,7 +36,7 @@ int mi355_yolo_info(const mi355_yolo* h, mi355_model_info* info) {
     for (size_t i = 0; i < h->levels.size(); ++i) info->strides[i] = h->levels[i].stride;
     info->n_convs = (int)h->convs.size(); info->n_ops = (int)h->ops.size(); info->n_buffers = (int)h->bufs.size();
     info->n_params = h->n_params; info->macs_640 = h->macs640;
-    std::strncpy(info->family, h->hdr.family == 0 ? "v8" : "v5u", sizeof(info->family) - 1);
+    std::strncpy(info->family, h->hdr.family == 0 ? "v8" : h->hdr.family == 1 ? "v5u" : h->hdr.family == 2 ? "v11" : "?", sizeof(info->family) - 1);
     info->scale = (char)h->hdr.scale;
     return MI355_OK;
 }

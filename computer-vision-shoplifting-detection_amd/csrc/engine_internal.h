@@ -36,7 +36,8 @@ inline int fail(int code, const std::string& msg) { g_err = msg; return code; }
         if (m_) return fail(MI355_EHIP, std::string("launch failed: ") + m_);                \
     } while (0)
 
-enum { OP_STEM = 0, OP_CONV = 1, OP_UPSAMPLE = 2, OP_SPPF_POOL = 3 };
+// OP_DWCONV / OP_ATTN (YOLO11, file version 2): FileOp.r0 = groups (== channels) / heads; for OP_ATTN k = key_dim, s = head_dim
+enum { OP_STEM = 0, OP_CONV = 1, OP_UPSAMPLE = 2, OP_SPPF_POOL = 3, OP_DWCONV = 4, OP_ATTN = 5 };
 
 #pragma pack(push, 1)
 struct FileHeader {
@@ -54,6 +55,7 @@ struct FileLevel { uint32_t buf, box_off, cls_off, kpt_off, stride; };
 #pragma pack(pop)
 
 struct DevConv { float* wpk = nullptr; float* bias = nullptr; float* w_raw = nullptr; void* w_frag = nullptr; };   // w_frag: stem3_weight_frags (half k3 stems)
+                                                                                                             // depthwise convs: w_raw = [k*k][round_up(c, 4)]
 
 // LetterBox geometry (data/augment.py:LetterBox, auto=True, scaleup=True, center=True, stride 32) and the
 // scale-back constants of utils/ops.py:scale_boxes / scale_coords, in the same double arithmetic as Python.

@@ -54,7 +54,7 @@ int parse_blob(mi355_yolo* h, const uint8_t* blob, size_t n) {
     if (n < sizeof(FileHeader) || std::memcmp(blob, "MI355YW1", 8) != 0) return fail(MI355_EFORMAT, "not a .mi355w file (bad magic)");
     std::memcpy(&h->hdr, blob, sizeof(FileHeader));
     const FileHeader& H = h->hdr;
-    if (H.version != 1) return fail(MI355_EFORMAT, "unsupported .mi355w version");
+    if (H.version != 1 && H.version != 2) return fail(MI355_EFORMAT, "unsupported .mi355w version");
     size_t p = sizeof(FileHeader);
     const size_t need = p + sizeof(FileBuf) * H.n_buffers + sizeof(FileOp) * H.n_ops + sizeof(FileConv) * H.n_convs +
                         sizeof(FileLevel) * H.n_levels;
@@ -71,6 +71,33 @@ int parse_blob(mi355_yolo* h, const uint8_t* blob, size_t n) {
         h->model_hash = hsh;
     }
     // validate the program
+    std::vector<int> conv_groups(H.n_convs, 1);
+    bool new_ops = false;
+    for (const FileOp& o : h->ops) {
+        if (o.type < OP_STEM || o.type > OP_ATTN) return fail(MI355_EFORMAT, "unknown op type in program");
+        if (o.type == OP_DWCONV || o.type == OP_ATTN) {
+            new_ops = true;
+            if (H.version < 2) return fail(MI355_EFORMAT, "depthwise / attention ops need a version 2 .mi355w file");
+            if (o.src_buf < 0 || o.src_buf >= (int)H.n_buffers || o.dst_buf < 0 || o.dst_buf >= (int)H.n_buffers ||
+                h->bufs[o.src_buf].stride_div != h->bufs[o.dst_buf].stride_div)
+                return fail(MI355_EFORMAT, "depthwise / attention op changes resolution");
+        }
+        if (o.type == OP_DWCONV) {
+            if (o.conv < 0 || o.conv >= (int)H.n_convs) return fail(MI355_EFORMAT, "bad conv index");
+            const FileConv& c = h->convs[o.conv];
+            if (o.r0 <= 0 || (int)c.cin != o.r0 || (int)c.cout != o.r0 || o.src_c != o.r0 || o.dst_c != o.r0 || c.k != 3 ||
+                c.s != 1 || o.s != 1 || (int)c.pad != (int)c.k / 2 || o.act != (int)c.act)
+                return fail(MI355_EFORMAT, "depthwise op: channels / groups / kernel size inconsistent (k 3, stride 1)");
+            conv_groups[o.conv] = o.r0;
+        }
+        if (o.type == OP_ATTN && (o.k != 32 || o.s != 64 || o.r0 <= 0 || o.src_c != o.r0 * (2 * o.k + o.s) || o.dst_c != o.r0 * o.s ||
+                                  o.res_buf >= 0 || o.conv >= 0))
+            return fail(MI355_EFORMAT, "attention op: heads / key_dim / head_dim inconsistent (key_dim 32, head_dim 64)");
+    }
+    for (const FileOp& o : h->ops)                 // a depthwise conv's weights are not a dense conv's (and vice versa)
+        if ((o.type == OP_STEM || o.type == OP_CONV) && o.conv >= 0 && o.conv < (int)H.n_convs && conv_groups[o.conv] != 1)
+            return fail(MI355_EFORMAT, "a conv is used as both depthwise and dense");
+    if (new_ops && h->half) return fail(MI355_EFORMAT, "half=True is not supported for this model (YOLO11 depthwise / attention ops run in fp32 only)");
     for (const FileOp& o : h->ops) {
         auto okv = [&](int b, int off, int c) { return b >= 0 && b < (int)H.n_buffers && off >= 0 && (off & 3) == 0 && off + c <= (int)h->bufs[b].channels; };
         if (o.type != OP_STEM && !okv(o.src_buf, o.src_choff, o.src_c)) return fail(MI355_EFORMAT, "op reads outside its buffer");
@@ -100,11 +127,11 @@ int parse_blob(mi355_yolo* h, const uint8_t* blob, size_t n) {
     }
     h->n_params = H.reg_max; h->macs640 = 0;
     for (const FileOp& o : h->ops) {
-        if (o.type != OP_STEM && o.type != OP_CONV) continue;
+        if (o.type != OP_STEM && o.type != OP_CONV && o.type != OP_DWCONV) continue;
         const FileConv& c = h->convs[o.conv];
-        const long long sd = h->bufs[o.dst_buf].stride_div;
-        h->n_params += (long long)c.cout * c.cin * c.k * c.k + c.cout;
-        h->macs640 += (long long)c.cout * c.cin * c.k * c.k * (640 / sd) * (640 / sd);
+        const long long sd = h->bufs[o.dst_buf].stride_div, cin = c.cin / conv_groups[o.conv];
+        h->n_params += (long long)c.cout * cin * c.k * c.k + c.cout;
+        h->macs640 += (long long)c.cout * cin * c.k * c.k * (640 / sd) * (640 / sd);
     }
     // upload weights
     const uint8_t* data = blob + H.header_bytes;
@@ -112,7 +139,7 @@ int parse_blob(mi355_yolo* h, const uint8_t* blob, size_t n) {
     std::vector<float> tmp;
     for (size_t i = 0; i < h->convs.size(); ++i) {
         const FileConv& c = h->convs[i];
-        const size_t wn = (size_t)c.cout * c.cin * c.k * c.k;
+        const size_t wn = (size_t)c.cout * (c.cin / conv_groups[i]) * c.k * c.k;
         if (c.w_off + wn * 4 > H.data_bytes || c.b_off + (size_t)c.cout * 4 > H.data_bytes) return fail(MI355_EFORMAT, "tensor outside the data region");
         const float* w = (const float*)(data + c.w_off);
         const float* b = (const float*)(data + c.b_off);
@@ -123,7 +150,14 @@ int parse_blob(mi355_yolo* h, const uint8_t* blob, size_t n) {
         std::memcpy(tmp.data(), b, (size_t)c.cout * 4);
         HIPCHK(hipMalloc(&d.bias, bn * 4));
         HIPCHK(hipMemcpy(d.bias, tmp.data(), bn * 4, hipMemcpyHostToDevice));
-        if (c.cin == 3) {                      // stem: raw OIHW, read by stem_mfma_u8
+        if (conv_groups[i] != 1) {             // depthwise: tap-major [k*k][c_pad], read 4 channels at a time by dwconv_kernel
+            const int cp = round_up((int)c.cout, 4), kk = (int)(c.k * c.k);
+            std::vector<float> wt((size_t)kk * cp, 0.f);
+            for (int ch = 0; ch < (int)c.cout; ++ch)
+                for (int t = 0; t < kk; ++t) wt[(size_t)t * cp + ch] = w[(size_t)ch * kk + t];
+            HIPCHK(hipMalloc(&d.w_raw, wt.size() * 4));
+            HIPCHK(hipMemcpy(d.w_raw, wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
+        } else if (c.cin == 3) {                      // stem: raw OIHW, read by stem_mfma_u8
             HIPCHK(hipMalloc(&d.w_raw, wn * 4));
             HIPCHK(hipMemcpy(d.w_raw, w, wn * 4, hipMemcpyHostToDevice));
             if (h->half && c.k == 3) {         // A fragments of stem3s2_u8_h

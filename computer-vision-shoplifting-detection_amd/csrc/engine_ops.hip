@@ -97,6 +97,54 @@ static int op_conv2d_impl(int device_id, const float* x, int n, int h, int w, in
     return MI355_OK;
 }
 
+int mi355_op_dwconv2d(int device_id, const float* x, int n, int h, int w, int x_cs, int x_off, int c, const float* w_c1kk,
+                      const float* bias, int k, int silu, const float* residual, int res_cs, int res_off, float* y, int y_cs, int y_off) {
+    if (!x || !w_c1kk || !bias || !y || n <= 0 || h <= 0 || w <= 0 || c <= 0 || k != 3) return fail(MI355_EINVAL, "bad argument");
+    auto view_ok = [&](int cs, int off) { return cs > 0 && off >= 0 && !(cs & 3) && !(off & 3) && off + round_up(c, 4) <= cs; };
+    if (!view_ok(x_cs, x_off) || !view_ok(y_cs, y_off) || (residual && !view_ok(res_cs, res_off)))
+        return fail(MI355_EINVAL, "views: strides / offsets must be multiples of 4 and the view (rounded up to 4 channels) inside the tensor");
+    HIPCHK(hipSetDevice(device_id));
+    const size_t np = (size_t)n * h * w;
+    const int cp = round_up(c, 4), kk = k * k;
+    std::vector<float> wt((size_t)kk * cp, 0.f), bp(cp, 0.f);
+    for (int ch = 0; ch < c; ++ch)
+        for (int t = 0; t < kk; ++t) wt[(size_t)t * cp + ch] = w_c1kk[(size_t)ch * kk + t];
+    std::memcpy(bp.data(), bias, (size_t)c * 4);
+    DevMem dm; float *d_x, *d_y, *d_r = nullptr, *d_w, *d_b;
+    HIPCHK(dm.alloc(&d_x, np * x_cs * 4)); HIPCHK(hipMemcpy(d_x, x, np * x_cs * 4, hipMemcpyHostToDevice));
+    HIPCHK(dm.alloc(&d_y, np * y_cs * 4)); HIPCHK(hipMemcpy(d_y, y, np * y_cs * 4, hipMemcpyHostToDevice));
+    if (residual) { HIPCHK(dm.alloc(&d_r, np * res_cs * 4)); HIPCHK(hipMemcpy(d_r, residual, np * res_cs * 4, hipMemcpyHostToDevice)); }
+    HIPCHK(dm.alloc(&d_w, wt.size() * 4)); HIPCHK(hipMemcpy(d_w, wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(dm.alloc(&d_b, bp.size() * 4)); HIPCHK(hipMemcpy(d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
+    DwConvArgs a{};
+    a.src = d_x + x_off; a.src_cs = x_cs; a.dst = d_y + y_off; a.dst_cs = y_cs;
+    if (residual) { a.res = d_r + res_off; a.res_cs = res_cs; }
+    a.w = d_w; a.bias = d_b; a.B = n; a.H = h; a.W = w; a.C = c; a.k = k; a.act = silu ? 1 : 0; a.c_pad = cp;
+    KCHK(launch_dwconv(a, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(y, d_y, np * y_cs * 4, hipMemcpyDeviceToHost));
+    return MI355_OK;
+}
+
+int mi355_op_psa_attention(int device_id, const float* qkv, int n, int hw, int heads, int key_dim, int head_dim, float* y) {
+    if (!qkv || !y || n <= 0 || hw <= 0 || heads <= 0) return fail(MI355_EINVAL, "bad argument");
+    if (key_dim != 32 || head_dim != 64) return fail(MI355_EINVAL, "key_dim must be 32 and head_dim 64");
+    HIPCHK(hipSetDevice(device_id));
+    const size_t np = (size_t)n * hw;
+    const int cin = heads * (2 * key_dim + head_dim), cout = heads * head_dim;
+    DevMem dm; float *d_x, *d_y;
+    HIPCHK(dm.alloc(&d_x, np * cin * 4)); HIPCHK(hipMemcpy(d_x, qkv, np * cin * 4, hipMemcpyHostToDevice));
+    HIPCHK(dm.alloc(&d_y, np * cout * 4)); HIPCHK(hipMemset(d_y, 0, np * cout * 4));
+    PsaAttnArgs a{};
+    a.qkv = d_x; a.qkv_cs = cin; a.dst = d_y; a.dst_cs = cout;
+    a.B = n; a.N = hw; a.heads = heads; a.key_dim = key_dim; a.head_dim = head_dim;
+    a.scale = (float)(1.0 / std::sqrt((double)key_dim));
+    KCHK(launch_psa_attention(a, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(y, d_y, np * cout * 4, hipMemcpyDeviceToHost));
+    return MI355_OK;
+}
+
 int mi355_op_conv2d(int device_id, const float* x, int n, int h, int w, int cin, const float* w_oihw, const float* bias,
                     int cout, int k, int stride, int silu, const float* residual, float* y, int plan_index, int* n_plans) {
     return op_conv2d_impl(device_id, x, n, h, w, cin, w_oihw, bias, cout, k, stride, silu, residual, y, plan_index, n_plans, false, false);

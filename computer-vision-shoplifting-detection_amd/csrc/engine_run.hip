@@ -110,6 +110,26 @@ int launch_net(mi355_yolo* h, Prof& pf, const uint8_t* stem_in, int nb, const Ge
                 KCHK(launch_sppf_pools(h->view(o.src_buf, o.src_choff), h->dbuf_cs[o.src_buf], dst, h->dbuf_cs[o.dst_buf], nb,
                                        g.Hl / sd_out, g.Wl / sd_out, o.src_c, st));
             pf.end();
+        } else if (o.type == OP_DWCONV) {
+            const FileConv& c = h->convs[o.conv];
+            DwConvArgs a{};
+            a.src = h->view(o.src_buf, o.src_choff); a.src_cs = h->dbuf_cs[o.src_buf];
+            a.dst = dst; a.dst_cs = h->dbuf_cs[o.dst_buf];
+            if (o.res_buf >= 0) { a.res = h->view(o.res_buf, o.res_choff); a.res_cs = h->dbuf_cs[o.res_buf]; }
+            a.w = h->dconv[o.conv].w_raw; a.bias = h->dconv[o.conv].bias;
+            a.B = nb; a.H = g.Hl / sd_out; a.W = g.Wl / sd_out; a.C = o.dst_c; a.k = c.k; a.act = o.act; a.c_pad = round_up(o.dst_c, 4);
+            if (pf.begin(K_CONV)) return fail(MI355_EHIP, "event");
+            KCHK(launch_dwconv(a, st));
+            pf.end();
+        } else if (o.type == OP_ATTN) {
+            PsaAttnArgs a{};
+            a.qkv = h->view(o.src_buf, o.src_choff); a.qkv_cs = h->dbuf_cs[o.src_buf];
+            a.dst = dst; a.dst_cs = h->dbuf_cs[o.dst_buf];
+            a.B = nb; a.N = (g.Hl / sd_out) * (g.Wl / sd_out); a.heads = o.r0; a.key_dim = o.k; a.head_dim = o.s;
+            a.scale = (float)(1.0 / std::sqrt((double)o.k));      // Attention.scale = key_dim ** -0.5, rounded to fp32 once
+            if (pf.begin(K_CONV)) return fail(MI355_EHIP, "event");
+            KCHK(launch_psa_attention(a, st));
+            pf.end();
         } else {
             return fail(MI355_EFORMAT, "unknown op type in program");
         }

@@ -100,9 +100,54 @@ _V5_HEAD = [
     ((17, 20, 23), 1, "HEAD", ()),
 ]
 
-FAMILIES = {"v8": (_V8_BACKBONE, _V8_HEAD), "v5u": (_V5_BACKBONE, _V5_HEAD)}
+# yolo11.yaml `scales`
+SCALES_V11: Dict[str, Tuple[float, float, int]] = {
+    "n": (0.50, 0.25, 1024),
+    "s": (0.50, 0.50, 1024),
+    "m": (0.50, 1.00, 512),
+    "l": (1.00, 1.00, 512),
+    "x": (1.00, 1.50, 512),
+}
 
-OP_STEM, OP_CONV, OP_UPSAMPLE, OP_SPPF_POOL = 0, 1, 2, 3
+# YOLO11 (yolo11.yaml / yolo11-pose.yaml): C3k2 blocks (args: c2, c3k, e), C2PSA attention at P5, and the non-legacy head
+# (depthwise class branch).  parse_model forces c3k=True for the m/l/x scales.
+_V11_BACKBONE = [
+    (-1, 1, "Conv", (64, 3, 2)),
+    (-1, 1, "Conv", (128, 3, 2)),
+    (-1, 2, "C3k2", (256, False, 0.25)),
+    (-1, 1, "Conv", (256, 3, 2)),
+    (-1, 2, "C3k2", (512, False, 0.25)),
+    (-1, 1, "Conv", (512, 3, 2)),
+    (-1, 2, "C3k2", (512, True, 0.5)),
+    (-1, 1, "Conv", (1024, 3, 2)),
+    (-1, 2, "C3k2", (1024, True, 0.5)),
+    (-1, 1, "SPPF", (1024, 5)),
+    (-1, 2, "C2PSA", (1024,)),
+]
+_V11_HEAD = [
+    (-1, 1, "Upsample", ()),
+    ((-1, 6), 1, "Concat", ()),
+    (-1, 2, "C3k2", (512, False, 0.5)),
+    (-1, 1, "Upsample", ()),
+    ((-1, 4), 1, "Concat", ()),
+    (-1, 2, "C3k2", (256, False, 0.5)),
+    (-1, 1, "Conv", (256, 3, 2)),
+    ((-1, 13), 1, "Concat", ()),
+    (-1, 2, "C3k2", (512, False, 0.5)),
+    (-1, 1, "Conv", (512, 3, 2)),
+    ((-1, 10), 1, "Concat", ()),
+    (-1, 2, "C3k2", (1024, True, 0.5)),
+    ((16, 19, 22), 1, "HEAD", ()),
+]
+
+FAMILIES = {"v8": (_V8_BACKBONE, _V8_HEAD), "v5u": (_V5_BACKBONE, _V5_HEAD), "v11": (_V11_BACKBONE, _V11_HEAD)}
+FAMILY_SCALES = {"v8": SCALES, "v5u": SCALES_V5, "v11": SCALES_V11}
+
+# OP_DWCONV: depthwise k x k conv (+bias, +SiLU, +residual), weights of a ConvSpec with groups == cin == cout.
+# OP_ATTN: multi-head spatial self-attention over the pixels of one frame (PSABlock's Attention minus its convs): reads the
+# permuted qkv slice [q of every head | k of every head | v of every head] (key_dim, key_dim, head_dim channels per head),
+# writes softmax(q^T k * key_dim^-0.5) applied to v, head after head.  Op fields: k = key_dim, s = head_dim, heads.
+OP_STEM, OP_CONV, OP_UPSAMPLE, OP_SPPF_POOL, OP_DWCONV, OP_ATTN = 0, 1, 2, 3, 4, 5
 ACT_NONE, ACT_SILU = 0, 1
 TASK_DETECT, TASK_POSE = 0, 1
 REG_MAX = 16
@@ -123,6 +168,9 @@ class ConvSpec:
     act: int             # ACT_SILU for Conv modules, ACT_NONE for the head's final nn.Conv2d
     has_bn: bool         # True: checkpoint holds <name>.conv.weight + <name>.bn.*; False: <name>.weight/.bias
     stride_div: int      # output resolution = input / stride_div
+    groups: int = 1      # cin // groups input channels per output channel (depthwise: groups == cin == cout)
+    sd_name: Optional[str] = None              # state-dict prefix when it differs from `name` (the weights' source)
+    rows: Optional[Tuple[int, ...]] = None     # fused output channel j = checkpoint output channel rows[j]
 
     @property
     def pad(self) -> int:
@@ -147,6 +195,7 @@ class Op:
     dst: Optional[View] = None
     res: Optional[View] = None
     conv: int = -1       # index into Program.convs
+    heads: int = 0       # OP_ATTN: number of heads
 
 
 @dataclass
@@ -186,11 +235,12 @@ class Program:
     def param_count(self, include_dfl: bool = True) -> int:
         """Fused parameter count (weights + biases), the number Ultralytics prints in
         ``model.info()`` after ``fuse()``; the DFL arange conv (16 frozen params) is counted there."""
-        n = sum(c.cout * c.cin * c.k * c.k + c.cout for c in self.convs)
+        n = sum(c.cout * (c.cin // c.groups) * c.k * c.k + c.cout for c in self.convs)
         return n + (REG_MAX if include_dfl else 0)
 
     def macs(self, h: int = 640, w: int = 640) -> int:
-        return sum(c.cout * c.cin * c.k * c.k * (h // c.stride_div) * (w // c.stride_div) for c in self.convs)
+        """Conv multiply-adds (what the model cards' GFLOPs count: the attention's matmuls are not in them)."""
+        return sum(c.cout * (c.cin // c.groups) * c.k * c.k * (h // c.stride_div) * (w // c.stride_div) for c in self.convs)
 
     def act_bytes(self, h: int = 640, w: int = 640, elem: int = 4) -> int:
         """SURVEY 8(d) 'layerwise bytes': sum over convs of input read + output write."""
@@ -216,11 +266,23 @@ class _Builder:
         self.p.ops.append(Op(OP_STEM if stem else OP_CONV, k, s, act, src, dst, res, len(self.p.convs) - 1))
         return dst
 
+    def pconv(self, name: str, src: View, dst: View, cout: int, act: int, rows: Tuple[int, ...], sd: int,
+              res: Optional[View] = None) -> View:
+        """1x1 conv whose output channels are a permutation `rows` of the checkpoint's (applied when the weights are fused)."""
+        self.p.convs.append(ConvSpec(name, src.c, cout, 1, 1, act, True, sd, rows=tuple(rows)))
+        self.p.ops.append(Op(OP_CONV, 1, 1, act, src, dst, res, len(self.p.convs) - 1))
+        return dst
+
+    def dwconv(self, name: str, src: View, dst: View, k: int, sd: int, act: int = ACT_SILU, res: Optional[View] = None) -> View:
+        self.p.convs.append(ConvSpec(name, src.c, src.c, k, 1, act, True, sd, groups=src.c))
+        self.p.ops.append(Op(OP_DWCONV, k, 1, act, src, dst, res, len(self.p.convs) - 1))
+        return dst
+
 
 def build_program(family: str = "v8", scale: str = "n", task: str = "detect", nc: Optional[int] = None,
                   kpt_shape: Tuple[int, int] = (17, 3)) -> Program:
     """parse_model + the module forward()s, flattened (Appendix A.2-A.4)."""
-    depth, width, max_ch = (SCALES_V5 if family == "v5u" else SCALES)[scale]
+    depth, width, max_ch = FAMILY_SCALES[family][scale]
     tsk = TASK_POSE if task == "pose" else TASK_DETECT
     if nc is None:
         nc = 1 if tsk == TASK_POSE else 80
@@ -247,7 +309,7 @@ def build_program(family: str = "v8", scale: str = "n", task: str = "detect", nc
         sdin = 1 if i == 0 else sd_out[f[0]]
         if mod == "Conv":
             c_out[i], sd_out[i] = ch(args[0]), sdin * args[2]
-        elif mod in ("C2f", "C3", "SPPF"):
+        elif mod in ("C2f", "C3", "SPPF", "C3k2", "C2PSA"):
             c_out[i], sd_out[i] = ch(args[0]), sdin
         elif mod == "Upsample":
             c_out[i], sd_out[i] = cin, sdin // 2
@@ -274,6 +336,46 @@ def build_program(family: str = "v8", scale: str = "n", task: str = "detect", nc
         if i not in node_buf:
             node_buf[i] = b.new_buf(c_out[i], sd_out[i])
         return View(node_buf[i], 0, c_out[i])
+
+    def c3_block(name: str, x: View, dst_view, c2: int, nrep: int, shortcut: bool, k1: int, sd: int) -> View:
+        """C3 (k1 = 1: Bottleneck k=(1, 3), yolov5u) or C3k (k1 = 3: k=(3, 3)), e = 0.5, inner Bottlenecks e = 1.0.
+        dst_view() gives the output view; it is called last, so that the buffers keep the order the v5u images were built with."""
+        c_ = int(c2 * 0.5)
+        ybuf = b.new_buf(2 * c_, sd)                             # cat(m(cv1(x)), cv2(x))
+        cur = View(b.new_buf(c_, sd), 0, c_)
+        b.conv(f"{name}.cv1", x, cur, x.c, c_, 1, 1, sd)
+        b.conv(f"{name}.cv2", x, View(ybuf, c_, c_), x.c, c_, 1, 1, sd)
+        for r in range(nrep):
+            tmp = View(b.new_buf(c_, sd), 0, c_)
+            b.conv(f"{name}.m.{r}.cv1", cur, tmp, c_, c_, k1, 1, sd)
+            dst = View(ybuf, 0, c_) if r == nrep - 1 else View(b.new_buf(c_, sd), 0, c_)
+            b.conv(f"{name}.m.{r}.cv2", tmp, dst, c_, c_, 3, 1, sd, res=cur if shortcut else None)
+            cur = dst
+        return b.conv(f"{name}.cv3", View(ybuf, 0, 2 * c_), dst_view(), 2 * c_, c2, 1, 1, sd)
+
+    def psa_block(name: str, x: View, dst: View, sd: int) -> View:
+        """PSABlock(c, attn_ratio=0.5, num_heads=c // 64): x = x + attn(x); x = x + ffn(x).  Attention: qkv 1x1 (rows permuted
+        to [q heads | k heads | v heads]), the attention op, pe = depthwise 3x3 on the v slice with the attention output as its
+        residual, proj 1x1 with x as residual."""
+        c = x.c
+        nh = c // 64
+        hd = c // nh
+        kd = int(hd * 0.5)
+        per = 2 * kd + hd
+        rows = [hh * per + j for hh in range(nh) for j in range(kd)] + \
+               [hh * per + kd + j for hh in range(nh) for j in range(kd)] + \
+               [hh * per + 2 * kd + j for hh in range(nh) for j in range(hd)]
+        qkv = b.new_buf(c + 2 * nh * kd, sd)
+        b.pconv(f"{name}.attn.qkv", x, View(qkv, 0, c + 2 * nh * kd), c + 2 * nh * kd, ACT_NONE, rows, sd)
+        att = View(b.new_buf(c, sd), 0, c)
+        prog.ops.append(Op(OP_ATTN, kd, hd, ACT_NONE, View(qkv, 0, c + 2 * nh * kd), att, heads=nh))
+        pe = View(b.new_buf(c, sd), 0, c)
+        b.dwconv(f"{name}.attn.pe", View(qkv, 2 * nh * kd, c), pe, 3, sd, act=ACT_NONE, res=att)
+        x1 = View(b.new_buf(c, sd), 0, c)
+        b.conv(f"{name}.attn.proj", pe, x1, c, c, 1, 1, sd, act=ACT_NONE, res=x)
+        f1 = View(b.new_buf(2 * c, sd), 0, 2 * c)
+        b.conv(f"{name}.ffn.0", x1, f1, c, 2 * c, 1, 1, sd)
+        return b.conv(f"{name}.ffn.1", f1, dst, 2 * c, c, 1, 1, sd, act=ACT_NONE, res=x1)
 
     # ---- pass 2: emit ops ---------------------------------------------------------------------
     views: List[Optional[View]] = [None] * n_nodes
@@ -302,20 +404,37 @@ def build_program(family: str = "v8", scale: str = "n", task: str = "detect", nc
                        res=last if shortcut else None)
             views[i] = b.conv(f"{name}.cv2", View(ybuf, 0, (2 + nrep) * c), out_view(i), (2 + nrep) * c, c2, 1, 1, sd)
         elif mod == "C3":
+            views[i] = c3_block(name, views[f[0]], lambda i=i: out_view(i), c_out[i], rep(n), args[1], 1, sd)
+        elif mod == "C3k2":
+            # a C2f with self.c = int(c2 * e) whose blocks are Bottleneck(c, c, e=0.5) or, c3k, C3k(c, c, 2) (3x3 / 3x3 inner blocks)
             x = views[f[0]]
-            c2, nrep, shortcut = c_out[i], rep(n), args[1]
-            c_ = int(c2 * 0.5)
-            ybuf = b.new_buf(2 * c_, sd)                             # cat(m(cv1(x)), cv2(x))
-            cur = View(b.new_buf(c_, sd), 0, c_)
-            b.conv(f"{name}.cv1", x, cur, x.c, c_, 1, 1, sd)
-            b.conv(f"{name}.cv2", x, View(ybuf, c_, c_), x.c, c_, 1, 1, sd)
+            c2, nrep, c3k, e = c_out[i], rep(n), args[1] or scale in "mlx", args[2]
+            c = int(c2 * e)
+            ybuf = b.new_buf((2 + nrep) * c, sd)
+            b.conv(f"{name}.cv1", x, View(ybuf, 0, 2 * c), x.c, 2 * c, 1, 1, sd)
             for r in range(nrep):
-                tmp = View(b.new_buf(c_, sd), 0, c_)
-                b.conv(f"{name}.m.{r}.cv1", cur, tmp, c_, c_, 1, 1, sd)
-                dst = View(ybuf, 0, c_) if r == nrep - 1 else View(b.new_buf(c_, sd), 0, c_)
-                b.conv(f"{name}.m.{r}.cv2", tmp, dst, c_, c_, 3, 1, sd, res=cur if shortcut else None)
+                last, out = View(ybuf, (1 + r) * c, c), View(ybuf, (2 + r) * c, c)
+                if c3k:
+                    c3_block(f"{name}.m.{r}", last, lambda out=out: out, c, 2, True, 3, sd)
+                else:
+                    tmp = View(b.new_buf(c // 2, sd), 0, c // 2)
+                    b.conv(f"{name}.m.{r}.cv1", last, tmp, c, c // 2, 3, 1, sd)
+                    b.conv(f"{name}.m.{r}.cv2", tmp, out, c // 2, c, 3, 1, sd, res=last)
+            views[i] = b.conv(f"{name}.cv2", View(ybuf, 0, (2 + nrep) * c), out_view(i), (2 + nrep) * c, c2, 1, 1, sd)
+        elif mod == "C2PSA":
+            # cv2(cat(a, PSABlock^n(b))) with a, b = cv1(x).split(c).  cv1's rows are permuted to [b | a] at fuse time so that
+            # the last block can write its output right after a: the buffer is [b | a | out] and cv2 reads [a | out]
+            x = views[f[0]]
+            c = int(x.c * 0.5)
+            nrep = rep(n)
+            ybuf = b.new_buf(3 * c, sd)
+            b.pconv(f"{name}.cv1", x, View(ybuf, 0, 2 * c), 2 * c, ACT_SILU, list(range(c, 2 * c)) + list(range(c)), sd)
+            cur = View(ybuf, 0, c)
+            for r in range(nrep):
+                dst = View(ybuf, 2 * c, c) if r == nrep - 1 else View(b.new_buf(c, sd), 0, c)
+                psa_block(f"{name}.m.{r}", cur, dst, sd)
                 cur = dst
-            views[i] = b.conv(f"{name}.cv3", View(ybuf, 0, 2 * c_), out_view(i), 2 * c_, c2, 1, 1, sd)
+            views[i] = b.conv(f"{name}.cv2", View(ybuf, c, 2 * c), out_view(i), 2 * c, x.c, 1, 1, sd)
         elif mod == "SPPF":
             x = views[f[0]]
             c2 = c_out[i]
@@ -346,6 +465,16 @@ def build_program(family: str = "v8", scale: str = "n", task: str = "detect", nc
                 if tsk == TASK_POSE:
                     branches.append(("cv4", c4h, prog.nk, kpt_off))
                 for bn_, cmid, cfin, off in branches:
+                    if bn_ == "cv3" and family == "v11":
+                        # non-legacy class branch: [DWConv(x, x, 3), Conv(x, c3, 1)], [DWConv(c3, c3, 3), Conv(c3, c3, 1)], Conv2d
+                        t = x
+                        for s_, cin_ in ((0, x.c), (1, cmid)):
+                            d1 = View(b.new_buf(cin_, sdl), 0, cin_)
+                            b.dwconv(f"{name}.cv3.{li}.{s_}.0", t, d1, 3, sdl)
+                            t = View(b.new_buf(cmid, sdl), 0, cmid)
+                            b.conv(f"{name}.cv3.{li}.{s_}.1", d1, t, cin_, cmid, 1, 1, sdl)
+                        b.conv(f"{name}.cv3.{li}.2", t, View(hb, off, cfin), cmid, cfin, 1, 1, sdl, act=ACT_NONE, has_bn=False)
+                        continue
                     t1 = View(b.new_buf(cmid, sdl), 0, cmid)
                     t2 = View(b.new_buf(cmid, sdl), 0, cmid)
                     b.conv(f"{name}.{bn_}.{li}.0", x, t1, x.c, cmid, 3, 1, sdl)
@@ -381,7 +510,7 @@ def merge_sibling_convs(prog: Program, fused: Optional[Dict[str, tuple]] = None)
 
     groups: Dict[tuple, List[int]] = {}
     for i, o in enumerate(prog.ops):
-        if o.type != OP_CONV or o.res is not None or o.dst.buf in head_bufs:
+        if o.type != OP_CONV or o.res is not None or o.dst.buf in head_bufs or prog.convs[o.conv].rows is not None:
             continue
         c = prog.convs[o.conv]
         whole = o.dst.choff == 0 and o.dst.c == prog.buffers[o.dst.buf][0] and len(writers(o.dst.buf)) == 1
@@ -468,7 +597,7 @@ def engine_program(family: str = "v8", scale: str = "n", task: str = "detect", n
 
 
 def parse_model_name(name: str) -> Tuple[str, str, str]:
-    """'yolov8n', 'yolov8s-pose', 'yolov5mu' -> (family, scale, task)."""
+    """'yolov8n', 'yolov8s-pose', 'yolov5mu', 'yolo11n-pose' -> (family, scale, task)."""
     n = name.lower().replace(".pt", "").replace(".mi355w", "").replace(".yaml", "")
     task = "pose" if n.endswith("-pose") else "detect"
     n = n.replace("-pose", "")
@@ -476,4 +605,7 @@ def parse_model_name(name: str) -> Tuple[str, str, str]:
         return "v8", n[6], task
     if n.startswith("yolov5") and n.endswith("u") and len(n) == 8 and n[6] in SCALES:
         return "v5u", n[6], task
-    raise ValueError(f"unsupported model name {name!r} (yolov8{{n,s,m,l,x}}[-pose] or yolov5{{n,s,m,l,x}}u)")
+    if n.startswith("yolo11") and len(n) == 7 and n[6] in SCALES_V11:
+        return "v11", n[6], task
+    raise ValueError(f"unsupported model name {name!r} (yolov8{{n,s,m,l,x}}[-pose], yolov5{{n,s,m,l,x}}u or "
+                     f"yolo11{{n,s,m,l,x}}[-pose])")

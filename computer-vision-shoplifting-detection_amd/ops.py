@@ -64,6 +64,38 @@ def conv1x1_upcat(x_half: np.ndarray, x_skip: np.ndarray, w_oihw: np.ndarray, bi
     return (y, npl.value) if return_n_plans else y
 
 
+def dwconv2d(x_nhwc: np.ndarray, w_c1kk: np.ndarray, bias: np.ndarray, silu: bool = True, residual: Optional[np.ndarray] = None,
+             x_off: int = 0, c: Optional[int] = None, res_off: int = 0, y: Optional[np.ndarray] = None, y_off: int = 0,
+             device: int = 0) -> np.ndarray:
+    """Depthwise k x k conv (stride 1, pad k/2) + bias (+SiLU) (+residual) on channel views (YOLO11 DWConv / Attention.pe):
+    reads channels x_off .. x_off+c-1 of x [N,H,W,Cx] (and res_off .. of residual [N,H,W,Cr]), writes channels y_off .. of
+    y [N,H,W,Cy] (a copy of ``y`` if given, else zeros [N,H,W,c]); the other channels of y come back unchanged."""
+    x, w, b = _f32(x_nhwc), _f32(w_c1kk), _f32(bias)
+    n, h, wd, cx = x.shape
+    c = w.shape[0] if c is None else c
+    k = w.shape[2]
+    if w.shape != (c, 1, k, k) or b.shape != (c,):
+        raise ValueError("shape mismatch between w, bias and the channel count")
+    out = np.zeros((n, h, wd, c), np.float32) if y is None else np.array(y, dtype=np.float32, order="C", copy=True)
+    r = _f32(residual) if residual is not None else None
+    _lib.check(_lib.lib().mi355_op_dwconv2d(device, x.ctypes.data, n, h, wd, cx, x_off, c, w.ctypes.data, b.ctypes.data, k, int(silu),
+                                            r.ctypes.data if r is not None else None, r.shape[3] if r is not None else 0, res_off,
+                                            out.ctypes.data, out.shape[3], y_off))
+    return out
+
+
+def psa_attention(qkv: np.ndarray, heads: int, key_dim: int = 32, head_dim: int = 64, device: int = 0) -> np.ndarray:
+    """PSA attention (YOLO11 Attention between qkv and pe): qkv [N, HW, heads*(2*key_dim+head_dim)] laid out
+    [q of every head | k of every head | v of every head] -> [N, HW, heads*head_dim]."""
+    x = _f32(qkv)
+    n, hw, cin = x.shape
+    if cin != heads * (2 * key_dim + head_dim):
+        raise ValueError("qkv channel count does not match heads / key_dim / head_dim")
+    y = np.empty((n, hw, heads * head_dim), np.float32)
+    _lib.check(_lib.lib().mi355_op_psa_attention(device, x.ctypes.data, n, hw, heads, key_dim, head_dim, y.ctypes.data))
+    return y
+
+
 def conv2d_fused(x_nhwc: np.ndarray, w1: np.ndarray, b1: np.ndarray, w2: np.ndarray, b2: np.ndarray, stride: int = 1, silu2: bool = False,
                  device: int = 0, plan: int = 0, return_n_plans: bool = False, half: bool = False, out_f32: bool = False):
     """Conv3x3 + bias + SiLU -> Conv1x1 + bias (+SiLU) as one fused launch: x [N,H,W,Cin] -> [N,H/s,W/s,C2].

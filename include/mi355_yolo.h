@@ -358,6 +358,18 @@ int  mi355_gmc_batch_frames(mi355_gmc* g, unsigned long long after_seq, int time
                             long long* stride);
 int  mi355_gmc_track_reset(mi355_gmc* g);
 int  mi355_gmc_track_state(const mi355_gmc* g, int* oh, int* ow, int* n_pts, uint8_t* gray_out, float* pts_out, int pts_cap);
+/* Depthwise 3x3 conv (stride 1, pad 1) + bias (+SiLU) (+residual) on channel views, fp32, as the engine runs YOLO11's
+ * DWConv and Attention.pe (ultralytics nn/modules/conv.py:DWConv, Conv with groups = c).  x[n][h][w][x_cs] holds the input view at
+ * channels x_off .. x_off+c-1; residual (or NULL) [n][h][w][res_cs] at res_off; y[n][h][w][y_cs] is read in, its view y_off ..
+ * y_off+c-1 written and every other channel handed back unchanged.  w[c][1][k][k], bias[c].  All strides and offsets are
+ * multiples of 4 and every view lies inside its tensor. */
+int  mi355_op_dwconv2d(int device_id, const float* x, int n, int h, int w, int x_cs, int x_off, int c, const float* w_c1kk,
+                       const float* bias, int k, int silu, const float* residual, int res_cs, int res_off, float* y, int y_cs,
+                       int y_off);
+/* PSA attention (ultralytics nn/modules/block.py:Attention between qkv and pe), fp32: qkv[n][hw][heads*(2*key_dim+head_dim)] laid
+ * out [q of every head | k of every head | v of every head]; y[n][hw][heads*head_dim] = per frame and head
+ * softmax_j(q_i . k_j * key_dim^-0.5) v_j.  key_dim 32, head_dim 64 (every YOLO11 scale). */
+int  mi355_op_psa_attention(int device_id, const float* qkv, int n, int hw, int heads, int key_dim, int head_dim, float* y);
 /* The u8 stem: letterboxed BGR frames -> (x/255, RGB) -> conv k x k stride s (pad k/2, or 2 for k=6) + bias + SiLU. */
 int  mi355_op_stem(int device_id, const uint8_t* bgr, int n, int h, int w, const float* w_oihw, const float* bias,
                    int cout, int k, int stride, float* y);

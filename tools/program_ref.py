@@ -13,7 +13,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from cvsd_amd.graph import ACT_SILU, OP_CONV, OP_SPPF_POOL, OP_STEM, OP_UPSAMPLE, Program
+from cvsd_amd.graph import ACT_SILU, OP_ATTN, OP_CONV, OP_DWCONV, OP_SPPF_POOL, OP_STEM, OP_UPSAMPLE, Program
 
 
 def conv_nhwc(x: np.ndarray, w: np.ndarray, stride: int, pad: int) -> np.ndarray:
@@ -28,6 +28,33 @@ def conv_nhwc(x: np.ndarray, w: np.ndarray, stride: int, pad: int) -> np.ndarray
             patch = xp[:, kh:kh + (ho - 1) * stride + 1:stride, kw:kw + (wo - 1) * stride + 1:stride, :]
             out += patch @ w[:, :, kh, kw].T.astype(x.dtype)
     return out
+
+
+def dwconv_nhwc(x: np.ndarray, w: np.ndarray, stride: int, pad: int) -> np.ndarray:
+    """depthwise: x [N,H,W,C], w [C,1,k,k] -> [N,Ho,Wo,C]."""
+    n, h, wd, c = x.shape
+    k = w.shape[2]
+    ho, wo = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
+    xp = np.pad(x, ((0, 0), (pad, pad), (pad, pad), (0, 0)))
+    out = np.zeros((n, ho, wo, c), dtype=x.dtype)
+    for kh in range(k):
+        for kw in range(k):
+            out += xp[:, kh:kh + (ho - 1) * stride + 1:stride, kw:kw + (wo - 1) * stride + 1:stride, :] * w[:, 0, kh, kw].astype(x.dtype)
+    return out
+
+
+def psa_attention(qkv: np.ndarray, heads: int, key_dim: int, head_dim: int) -> np.ndarray:
+    """OP_ATTN on an NHWC slice [N,H,W,heads*(2*key_dim+head_dim)] laid out [q heads | k heads | v heads] -> [N,H,W,heads*head_dim]:
+    per frame and head, softmax_j(q_i . k_j * key_dim**-0.5) applied to v (Ultralytics' Attention between qkv and pe)."""
+    n, h, w, _ = qkv.shape
+    t = qkv.reshape(n, h * w, -1)
+    q = t[..., :heads * key_dim].reshape(n, h * w, heads, key_dim).transpose(0, 2, 1, 3)           # [n, nh, N, kd]
+    k = t[..., heads * key_dim:2 * heads * key_dim].reshape(n, h * w, heads, key_dim).transpose(0, 2, 1, 3)
+    v = t[..., 2 * heads * key_dim:].reshape(n, h * w, heads, head_dim).transpose(0, 2, 1, 3)       # [n, nh, N, hd]
+    s = (q @ k.transpose(0, 1, 3, 2)) * (key_dim ** -0.5)
+    s = np.exp(s - s.max(-1, keepdims=True))
+    a = s / s.sum(-1, keepdims=True)
+    return (a @ v).transpose(0, 2, 1, 3).reshape(n, h, w, heads * head_dim)
 
 
 def silu(x: np.ndarray) -> np.ndarray:
@@ -59,16 +86,20 @@ class ProgramExecutor:
         self.bufs = [np.zeros((n, h // sd, w // sd, c), self.dtype) for c, sd in prog.buffers]
         x0 = x_rgb01.astype(self.dtype)
         for op in prog.ops:
-            if op.type in (OP_STEM, OP_CONV):
+            if op.type in (OP_STEM, OP_CONV, OP_DWCONV):
                 c = prog.convs[op.conv]
                 src = x0 if op.type == OP_STEM else self.bufs[op.src.buf][..., op.src.choff:op.src.choff + op.src.c]
                 wt, b = get_wb(op.conv, src)
-                y = conv_nhwc(src, wt.astype(self.dtype), c.s, c.pad) + b.astype(self.dtype)
+                cf = dwconv_nhwc if op.type == OP_DWCONV else conv_nhwc
+                y = cf(src, wt.astype(self.dtype), c.s, c.pad) + b.astype(self.dtype)
                 if op.act == ACT_SILU:
                     y = silu(y)
                 if op.res is not None:
                     y = y + self.bufs[op.res.buf][..., op.res.choff:op.res.choff + op.dst.c]
                 self.bufs[op.dst.buf][..., op.dst.choff:op.dst.choff + op.dst.c] = y
+            elif op.type == OP_ATTN:
+                src = self.bufs[op.src.buf][..., op.src.choff:op.src.choff + op.src.c]
+                self.bufs[op.dst.buf][..., op.dst.choff:op.dst.choff + op.dst.c] = psa_attention(src, op.heads, op.k, op.s)
             elif op.type == OP_UPSAMPLE:
                 src = self.bufs[op.src.buf][..., op.src.choff:op.src.choff + op.src.c]
                 self.bufs[op.dst.buf][..., op.dst.choff:op.dst.choff + op.dst.c] = src.repeat(2, 1).repeat(2, 2)

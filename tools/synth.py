@@ -48,22 +48,31 @@ def synthetic_state_dict(prog: Program, seed: int = 0) -> Dict[str, np.ndarray]:
 
     def get_wb(ci: int, src: np.ndarray):
         from .program_ref import conv_nhwc
+        from .program_ref import dwconv_nhwc
         c = prog.convs[ci]
-        fan_in = c.cin * c.k * c.k
+        cig = c.cin // c.groups
+        fan_in = cig * c.k * c.k
         if c.has_bn:
-            w = (rng.standard_normal((c.cout, c.cin, c.k, c.k)) / np.sqrt(fan_in)).astype(f32)
+            w = (rng.standard_normal((c.cout, cig, c.k, c.k)) / np.sqrt(fan_in)).astype(f32)
             gamma = rng.uniform(0.7, 1.3, c.cout).astype(f32)
             beta = (rng.standard_normal(c.cout) * 0.5).astype(f32)
-            y = conv_nhwc(src, w.astype(np.float64), c.s, c.pad)
+            # checkpoint channel order; a permuted conv (graph.ConvSpec.rows) computes them in program order
+            inv = np.argsort(c.rows) if c.rows is not None else None
+            y = (dwconv_nhwc if c.groups > 1 else conv_nhwc)(src, w.astype(np.float64), c.s, c.pad)
+            if inv is not None:
+                w = np.ascontiguousarray(w[inv])
+                y = y[..., inv]
             rmean = _q12(y.mean((0, 1, 2))).astype(f32)
             rvar = _q12(y.var((0, 1, 2)) + 1e-6).astype(f32)
-            sd[f"{c.name}.conv.weight"] = w
-            sd[f"{c.name}.bn.weight"] = gamma
-            sd[f"{c.name}.bn.bias"] = beta
-            sd[f"{c.name}.bn.running_mean"] = rmean
-            sd[f"{c.name}.bn.running_var"] = rvar
+            nm = c.sd_name or c.name
+            sd[f"{nm}.conv.weight"] = w
+            sd[f"{nm}.bn.weight"] = gamma
+            sd[f"{nm}.bn.bias"] = beta
+            sd[f"{nm}.bn.running_mean"] = rmean
+            sd[f"{nm}.bn.running_var"] = rvar
             scale = gamma.astype(np.float64) / np.sqrt(1e-3 + rvar.astype(np.float64))
-            return w.astype(np.float64) * scale[:, None, None, None], beta - rmean * scale
+            wf, bf = w.astype(np.float64) * scale[:, None, None, None], beta - rmean * scale
+            return (wf[list(c.rows)], bf[list(c.rows)]) if c.rows is not None else (wf, bf)
         branch = c.name.split(".")[2]                                  # cv2 (box) / cv3 (cls) / cv4 (kpt)
         t = {"cv2": BOX_LOGIT_STD, "cv3": CLS_LOGIT_STD}.get(branch, KPT_STD)
         m2 = float(_q12((src * src).mean()))
@@ -84,7 +93,7 @@ def synthetic_state_dict(prog: Program, seed: int = 0) -> Dict[str, np.ndarray]:
         return w.astype(np.float64), bias.astype(np.float64)
 
     ProgramExecutor(prog, np.float64).run(x, get_wb)
-    sd["model.%d.dfl.conv.weight" % (22 if prog.family == "v8" else 24)] = \
+    sd["model.%d.dfl.conv.weight" % {"v8": 22, "v5u": 24, "v11": 23}[prog.family]] = \
         np.arange(16, dtype=f32).reshape(1, 16, 1, 1)
     return sd
 
