@@ -144,6 +144,11 @@ SIGNATURES = {
     "mi355_op_letterbox": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mi355_letterbox_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _P(C.c_double)]),
     "mi355_op_letterbox_multi": (C.c_int, [C.c_int, C.c_void_p, _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_void_p]),
+    "mi355_shopformer_create": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, _P(C.c_void_p)]),
+    "mi355_shopformer_destroy": (None, [C.c_void_p]),
+    "mi355_shopformer_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi355_shopformer_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi355_shopformer_score_device_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi355_op_nms": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,
                                C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
 }

@@ -1,0 +1,39 @@
+// Shopformer score path: what the host unit (shopformer_host.hip) hands to the one kernel (shopformer_kernels.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace mi355 {
+
+constexpr int SF_MAX_LAYERS = 4;
+constexpr int SF_MAX_V = 18;          // joints per pose the register-resident A.X step is unrolled for
+constexpr int SF_THREADS = 512;       // 8 waves, 2 per SIMD
+constexpr int SF_LDS_BYTES = 160 * 1024;
+
+struct SfLin  { const float* w; const float* b; };      // w: packed A-operand fragments (shopformer.py:pack_mfma), b: bias padded to 16
+struct SfNorm { const float* g; const float* b; };
+struct SfAttn { SfLin q, kv, out; };
+struct SfEnc  { SfAttn sa; SfNorm n1; SfLin f1, f2; SfNorm n2; };
+struct SfDec  { SfAttn sa; SfNorm n1; SfAttn ca; SfNorm n2; SfLin f1, f2; SfNorm n3; };
+struct SfBlock { const float *gw, *gb, *tw, *tb, *rw, *rb; };     // rw == nullptr: identity residual; block 0: gw / rw plain [H][2]
+
+struct SfParams {
+    int V, T, H, L, heads, layers, ff, D, ntok, nnz;
+    int s[4], Tn[5];
+    int G;                                 // windows per workgroup
+    int csH, csD, csQ, csF;                // LDS row strides (floats), each 4 * odd: 16 rows of float4 reads hit 64 distinct banks
+    int offXin, offAx, offP, offQ;         // LDS regions (floats): normalised input, A.X of it, ping, pong
+    float att_scale;                       // 1 / sqrt(head_dim)
+    const float *in_scale, *in_shift, *adj_col, *adj_val, *pe_in, *pe_score;
+    SfBlock blk[4];
+    SfEnc enc[SF_MAX_LAYERS];
+    SfDec dec[SF_MAX_LAYERS];
+    SfLin proj;
+};
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) for the CURRENT device (the attribute is per device): once per handle, at create
+const char* prepare_shopformer_device();
+// one launch for n windows, parameters in device memory; *launches is incremented per kernel launch; nullptr or the HIP error string
+const char* launch_shopformer(const SfParams* p_dev, int group, const float* windows, int n, float* scores, float* tokens, float* recon,
+                              hipStream_t stream, long long* launches);
+
+}  // namespace mi355

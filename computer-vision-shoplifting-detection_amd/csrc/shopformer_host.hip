@@ -1,0 +1,235 @@
+// Shopformer score path, host side: parse the weight image (cvsd_amd/shopformer.py:build_image), upload it, plan LDS, and the C ABI
+// mi355_shopformer_* of include/mi355_yolo.h.  One kernel launch per call whatever the number of windows (shopformer_kernels.hip).
+#include "engine_internal.h"
+#include "shopformer.h"
+
+#include <cmath>
+#include <cstring>
+#include <map>
+
+using namespace mi355;
+
+struct mi355_shopformer {
+    int device = 0;
+    SfParams p{};
+    SfParams* d_params = nullptr;       // the kernel reads its parameters from device memory
+    float* d_weights = nullptr;
+    long long launches = 0;             // kernel launches enqueued through this handle
+    float *d_win = nullptr, *d_score = nullptr, *d_tok = nullptr, *d_rec = nullptr;
+    size_t cap = 0;                     // windows the staging buffers hold
+    hipStream_t stream = nullptr;
+    long long n_params = 0, macs = 0;
+    int lds_bytes = 0;
+    ~mi355_shopformer() {
+        if (d_weights) (void)hipFree(d_weights);
+        if (d_params) (void)hipFree(d_params);
+        for (float* q : {d_win, d_score, d_tok, d_rec}) if (q) (void)hipFree(q);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+
+struct Entry { uint32_t kind, d[3]; uint64_t off, count; };
+const char* kCfg[] = {"V", "T", "H", "L", "heads", "layers", "ff", "D", "ntok", "nnz", "s0", "s1", "s2", "s3", "T1", "T2", "T3", "T4"};
+constexpr int kNCfg = 18;
+
+int pad_stride(int k) { int c = (k + 3) / 4 * 4; if (((c / 4) & 1) == 0) c += 4; return c; }   // 4 * odd
+
+int in_set(int v, std::initializer_list<int> s) { for (int x : s) if (x == v) return 1; return 0; }
+
+int create_impl_sf(const uint8_t* blob, size_t nbytes, int device, mi355_shopformer** out) {
+    if (!blob || !out) return fail(MI355_EINVAL, "null argument");
+    if (nbytes < 24 || std::memcmp(blob, "MI355SF1", 8) != 0) return fail(MI355_EFORMAT, "not a Shopformer weight image (bad magic)");
+    uint32_t ver, ncfg;
+    std::memcpy(&ver, blob + 8, 4); std::memcpy(&ncfg, blob + 12, 4);
+    if (ver != 1 || ncfg != kNCfg) return fail(MI355_EFORMAT, "unsupported Shopformer weight image version");
+    size_t pos = 16;
+    int cfg[kNCfg];
+    if (nbytes < pos + 4 * kNCfg + 4) return fail(MI355_EFORMAT, "truncated Shopformer weight image");
+    std::memcpy(cfg, blob + pos, 4 * kNCfg); pos += 4 * kNCfg;
+    uint32_t nent; std::memcpy(&nent, blob + pos, 4); pos += 4;
+    const size_t rec = 32 + 4 + 12 + 16;
+    if (nent > 4096 || nbytes < pos + nent * rec) return fail(MI355_EFORMAT, "truncated Shopformer weight image");
+    std::map<std::string, Entry> tab;
+    for (uint32_t i = 0; i < nent; ++i) {
+        const uint8_t* r = blob + pos + i * rec;
+        char name[33] = {0}; std::memcpy(name, r, 32);
+        Entry e; std::memcpy(&e.kind, r + 32, 4); std::memcpy(e.d, r + 36, 12); std::memcpy(&e.off, r + 48, 8); std::memcpy(&e.count, r + 56, 8);
+        tab[name] = e;
+    }
+    pos += nent * rec; pos += (16 - pos % 16) % 16;
+    const size_t nfloats = (nbytes - pos) / 4;
+    for (auto& kv : tab)
+        if (kv.second.off > nfloats || kv.second.count > nfloats - kv.second.off || kv.second.off % 4)       // no wrap; float4 reads
+            return fail(MI355_EFORMAT, "Shopformer weight image: tensor '" + kv.first + "' lies outside the file");
+
+    std::unique_ptr<mi355_shopformer> h(new mi355_shopformer);
+    SfParams& p = h->p;
+    p.V = cfg[0]; p.T = cfg[1]; p.H = cfg[2]; p.L = cfg[3]; p.heads = cfg[4]; p.layers = cfg[5]; p.ff = cfg[6]; p.D = cfg[7]; p.ntok = cfg[8]; p.nnz = cfg[9];
+    for (int i = 0; i < 4; ++i) { p.s[i] = cfg[10 + i]; p.Tn[i + 1] = cfg[14 + i]; }
+    p.Tn[0] = p.T;
+    // the kernel's envelope (the Python loader refuses the same fields by name before an image is ever built)
+    auto bad = [&](const char* f, int v) { return fail(MI355_EFORMAT, std::string("Shopformer weight image: unsupported ") + f + " = " + std::to_string(v)); };
+    if (!in_set(p.V, {17, 18})) return bad("num_keypoints", p.V);
+    if (!in_set(p.T, {12, 24})) return bad("seq_len", p.T);
+    if (!in_set(p.H, {32, 64})) return bad("hidden_channels", p.H);
+    if (!in_set(p.L, {4, 8})) return bad("latent_channels", p.L);
+    if (!in_set(p.heads, {1, 2, 4}) || p.D != p.L * p.V || p.D % p.heads) return bad("transformer_heads", p.heads);
+    if (p.layers < 1 || p.layers > SF_MAX_LAYERS) return bad("transformer_layers", p.layers);
+    if (p.ff <= 0 || p.ff % 4 || p.ff > 64) return bad("transformer_ff_dim", p.ff);
+    if (p.nnz < 1 || p.nnz > p.V) return bad("adjacency row length", p.nnz);
+    for (int i = 0; i < 4; ++i) {
+        if (!in_set(p.s[i], {1, 2}) || p.Tn[i + 1] != (p.Tn[i] - 1) / p.s[i] + 1) return bad("block stride", p.s[i]);
+    }
+    if (p.ntok != p.Tn[4] || p.ntok < 1 || p.ntok > 8) return bad("token count", p.ntok);
+    p.att_scale = 1.0f / std::sqrt((float)(p.D / p.heads));
+    p.csH = pad_stride(p.H); p.csD = pad_stride(p.D); p.csQ = pad_stride(3 * p.D); p.csF = pad_stride(p.ff);
+
+    // LDS plan: the largest group of windows that fits (floats; every region a multiple of 4)
+    auto plan = [&](int G, int* offs) {
+        const int in = (G * p.T * p.V * 2 + 3) / 4 * 4;
+        const int rows = G * p.ntok;
+        const int tf = rows * (5 * p.csD + p.csQ + p.csF) + (G * p.heads * p.ntok * p.ntok + 3) / 4 * 4;
+        const int P = std::max(G * p.Tn[1] * p.V * p.csH, tf);
+        const int Q = G * std::max(p.Tn[2], p.Tn[4]) * p.V * p.csH;
+        offs[0] = 0; offs[1] = in; offs[2] = 2 * in; offs[3] = 2 * in + P;
+        return (2 * in + P + Q) * 4;
+    };
+    int offs[4], G = 0;
+    for (int g = 8; g >= 1; --g) if (plan(g, offs) <= SF_LDS_BYTES) { G = g; break; }
+    if (!G) return fail(MI355_EFORMAT, "Shopformer weight image: one window does not fit the 160 KiB of LDS");
+    h->lds_bytes = plan(G, offs);
+    p.G = G; p.offXin = offs[0]; p.offAx = offs[1]; p.offP = offs[2]; p.offQ = offs[3];
+
+    // adjacency columns must stay inside a pose (they index LDS rows)
+    const float* data = (const float*)(blob + pos);
+    bool missing = false; std::string miss;
+    auto host = [&](const std::string& n) -> const Entry* { auto it = tab.find(n); if (it == tab.end()) { missing = true; miss = n; return nullptr; } return &it->second; };
+    if (const Entry* e = host("adj_col")) {
+        if (e->count < (uint64_t)p.V * p.nnz) return fail(MI355_EFORMAT, "Shopformer weight image: adjacency table too short");
+        for (int i = 0; i < p.V * p.nnz; ++i) { const float c = data[e->off + i]; if (!(c >= 0.f && c <= (float)(p.V - 1)) || c != std::floor(c)) return fail(MI355_EFORMAT, "Shopformer weight image: adjacency column outside the pose"); }
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MI355_EHIP, "no HIP device: the Shopformer kernel needs an MI355X (there is no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(MI355_EINVAL, "device index out of range");
+    h->device = device;
+    HIPCHK(hipSetDevice(device));
+    KCHK(prepare_shopformer_device());
+    HIPCHK(hipMalloc(&h->d_weights, std::max<size_t>(nfloats, 4) * 4));
+    HIPCHK(hipMemcpy(h->d_weights, data, nfloats * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+
+    // packed: [tiles of 16 out][taps][blocks of 16 in][256]; plain: at least `need` floats
+    auto packed = [&](const std::string& n, int co, int taps, int ci) -> const float* {
+        const Entry* e = host(n); if (!e) return nullptr;
+        const uint64_t want = (uint64_t)((co + 15) / 16) * taps * ((ci + 15) / 16) * 256;
+        if (e->kind != 1 || (int)e->d[0] != co || (int)e->d[1] != taps || (int)e->d[2] != ci || e->count != want) { missing = true; miss = n + " (shape)"; return nullptr; }
+        h->n_params += (long long)co * taps * ci;
+        return h->d_weights + e->off;
+    };
+    auto plain = [&](const std::string& n, int need) -> const float* {
+        const Entry* e = host(n); if (!e) return nullptr;
+        if (e->kind != 0 || e->count < (uint64_t)((need + 15) / 16 * 16)) { missing = true; miss = n + " (shape)"; return nullptr; }
+        h->n_params += need;
+        return h->d_weights + e->off;
+    };
+    auto lin = [&](const std::string& n, int o, int i) { SfLin l; l.w = packed(n + ".w", o, 1, i); l.b = plain(n + ".b", o); return l; };
+    auto norm = [&](const std::string& n) { SfNorm l; l.g = plain(n + ".g", p.D); l.b = plain(n + ".b", p.D); return l; };
+    auto attn = [&](const std::string& n) { SfAttn a; a.q = lin(n + ".q", p.D, p.D); a.kv = lin(n + ".kv", 2 * p.D, p.D); a.out = lin(n + ".out", p.D, p.D); return a; };
+    p.in_scale = plain("in_scale", 2 * p.V); p.in_shift = plain("in_shift", 2 * p.V);
+    p.adj_col = plain("adj_col", p.V * p.nnz); p.adj_val = plain("adj_val", p.V * p.nnz);
+    p.pe_in = plain("pe_in", p.ntok * p.D); p.pe_score = plain("pe_score", p.ntok * p.D);
+    const int ch[5] = {2, p.H, p.H, p.H, p.L};
+    for (int b = 0; b < 4; ++b) {
+        const std::string n = "b" + std::to_string(b);
+        const bool conv_res = ch[b] != ch[b + 1] || p.s[b] != 1;
+        SfBlock& k = p.blk[b];
+        k.gw = b == 0 ? plain(n + ".gw", 2 * p.H) : packed(n + ".gw", ch[b + 1], 1, ch[b]);
+        k.gb = plain(n + ".gb", ch[b + 1]);
+        k.tw = packed(n + ".tw", ch[b + 1], 9, ch[b + 1]); k.tb = plain(n + ".tb", ch[b + 1]);
+        k.rw = !conv_res ? nullptr : b == 0 ? plain(n + ".rw", 2 * p.H) : packed(n + ".rw", ch[b + 1], 1, ch[b]);
+        k.rb = conv_res ? plain(n + ".rb", ch[b + 1]) : nullptr;
+    }
+    for (int e = 0; e < p.layers; ++e) {
+        const std::string a = "e" + std::to_string(e), d = "d" + std::to_string(e);
+        p.enc[e] = SfEnc{attn(a + ".sa"), norm(a + ".n1"), lin(a + ".f1", p.ff, p.D), lin(a + ".f2", p.D, p.ff), norm(a + ".n2")};
+        p.dec[e] = SfDec{attn(d + ".sa"), norm(d + ".n1"), attn(d + ".ca"), norm(d + ".n2"), lin(d + ".f1", p.ff, p.D), lin(d + ".f2", p.D, p.ff), norm(d + ".n3")};
+    }
+    p.proj = lin("proj", p.D, p.D);
+    if (missing) return fail(MI355_EFORMAT, "Shopformer weight image: tensor '" + miss + "' is missing or has the wrong shape");
+    // multiply-accumulates per window, zero-padding taps not counted
+    long long macs = 0;
+    for (int b = 0; b < 4; ++b) {
+        long long taps = 0;
+        for (int to = 0; to < p.Tn[b + 1]; ++to) for (int k = 0; k < 9; ++k) { const int ti = to * p.s[b] + k - 4; taps += ti >= 0 && ti < p.Tn[b]; }
+        macs += (long long)p.V * (taps * ch[b + 1] * ch[b + 1] + (long long)p.Tn[b] * ch[b] * ch[b + 1] + (p.blk[b].rw ? (long long)p.Tn[b + 1] * ch[b] * ch[b + 1] : 0));
+    }
+    const long long at = 4LL * p.D * p.D, ffm = 2LL * p.D * p.ff;
+    macs += (long long)p.ntok * (p.layers * (at + ffm) + p.layers * (2 * at + ffm) + (long long)p.D * p.D);
+    h->macs = macs;
+    HIPCHK(hipMalloc(&h->d_params, sizeof(SfParams)));
+    HIPCHK(hipMemcpy(h->d_params, &p, sizeof(SfParams), hipMemcpyHostToDevice));
+    *out = h.release();
+    return MI355_OK;
+}
+
+int ensure_cap(mi355_shopformer* h, size_t n) {
+    if (n <= h->cap) return MI355_OK;
+    for (float** q : {&h->d_win, &h->d_score, &h->d_tok, &h->d_rec}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    h->cap = 0;
+    const SfParams& p = h->p;
+    HIPCHK(hipMalloc(&h->d_win, n * 2 * p.T * p.V * 4));
+    HIPCHK(hipMalloc(&h->d_score, n * 4));
+    HIPCHK(hipMalloc(&h->d_tok, n * p.ntok * p.D * 4));
+    HIPCHK(hipMalloc(&h->d_rec, n * p.ntok * p.D * 4));
+    h->cap = n;
+    return MI355_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi355_shopformer_create(const void* image, size_t nbytes, int device_id, mi355_shopformer** out) {
+    return create_impl_sf((const uint8_t*)image, nbytes, device_id, out);
+}
+
+void mi355_shopformer_destroy(mi355_shopformer* h) { delete h; }
+
+int mi355_shopformer_info(const mi355_shopformer* h, mi355_shopformer_info_t* info) {
+    if (!h || !info) return fail(MI355_EINVAL, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    const SfParams& p = h->p;
+    info->num_keypoints = p.V; info->seq_len = p.T; info->hidden_channels = p.H; info->latent_channels = p.L; info->heads = p.heads;
+    info->layers = p.layers; info->n_tokens = p.ntok; info->d_model = p.D; info->group = p.G; info->lds_bytes = h->lds_bytes;
+    info->launches = h->launches; info->n_params = h->n_params; info->macs_per_window = h->macs;
+    return MI355_OK;
+}
+
+int mi355_shopformer_score_device_async(mi355_shopformer* h, const float* windows_dev, int n, float* scores_dev, float* tokens_dev,
+                                        float* recon_dev, void* stream) {
+    if (!h || n < 0 || (n > 0 && (!windows_dev || !scores_dev))) return fail(MI355_EINVAL, "null argument or negative count");
+    if (n == 0) return MI355_OK;
+    HIPCHK(hipSetDevice(h->device));
+    KCHK(launch_shopformer(h->d_params, h->p.G, windows_dev, n, scores_dev, tokens_dev, recon_dev, (hipStream_t)stream, &h->launches));
+    return MI355_OK;
+}
+
+int mi355_shopformer_score(mi355_shopformer* h, const float* windows, int n, float* scores, float* tokens, float* recon) {
+    if (!h || n < 0 || (n > 0 && (!windows || !scores))) return fail(MI355_EINVAL, "null argument or negative count");
+    if (n == 0) return MI355_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const int rc = ensure_cap(h, (size_t)n); if (rc) return rc;
+    const SfParams& p = h->p;
+    const size_t per = (size_t)p.ntok * p.D * 4;
+    HIPCHK(hipMemcpyAsync(h->d_win, windows, (size_t)n * 2 * p.T * p.V * 4, hipMemcpyHostToDevice, h->stream));
+    KCHK(launch_shopformer(h->d_params, p.G, h->d_win, n, h->d_score, tokens ? h->d_tok : nullptr, recon ? h->d_rec : nullptr, h->stream, &h->launches));
+    HIPCHK(hipMemcpyAsync(scores, h->d_score, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (tokens) HIPCHK(hipMemcpyAsync(tokens, h->d_tok, n * per, hipMemcpyDeviceToHost, h->stream));
+    if (recon) HIPCHK(hipMemcpyAsync(recon, h->d_rec, n * per, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MI355_OK;
+}
+
+}  // extern "C"

@@ -395,6 +395,30 @@ int  mi355_op_nms(int device_id, const float* pred, int n, int nc, int extra, in
                   const int* classes, int n_classes, int max_det, mi355_det* out_rows, int out_capacity_per_image,
                   int* out_counts);
 
+/* ---- Shopformer: pose windows -> anomaly score ----------------------------------------------------------------
+ * The score path of the reference's shopformer/ network in eval() mode as one fused kernel launch per call, whatever n is.
+ * `image` is the weight image cvsd_amd/shopformer.py builds from a checkpoint (folded BatchNorms, matrices in MFMA fragment order).
+ * windows [n][2][seq_len][num_keypoints] fp32, normalised as the reference's loader does; scores [n]; tokens and recon
+ * [n][n_tokens][d_model] or NULL.  A window's outputs do not depend on n or on its position in the batch, bit for bit.
+ * The device_async form takes device pointers, enqueues the one launch on the caller's stream (NULL = the null stream) and returns.
+ * The blocking form stages through buffers and a stream owned by the handle: one call at a time per handle (not re-entrant); use one
+ * handle per thread, or the device_async form with buffers of the caller. */
+typedef struct mi355_shopformer mi355_shopformer;
+typedef struct {
+    int num_keypoints, seq_len, hidden_channels, latent_channels, heads, layers, n_tokens, d_model;
+    int group;              /* windows per workgroup */
+    int lds_bytes;          /* LDS the plan of that group uses */
+    int reserved[2];
+    long long n_params, macs_per_window;
+    long long launches;     /* kernel launches this handle has enqueued so far: a counter incremented beside the launch itself */
+} mi355_shopformer_info_t;
+int  mi355_shopformer_create(const void* image, size_t nbytes, int device_id, mi355_shopformer** out);
+void mi355_shopformer_destroy(mi355_shopformer* h);
+int  mi355_shopformer_info(const mi355_shopformer* h, mi355_shopformer_info_t* info);
+int  mi355_shopformer_score(mi355_shopformer* h, const float* windows, int n, float* scores, float* tokens, float* recon);
+int  mi355_shopformer_score_device_async(mi355_shopformer* h, const float* windows_dev, int n, float* scores_dev, float* tokens_dev,
+                                         float* recon_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
