@@ -1,4 +1,5 @@
-// Shopformer score path: what the host unit (shopformer_host.hip) hands to the one kernel (shopformer_kernels.hip).
+// Shopformer score path: what the host unit (shopformer_host.hip) hands to the kernels (shopformer_kernels.hip).
+// Variant 1 (shopformer/) is one kernel; variant 2 (shopformer_2/) is two: the tokenizer, then the transformer over larger row groups.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +29,12 @@ struct SfParams {
     SfEnc enc[SF_MAX_LAYERS];
     SfDec dec[SF_MAX_LAYERS];
     SfLin proj;
+    // ---- variant 2 only (version-2 images).  D is d_model there, Din = L * V the token width; csD covers max(D, Din)
+    int variant, Din, in_proj, out_proj;
+    int GT;                                // windows per workgroup of the transformer launch (16 = two 16-row MFMA tiles of 2 tokens)
+    int offTgt, offX, offNb, offU, offSc;  // LDS regions of the transformer launch (floats)
+    SfLin inp, outp;                       // input / output projection (in_proj / out_proj)
+    SfNorm en, dn;                         // final norms of the encoder and the decoder
 };
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) for the CURRENT device (the attribute is per device): once per handle, at create
@@ -35,5 +42,10 @@ const char* prepare_shopformer_device();
 // one launch for n windows, parameters in device memory; *launches is incremented per kernel launch; nullptr or the HIP error string
 const char* launch_shopformer(const SfParams* p_dev, int group, const float* windows, int n, float* scores, float* tokens, float* recon,
                               hipStream_t stream, long long* launches);
+
+// variant 2: launch 1 writes tokens [n][ntok][Din] to HBM (the caller's buffer or the handle's scratch), launch 2 reads them back in
+// groups of GT windows and writes scores [n], token_scores [n][ntok] and recon [n][ntok][Din] (each may be nullptr); 2 launches
+const char* launch_shopformer2(const SfParams* p_dev, int group, int group_tf, int lds_tok, int lds_tf, const float* windows, int n,
+                               float* tokens, float* scores, float* token_scores, float* recon, hipStream_t stream, long long* launches);
 
 }  // namespace mi355

@@ -16,7 +16,10 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-enum { MM_RELU = 1, MM_ACC_INIT = 2, MM_FIRST = 4 };
+enum { MM_RELU = 1, MM_ACC_INIT = 2, MM_FIRST = 4, MM_GELU = 8 };
+
+// exact (erf) GELU; the device library's erff is straight-line code on its argument: the same bits at every position
+__device__ __forceinline__ float sf_gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 struct Mm {
     const float* in; int in_cs, K;        // LDS rows of K features (K % 4 == 0); MM_FIRST: rows of 2 floats (A.X of the input)
@@ -28,6 +31,7 @@ struct Mm {
     int Tin, Tout;
     int flags;
     const float *w0, *b0;                 // MM_FIRST: block 0's graph-conv weights [H][2] and bias (global)
+    int ncm;                              // output tiles of 16 a wave takes per job: 0 = 4; 1 or 2 spread a narrow layer over more waves
 };
 
 // B-operand fragment: 4 consecutive input features of one activation row (zeros beyond K)
@@ -51,11 +55,12 @@ __device__ void sf_mm(const Mm& a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     const int j = lane & 15, q = lane >> 4;
     const int mtiles = (a.R + 15) >> 4, mpairs = (mtiles + 1) >> 1;
-    const int nct = (a.N + 15) >> 4, nchunks = (nct + 3) >> 2, cib = (a.K + 15) >> 4;
+    const int ncm = a.ncm ? a.ncm : 4;    // a chain's order does not depend on how the output tiles are dealt out
+    const int nct = (a.N + 15) >> 4, nchunks = (nct + ncm - 1) / ncm, cib = (a.K + 15) >> 4;
     const int njobs = a.Tout * mpairs * nchunks;
     for (int job = wave; job < njobs; job += nwaves) {
         const int chunk = job % nchunks, mp = (job / nchunks) % mpairs, to = job / (nchunks * mpairs);
-        const int ct0 = chunk * 4, nc = min(4, nct - ct0);
+        const int ct0 = chunk * ncm, nc = min(ncm, nct - ct0);
         int in_base[2], out_row[2];
         bool live[2];
 #pragma unroll
@@ -107,6 +112,9 @@ __device__ void sf_mm(const Mm& a) {
                     if (a.flags & MM_RELU)
 #pragma unroll
                         for (int s = 0; s < 4; ++s) r[s] = __builtin_fmaxf(r[s], 0.f);
+                    if (a.flags & MM_GELU)
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) r[s] = sf_gelu(r[s]);
                     *reinterpret_cast<f32x4*>(a.out + out_row[mt] * a.out_cs + n0) = r;
                 }
             }
@@ -114,8 +122,9 @@ __device__ void sf_mm(const Mm& a) {
 }
 
 // plain rows x K -> rows x N
-__device__ void sf_linear(const float* in, int in_cs, int K, float* out, int out_cs, int N, SfLin l, int rows, int flags) {
+__device__ void sf_linear(const float* in, int in_cs, int K, float* out, int out_cs, int N, SfLin l, int rows, int flags, int ncm = 0) {
     Mm a{};
+    a.ncm = ncm;
     a.in = in; a.in_cs = in_cs; a.K = K; a.out = out; a.out_cs = out_cs; a.N = N; a.w = l.w; a.bias = l.b;
     a.ntaps = 1; a.stride = 1; a.pad = 0; a.V = rows; a.R = rows; a.in_w = 0; a.out_w = 0; a.Tin = 1; a.Tout = 1; a.flags = flags;
     sf_mm(a);
@@ -172,11 +181,11 @@ __device__ void sf_add_norm(const float* a, const float* b, float* out, int cs, 
 
 struct SfBufs { float *tok, *src, *tgt, *qkv, *att, *tmp, *ffb, *sc; };
 
-// x <- LayerNorm(x + out_proj(softmax(q k^T * scale) v)); q from x, k / v from kvsrc; all windows of the group, no mask
-__device__ void sf_attention(const SfParams& p, const SfBufs& B, float* x, const float* kvsrc, const SfAttn& at, SfNorm nrm, int nwin) {
+// B.att <- softmax(q k^T * scale) v per window and head; q from x, k / v from kvsrc; all windows of the group, no mask
+__device__ void sf_attn_core(const SfParams& p, const SfBufs& B, const float* x, const float* kvsrc, const SfAttn& at, int nwin, int ncm) {
     const int D = p.D, rows = nwin * p.ntok, hd = D / p.heads, nt = p.ntok;
-    sf_linear(x, p.csD, D, B.qkv, p.csQ, D, at.q, rows, 0);
-    sf_linear(kvsrc, p.csD, D, B.qkv + D, p.csQ, 2 * D, at.kv, rows, 0);
+    sf_linear(x, p.csD, D, B.qkv, p.csQ, D, at.q, rows, 0, ncm);
+    sf_linear(kvsrc, p.csD, D, B.qkv + D, p.csQ, 2 * D, at.kv, rows, 0, ncm);
     __syncthreads();
     const int cq = p.csQ;
     for (int it = threadIdx.x; it < nwin * p.heads * nt * nt; it += blockDim.x) {
@@ -205,6 +214,12 @@ __device__ void sf_attention(const SfParams& p, const SfBufs& B, float* x, const
         B.att[r * p.csD + f] = o;
     }
     __syncthreads();
+}
+
+// x <- LayerNorm(x + out_proj(attention)): the post-norm form of variant 1
+__device__ void sf_attention(const SfParams& p, const SfBufs& B, float* x, const float* kvsrc, const SfAttn& at, SfNorm nrm, int nwin) {
+    const int D = p.D, rows = nwin * p.ntok;
+    sf_attn_core(p, B, x, kvsrc, at, nwin, 0);
     sf_linear(B.att, p.csD, D, B.tmp, p.csD, D, at.out, rows, 0);
     __syncthreads();
     sf_add_norm(x, B.tmp, x, p.csD, D, rows, nrm);
@@ -220,12 +235,9 @@ __device__ void sf_ffn(const SfParams& p, const SfBufs& B, float* x, SfLin f1, S
     __syncthreads();
 }
 
-__global__ __launch_bounds__(SF_THREADS) void shopformer_kernel(const SfParams* __restrict__ pp, const float* __restrict__ windows, int n,
-                                                                 float* __restrict__ scores, float* __restrict__ tokens, float* __restrict__ recon) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const SfParams& p = *pp;              // device memory, uniform: scalar loads, no private copy of the per-layer tables
-    const int w0 = blockIdx.x * p.G, nwin = min(p.G, n - w0);
-    if (nwin <= 0) return;
+// the tokenizer both variants share: bn_input and the four ST-GCN blocks for windows w0 .. w0 + nwin - 1, everything in LDS;
+// -> the region that holds the tokens as [win][tok][v][c < L] rows of csH floats
+__device__ __forceinline__ float* sf_tokenizer(const SfParams& p, const float* __restrict__ windows, int w0, int nwin, float* lds) {
     const int V = p.V, T = p.T, H = p.H, TV = T * V;
     float* xin = lds + p.offXin;       // [win][t][v][2] after bn_input
     float* ax = lds + p.offAx;         // A . xin
@@ -295,6 +307,18 @@ __global__ __launch_bounds__(SF_THREADS) void shopformer_kernel(const SfParams* 
         __syncthreads();
         float* t = cur; cur = oth; oth = t;
     }
+    return cur;
+}
+
+__global__ __launch_bounds__(SF_THREADS) void shopformer_kernel(const SfParams* __restrict__ pp, const float* __restrict__ windows, int n,
+                                                                 float* __restrict__ scores, float* __restrict__ tokens, float* __restrict__ recon) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const SfParams& p = *pp;              // device memory, uniform: scalar loads, no private copy of the per-layer tables
+    const int w0 = blockIdx.x * p.G, nwin = min(p.G, n - w0);
+    if (nwin <= 0) return;
+    const int V = p.V;
+    float* P = lds + p.offP;
+    const float* cur = sf_tokenizer(p, windows, w0, nwin, lds);
     // ---- tokens: cur = Q holds [win][tok][v][c < L]; the transformer's buffers take over P
     const int D = p.D, nt = p.ntok, rows = nwin * nt, rowsG = p.G * nt;
     SfBufs B;
@@ -337,10 +361,152 @@ __global__ __launch_bounds__(SF_THREADS) void shopformer_kernel(const SfParams* 
     }
 }
 
+// ================================================================================================ variant 2
+// launch 1: the tokenizer alone; tokens [n][ntok][Din] go to HBM
+__global__ __launch_bounds__(SF_THREADS) void shopformer2_tok_kernel(const SfParams* __restrict__ pp, const float* __restrict__ windows, int n,
+                                                                      float* __restrict__ tokens) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const SfParams& p = *pp;
+    const int w0 = blockIdx.x * p.G, nwin = min(p.G, n - w0);
+    if (nwin <= 0) return;
+    const float* cur = sf_tokenizer(p, windows, w0, nwin, lds);
+    const int V = p.V, Din = p.Din, rows = nwin * p.ntok;
+    for (int it = threadIdx.x; it < rows * Din; it += blockDim.x) {
+        const int r = it / Din, f = it - r * Din, c = f / V, v = f - c * V;
+        tokens[((size_t)w0 * p.ntok + r) * Din + f] = cur[(r * V + v) * p.csH + c];
+    }
+}
+
+// out[r] = LayerNorm(a[r]) * g + beta, 16 lanes per row: the pre-norm form has the norm alone
+__device__ void sf_norm(const float* a, float* out, int cs, int D, int rows, SfNorm n) {
+    const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4, ngrp = blockDim.x >> 4;
+    for (int r0 = 0; r0 < rows; r0 += ngrp) {                       // uniform trip count: the shuffles need every lane
+        const int r = min(r0 + grp, rows - 1);
+        float s = 0.f;
+        for (int i = sub; i < D; i += 16) s += a[r * cs + i];
+        const float mean = sf_sum16(s) / (float)D;
+        float v = 0.f;
+        for (int i = sub; i < D; i += 16) { const float d = a[r * cs + i] - mean; v = __builtin_fmaf(d, d, v); }
+        const float rstd = 1.0f / sqrtf(sf_sum16(v) / (float)D + 1e-5f);
+        if (r0 + grp < rows)
+            for (int i = sub; i < D; i += 16) out[r * cs + i] = (a[r * cs + i] - mean) * rstd * n.g[i] + n.b[i];
+    }
+}
+
+// output tiles per job for a layer of N features on `rows` rows: the fewest jobs that still give every wave one (bits do not depend on it)
+__device__ __forceinline__ int sf_ncm(int N, int rows, int nwaves) {
+    const int nct = (N + 15) >> 4, mpairs = (((rows + 15) >> 4) + 1) >> 1;
+    if (((nct + 3) >> 2) * mpairs >= nwaves) return 4;
+    if (((nct + 1) >> 1) * mpairs >= nwaves) return 2;
+    return 1;
+}
+
+// x <- x + out_proj(attention(q from LayerNorm(x), k / v from kv (or from that same LayerNorm(x) when kv == nullptr)))
+__device__ void sf_attention_pre(const SfParams& p, const SfBufs& B, float* x, float* nb, const float* kv, const SfAttn& at, SfNorm nrm, int nwin) {
+    const int D = p.D, rows = nwin * p.ntok, nw = blockDim.x >> 6;
+    sf_norm(x, nb, p.csD, D, rows, nrm);
+    __syncthreads();
+    sf_attn_core(p, B, nb, kv ? kv : nb, at, nwin, sf_ncm(D, rows, nw));
+    sf_linear(B.att, p.csD, D, x, p.csD, D, at.out, rows, MM_ACC_INIT, sf_ncm(D, rows, nw));      // the residual add: x starts the chain
+    __syncthreads();
+}
+
+// x <- x + linear2(gelu(linear1(LayerNorm(x))))
+__device__ void sf_ffn_pre(const SfParams& p, float* x, float* nb, float* ffb, SfLin f1, SfLin f2, SfNorm nrm, int rows) {
+    const int nw = blockDim.x >> 6;
+    sf_norm(x, nb, p.csD, p.D, rows, nrm);
+    __syncthreads();
+    sf_linear(nb, p.csD, p.D, ffb, p.csF, p.ff, f1, rows, MM_GELU, sf_ncm(p.ff, rows, nw));
+    __syncthreads();
+    sf_linear(ffb, p.csF, p.ff, x, p.csD, p.D, f2, rows, MM_ACC_INIT, sf_ncm(p.D, rows, nw));
+    __syncthreads();
+}
+
+// launch 2: the transformer on the tokens of GT windows per workgroup (GT * ntok rows: with GT = 16 two full 16-row MFMA tiles), the
+// reconstruction and the scores.  Pre-norm layers, final norms, decoder fed from the encoder's own input, score without PE.
+__global__ __launch_bounds__(SF_THREADS) void shopformer2_tf_kernel(const SfParams* __restrict__ pp, const float* __restrict__ tokens, int n,
+                                                                     float* __restrict__ scores, float* __restrict__ token_scores,
+                                                                     float* __restrict__ recon) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const SfParams& p = *pp;
+    const int w0 = blockIdx.x * p.GT, nwin = min(p.GT, n - w0);
+    if (nwin <= 0) return;
+    const int D = p.D, Din = p.Din, nt = p.ntok, rows = nwin * nt, rowsG = p.GT * nt, cs = p.csD, nw = blockDim.x >> 6;
+    float *tgt = lds + p.offTgt, *x = lds + p.offX, *nb = lds + p.offNb;
+    SfBufs B{};
+    B.qkv = lds + p.offU; B.att = B.qkv + rowsG * p.csQ; B.ffb = lds + p.offU; B.sc = lds + p.offSc;   // qkv + att and ffb are never live together
+    const float* tk = tokens + (size_t)w0 * nt * Din;
+    // ---- x0 = input_projection(tokens) + PE: the encoder works on a copy (x), the decoder on x0 itself (tgt)
+    for (int it = threadIdx.x; it < rows * Din; it += blockDim.x) nb[(it / Din) * cs + it % Din] = tk[it];
+    __syncthreads();
+    if (p.in_proj) {
+        sf_linear(nb, cs, Din, tgt, cs, D, p.inp, rows, 0, sf_ncm(D, rows, nw));
+        __syncthreads();
+    }
+    for (int it = threadIdx.x; it < rows * D; it += blockDim.x) {
+        const int r = it / D, f = it - r * D;
+        const float v = (p.in_proj ? tgt[r * cs + f] : nb[r * cs + f]) + p.pe_in[(r % nt) * D + f];
+        tgt[r * cs + f] = v;
+        x[r * cs + f] = v;
+    }
+    __syncthreads();
+    for (int e = 0; e < p.layers; ++e) {
+        sf_attention_pre(p, B, x, nb, nullptr, p.enc[e].sa, p.enc[e].n1, nwin);
+        sf_ffn_pre(p, x, nb, B.ffb, p.enc[e].f1, p.enc[e].f2, p.enc[e].n2, rows);
+    }
+    sf_norm(x, x, cs, D, rows, p.en);                              // memory; a 16-lane group owns its row
+    __syncthreads();
+    for (int e = 0; e < p.layers; ++e) {
+        sf_attention_pre(p, B, tgt, nb, nullptr, p.dec[e].sa, p.dec[e].n1, nwin);
+        sf_attention_pre(p, B, tgt, nb, x, p.dec[e].ca, p.dec[e].n2, nwin);
+        sf_ffn_pre(p, tgt, nb, B.ffb, p.dec[e].f1, p.dec[e].f2, p.dec[e].n3, rows);
+    }
+    sf_norm(tgt, nb, cs, D, rows, p.dn);
+    __syncthreads();
+    const float* rec = nb;
+    if (p.out_proj) {
+        sf_linear(nb, cs, D, x, cs, Din, p.outp, rows, 0, sf_ncm(Din, rows, nw));
+        __syncthreads();
+        rec = x;
+    }
+    if (recon)
+        for (int it = threadIdx.x; it < rows * Din; it += blockDim.x) recon[((size_t)w0 * nt + it / Din) * Din + it % Din] = rec[(it / Din) * cs + it % Din];
+    // ---- scores: mean over features of (token - reconstruction)^2 per token, and over tokens too per window; 16 lanes per window
+    const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    if (grp < p.GT) {                                              // GT <= 32 groups of 16 lanes; whole groups take the branch together
+        const int w = min(grp, nwin - 1);
+        float tot = 0.f;
+        for (int t = 0; t < nt; ++t) {
+            const int r = w * nt + t;
+            float s = 0.f;
+            for (int f = sub; f < Din; f += 16) { const float d = tk[r * Din + f] - rec[r * cs + f]; s = __builtin_fmaf(d, d, s); }
+            s = sf_sum16(s);
+            tot += s;
+            if (token_scores && sub == 0 && grp < nwin) token_scores[(size_t)(w0 + grp) * nt + t] = s / (float)Din;
+        }
+        if (scores && sub == 0 && grp < nwin) scores[w0 + grp] = tot / (float)(nt * Din);
+    }
+}
+
 }  // namespace
 
 const char* prepare_shopformer_device() {
     hipError_t e = hipFuncSetAttribute((const void*)shopformer_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SF_LDS_BYTES);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)shopformer2_tok_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SF_LDS_BYTES);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)shopformer2_tf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SF_LDS_BYTES);
+    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+const char* launch_shopformer2(const SfParams* p_dev, int group, int group_tf, int lds_tok, int lds_tf, const float* windows, int n,
+                               float* tokens, float* scores, float* token_scores, float* recon, hipStream_t stream, long long* launches) {
+    hipLaunchKernelGGL(shopformer2_tok_kernel, dim3((n + group - 1) / group), dim3(SF_THREADS), lds_tok, stream, p_dev, windows, n, tokens);
+    ++*launches;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hipGetErrorString(e);
+    hipLaunchKernelGGL(shopformer2_tf_kernel, dim3((n + group_tf - 1) / group_tf), dim3(SF_THREADS), lds_tf, stream, p_dev, tokens, n, scores,
+                       token_scores, recon);
+    ++*launches;
+    e = hipGetLastError();
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 

@@ -5,6 +5,10 @@ Only what ``normality_score`` depends on is evaluated: ``bn_input`` -> 4 ST-GCN 
 encoding -> post-norm transformer encoder / decoder (no causal mask) -> ``output_proj`` -> mean squared error against
 ``tokens + PE``.  The GCAE decoder is not part of the score and is not loaded.
 
+A second variant, the reference's ``shopformer_2/`` network (pre-norm ``nn.Transformer`` layers, erf GELU, two real tokens, optional
+input / output projection, per-token scores), is loaded by the same functions: a nested config dict with a ``model``
+key, or ``variant=2``, selects it.  It runs as two launches: the tokenizer, then the transformer over row groups of 16 windows.
+
 This module holds (a) the loader: reference-named state dict -> folded tensors -> a small self-describing weight image whose
 matrices are already in the kernel's MFMA fragment order, (b) ``Shopformer``, the ctypes front of ``mi355_shopformer_*``, and (c) the
 host side between the tracker and the network: ``windows_from_poselift``, ``score_poselift``, ``StreamScorer``.
@@ -32,6 +36,16 @@ DEFAULT_CONFIG = {"seq_len": 12, "num_keypoints": 17, "num_tokens": 2, "hidden_c
 SUPPORTED = {"num_keypoints": (17, 18), "seq_len": (12, 24), "hidden_channels": (32, 64), "latent_channels": (4, 8),
              "transformer_heads": (1, 2, 4), "transformer_layers": (1, 2, 3, 4), "num_tokens": (2,)}
 CFG_FIELDS = ("V", "T", "H", "L", "heads", "layers", "ff", "D", "ntok", "nnz", "s0", "s1", "s2", "s3", "T1", "T2", "T3", "T4")
+# version-2 images (the shopformer_2 variant) carry six more ints; D is d_model, Din = latent_channels * num_keypoints the token width
+IMAGE_VERSION_2 = 2
+CFG_FIELDS_V2 = CFG_FIELDS + ("variant", "Din", "in_proj", "out_proj", "norm_kind", "act_kind")
+NORM_POST, NORM_PRE = 0, 1
+ACT_RELU, ACT_GELU_ERF = 0, 1
+# TransformerConfig's defaults in the reference, used for keys the ``model.transformer`` section leaves out
+DEFAULT_TRANSFORMER_2 = {"input_dim": 144, "d_model": 144, "num_heads": 12, "num_layers": 4, "dim_feedforward": 64}
+SUPPORTED_2 = {"num_keypoints": (17, 18), "seq_len": (12, 24), "gcae.hidden_channels": (32, 64), "gcae.latent_channels": (4, 8),
+               "num_tokens": (2,), "in_channels": (2,), "gcae.num_layers": (4,), "transformer.num_layers": (1, 2, 3, 4)}
+MAX_FF_2, MAX_D_MODEL_2 = 512, 144
 KIND_PLAIN, KIND_PACKED = 0, 1
 
 
@@ -64,33 +78,97 @@ def block_strides(seq_len: int, num_tokens: int, n_blocks: int = N_BLOCKS) -> Li
     return s
 
 
+def compute_strides_2(seq_len: int, num_tokens: int, num_layers: int = N_BLOCKS) -> Tuple[List[int], int, bool]:
+    """the shopformer_2 tokenizer's stride rule -> (strides, final length, needs the adaptive pool).  ``seq_len // num_tokens`` is
+    divided by 2, 3, 4, 5, 6 in turn as often as each goes; what is left above 1 is one more factor.  The smallest ``num_layers``
+    factors become strides, largest first.  12 / 2 -> [3, 2, 1, 1], 24 / 2 -> [3, 2, 2, 1].  The final length is the floor
+    division chain; the pool is needed when it misses ``num_tokens``."""
+    strides = [1] * num_layers
+    remaining, factors = seq_len // num_tokens, []
+    for p in (2, 3, 4, 5, 6):
+        while remaining % p == 0 and remaining > 1:
+            factors.append(p)
+            remaining //= p
+    if remaining > 1:
+        factors.append(remaining)
+    for i, f in enumerate(sorted(factors)[:num_layers]):
+        strides[i] = f
+    strides.sort(reverse=True)
+    final = seq_len
+    for s in strides:
+        final //= s
+    return strides, final, final != num_tokens
+
+
+def is_variant_2(config) -> bool:
+    return isinstance(config, dict) and isinstance(config.get("model"), dict)
+
+
+def resolve_config_2(config: dict) -> dict:
+    """the nested ``shopformer_2`` config (``model``, ``model.gcae``, ``model.transformer``) -> a flat dict of ints with dotted keys;
+    whatever the kernel does not cover is refused with the field named, before any image is built"""
+    if not is_variant_2(config):
+        raise ValueError("a shopformer_2 config is a nested dict with a 'model' section")
+    m = config["model"]
+    g, tr = m.get("gcae") or {}, m.get("transformer") or {}
+    cfg = {}
+    for k in ("in_channels", "num_keypoints", "seq_len", "num_tokens"):
+        if k not in m:
+            raise ValueError(f"shopformer_2 config has no field 'model.{k}'")
+        cfg[k] = int(m[k])
+    for k in ("hidden_channels", "latent_channels"):
+        if k not in g:
+            raise ValueError(f"shopformer_2 config has no field 'model.gcae.{k}'")
+        cfg["gcae." + k] = int(g[k])
+    cfg["gcae.num_layers"] = int(g.get("num_layers", N_BLOCKS))
+    for k, d in DEFAULT_TRANSFORMER_2.items():
+        cfg["transformer." + k] = int(tr.get(k, d))
+    for field, allowed in SUPPORTED_2.items():
+        if cfg[field] not in allowed:
+            raise ValueError(f"shopformer_2 config field '{field}' = {cfg[field]} is not supported (supported: {list(allowed)})")
+    strides, final, pool = compute_strides_2(cfg["seq_len"], cfg["num_tokens"], cfg["gcae.num_layers"])
+    t = cfg["seq_len"]
+    for s in strides:
+        t = (t - 1) // s + 1                       # what the 9-tap convolutions (pad 4) really emit
+    if pool or t != cfg["num_tokens"] or max(strides) > 3:
+        raise ValueError(f"shopformer_2 config fields 'seq_len' = {cfg['seq_len']} / 'num_tokens' = {cfg['num_tokens']}: strides {strides} end at "
+                         f"{t} frames; the adaptive average pool and strides above 3 are not supported")
+    din, d, heads, ff = (cfg["transformer." + k] for k in ("input_dim", "d_model", "num_heads", "dim_feedforward"))
+    if din != cfg["gcae.latent_channels"] * cfg["num_keypoints"]:
+        raise ValueError(f"shopformer_2 config field 'transformer.input_dim' = {din} is not latent_channels * num_keypoints = "
+                         f"{cfg['gcae.latent_channels'] * cfg['num_keypoints']}")
+    if d < 4 or d % 4 or d > MAX_D_MODEL_2:
+        raise ValueError(f"shopformer_2 config field 'transformer.d_model' = {d} is not supported (a multiple of 4, at most {MAX_D_MODEL_2})")
+    if heads < 1 or d % heads:
+        raise ValueError(f"shopformer_2 config field 'transformer.num_heads' = {heads} does not divide d_model = {d}")
+    if ff < 4 or ff % 4 or ff > MAX_FF_2:
+        raise ValueError(f"shopformer_2 config field 'transformer.dim_feedforward' = {ff} is not supported (a multiple of 4, at most {MAX_FF_2})")
+    return cfg
+
+
 def _bn(sd, p):
     g = np.asarray(sd[p + ".weight"], np.float64) / np.sqrt(np.asarray(sd[p + ".running_var"], np.float64) + BN_EPS)
     return g, np.asarray(sd[p + ".bias"], np.float64) - np.asarray(sd[p + ".running_mean"], np.float64) * g
 
 
-def fold_state_dict(sd: Dict[str, np.ndarray], config: Optional[dict] = None, dtype=np.float32) -> Tuple[dict, Dict[str, np.ndarray]]:
-    """reference state dict -> (geometry, logical folded tensors, float32; ``dtype=np.float64`` keeps the unrounded fold, for tests).  Every BatchNorm disappears into the scale/shift of the
-    input or into the weights and bias of the conv in front of it (folded in float64, rounded once).  Matrices are [out, taps, in]."""
-    cfg = resolve_config(config)
-    sd = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)) for k, v in sd.items()}
-    V, T, H, L = cfg["num_keypoints"], cfg["seq_len"], cfg["hidden_channels"], cfg["latent_channels"]
-    D = L * V
-    strides = block_strides(T, cfg["num_tokens"])
-    tn = [T]
-    for s in strides:
-        tn.append((tn[-1] - 1) // s + 1)
-    chans = [2, H, H, H, L]
-    enc = "gcae.encoder."
+def _np_state(sd) -> Dict[str, np.ndarray]:
+    return {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)) for k, v in sd.items()}
 
+
+def _needer(sd, cfg):
     def need(key, shape):
         if key not in sd:
             raise ValueError(f"Shopformer checkpoint has no tensor '{key}' (config {cfg})")
         if tuple(sd[key].shape) != tuple(shape):
             raise ValueError(f"Shopformer checkpoint tensor '{key}' has shape {tuple(sd[key].shape)}, the config asks for {tuple(shape)}")
         return np.asarray(sd[key], np.float64)
+    return need
 
-    t: Dict[str, np.ndarray] = {}
+
+def _fold_tokenizer(sd, need, t: Dict[str, np.ndarray], V: int, H: int, L: int, strides: List[int]) -> int:
+    """bn_input and the four ST-GCN blocks (the same modules in both variants) into ``t``; -> the adjacency's longest row"""
+    chans = [2, H, H, H, L]
+    enc = "gcae.encoder."
     need(enc + "bn_input.weight", (2 * V,))
     g, b = _bn(sd, enc + "bn_input")
     t["in_scale"], t["in_shift"] = g, b
@@ -115,9 +193,32 @@ def fold_state_dict(sd: Dict[str, np.ndarray], config: Optional[dict] = None, dt
             g, b = _bn(sd, p + "residual.1")
             t[f"b{i}.rw"] = (need(p + "residual.0.weight", (co, ci, 1, 1))[:, :, 0, 0] * g[:, None]).reshape(co, 1, ci)
             t[f"b{i}.rb"] = need(p + "residual.0.bias", (co,)) * g + b
+    return nnz
+
+
+def fold_state_dict(sd: Dict[str, np.ndarray], config: Optional[dict] = None, dtype=np.float32, variant: Optional[int] = None) -> Tuple[dict, Dict[str, np.ndarray]]:
+    """reference state dict -> (geometry, logical folded tensors, float32; ``dtype=np.float64`` keeps the unrounded fold, for tests).  Every BatchNorm disappears into the scale/shift of the
+    input or into the weights and bias of the conv in front of it (folded in float64, rounded once).  Matrices are [out, taps, in].
+    ``variant``: 1 = ``shopformer/``, 2 = ``shopformer_2/``, None = 2 when the config is the nested dict with a ``model`` key."""
+    if variant not in (None, 1, 2):
+        raise ValueError(f"Shopformer variant must be 1 or 2, got {variant}")
+    if variant == 2 or (variant is None and is_variant_2(config)):
+        return fold_state_dict_2(sd, config, dtype)
+    cfg = resolve_config(config)
+    sd = _np_state(sd)
+    V, T, H, L = cfg["num_keypoints"], cfg["seq_len"], cfg["hidden_channels"], cfg["latent_channels"]
+    D = L * V
+    strides = block_strides(T, cfg["num_tokens"])
+    tn = [T]
+    for s in strides:
+        tn.append((tn[-1] - 1) // s + 1)
+    need = _needer(sd, cfg)
+    t: Dict[str, np.ndarray] = {}
+    nnz = _fold_tokenizer(sd, need, t, V, H, L, strides)
     ntok = tn[-1]
-    t["pe_in"] = need("transformer.pos_encoder.pe", sd["transformer.pos_encoder.pe"].shape)[0, :ntok, :D]
-    t["pe_score"] = need("pos_encoder.pe", sd["pos_encoder.pe"].shape)[0, :ntok, :D]
+    shape = lambda k: sd[k].shape if k in sd else ()
+    t["pe_in"] = need("transformer.pos_encoder.pe", shape("transformer.pos_encoder.pe"))[0, :ntok, :D]
+    t["pe_score"] = need("pos_encoder.pe", shape("pos_encoder.pe"))[0, :ntok, :D]
     if t["pe_in"].shape != (ntok, D) or t["pe_score"].shape != (ntok, D):
         raise ValueError(f"Shopformer checkpoint: positional encodings do not cover {ntok} tokens of {D} features")
 
@@ -153,6 +254,70 @@ def fold_state_dict(sd: Dict[str, np.ndarray], config: Optional[dict] = None, dt
     geo = {"V": V, "T": T, "H": H, "L": L, "heads": cfg["transformer_heads"], "layers": cfg["transformer_layers"], "ff": FF_DIM, "D": D,
            "ntok": ntok, "nnz": nnz, "s0": strides[0], "s1": strides[1], "s2": strides[2], "s3": strides[3],
            "T1": tn[1], "T2": tn[2], "T3": tn[3], "T4": tn[4]}
+    return geo, {k: np.ascontiguousarray(v, dtype) for k, v in t.items()}
+
+
+def fold_state_dict_2(sd, config: dict, dtype=np.float32) -> Tuple[dict, Dict[str, np.ndarray]]:
+    """the ``shopformer_2`` state dict (``gcae.*``, ``transformer.encoder.layers.N.*``, ``transformer.encoder.norm.*``, the decoder
+    alike, ``transformer.input_projection.*`` / ``output_projection.*`` when input_dim != d_model) -> (geometry, folded tensors).
+    Layer names in the image: e{N} / d{N} as in variant 1, ``en`` / ``dn`` the two final norms, ``inp`` / ``outp`` the projections."""
+    cfg = resolve_config_2(config)
+    sd = _np_state(sd)
+    V, T, H, L = cfg["num_keypoints"], cfg["seq_len"], cfg["gcae.hidden_channels"], cfg["gcae.latent_channels"]
+    Din, D, ff = cfg["transformer.input_dim"], cfg["transformer.d_model"], cfg["transformer.dim_feedforward"]
+    layers, ntok = cfg["transformer.num_layers"], cfg["num_tokens"]
+    strides, _, _ = compute_strides_2(T, ntok, N_BLOCKS)
+    tn = [T]
+    for s in strides:
+        tn.append((tn[-1] - 1) // s + 1)
+    need = _needer(sd, cfg)
+    t: Dict[str, np.ndarray] = {}
+    nnz = _fold_tokenizer(sd, need, t, V, H, L, strides)
+    if "transformer.pos_encoder.pe" not in sd:
+        raise ValueError(f"Shopformer checkpoint has no tensor 'transformer.pos_encoder.pe' (config {cfg})")
+    t["pe_in"] = np.asarray(sd["transformer.pos_encoder.pe"], np.float64)[0, :ntok, :D]
+    if t["pe_in"].shape != (ntok, D):
+        raise ValueError(f"Shopformer checkpoint: the positional encoding does not cover {ntok} tokens of {D} features")
+
+    def lin(dst, src, o, i):
+        t[dst + ".w"], t[dst + ".b"] = need(src + "weight", (o, i)).reshape(o, 1, i), need(src + "bias", (o,))
+
+    def attn(dst, src):
+        w, b = need(src + "in_proj_weight", (3 * D, D)), need(src + "in_proj_bias", (3 * D,))
+        t[dst + ".q.w"], t[dst + ".q.b"] = w[:D].reshape(D, 1, D), b[:D]
+        t[dst + ".kv.w"], t[dst + ".kv.b"] = w[D:].reshape(2 * D, 1, D), b[D:]
+        lin(dst + ".out", src + "out_proj.", D, D)
+
+    def norm(dst, src):
+        t[dst + ".g"], t[dst + ".b"] = need(src + "weight", (D,)), need(src + "bias", (D,))
+
+    proj = Din != D
+    if proj:
+        lin("inp", "transformer.input_projection.", D, Din)
+    for e in range(layers):
+        p = f"transformer.encoder.layers.{e}."
+        attn(f"e{e}.sa", p + "self_attn.")
+        norm(f"e{e}.n1", p + "norm1.")
+        lin(f"e{e}.f1", p + "linear1.", ff, D)
+        lin(f"e{e}.f2", p + "linear2.", D, ff)
+        norm(f"e{e}.n2", p + "norm2.")
+    norm("en", "transformer.encoder.norm.")
+    for e in range(layers):
+        p = f"transformer.decoder.layers.{e}."
+        attn(f"d{e}.sa", p + "self_attn.")
+        norm(f"d{e}.n1", p + "norm1.")
+        attn(f"d{e}.ca", p + "multihead_attn.")
+        norm(f"d{e}.n2", p + "norm2.")
+        lin(f"d{e}.f1", p + "linear1.", ff, D)
+        lin(f"d{e}.f2", p + "linear2.", D, ff)
+        norm(f"d{e}.n3", p + "norm3.")
+    norm("dn", "transformer.decoder.norm.")
+    if proj:
+        lin("outp", "transformer.output_projection.", Din, D)
+    geo = {"V": V, "T": T, "H": H, "L": L, "heads": cfg["transformer.num_heads"], "layers": layers, "ff": ff, "D": D,
+           "ntok": ntok, "nnz": nnz, "s0": strides[0], "s1": strides[1], "s2": strides[2], "s3": strides[3],
+           "T1": tn[1], "T2": tn[2], "T3": tn[3], "T4": tn[4],
+           "variant": 2, "Din": Din, "in_proj": int(proj), "out_proj": int(proj), "norm_kind": NORM_PRE, "act_kind": ACT_GELU_ERF}
     return geo, {k: np.ascontiguousarray(v, dtype) for k, v in t.items()}
 
 
@@ -194,7 +359,8 @@ def build_image(geo: dict, tensors: Dict[str, np.ndarray]) -> bytes:
         entries.append((name.encode(), kind, dims, off, len(flat)))
         data.append(flat)
         off += len(flat)
-    head = MAGIC + struct.pack("<II", IMAGE_VERSION, len(CFG_FIELDS)) + struct.pack(f"<{len(CFG_FIELDS)}i", *(geo[f] for f in CFG_FIELDS))
+    ver, fields = (IMAGE_VERSION_2, CFG_FIELDS_V2) if geo.get("variant", 1) == 2 else (IMAGE_VERSION, CFG_FIELDS)
+    head = MAGIC + struct.pack("<II", ver, len(fields)) + struct.pack(f"<{len(fields)}i", *(geo[f] for f in fields))
     head += struct.pack("<I", len(entries))
     for name, kind, dims, o, n in entries:
         head += struct.pack("<32sI3IQQ", name, kind, *dims, o, n)
@@ -207,10 +373,11 @@ def parse_image(blob: bytes) -> Tuple[dict, Dict[str, np.ndarray]]:
     if blob[:8] != MAGIC:
         raise ValueError("not a Shopformer weight image (bad magic)")
     ver, ncfg = struct.unpack_from("<II", blob, 8)
-    if ver != IMAGE_VERSION or ncfg != len(CFG_FIELDS):
+    fields = {IMAGE_VERSION: CFG_FIELDS, IMAGE_VERSION_2: CFG_FIELDS_V2}.get(ver)
+    if fields is None or ncfg != len(fields):
         raise ValueError(f"unsupported Shopformer weight image version {ver}")
     pos = 16
-    geo = dict(zip(CFG_FIELDS, struct.unpack_from(f"<{ncfg}i", blob, pos)))
+    geo = dict(zip(fields, struct.unpack_from(f"<{ncfg}i", blob, pos)))
     pos += 4 * ncfg
     (n,) = struct.unpack_from("<I", blob, pos)
     pos += 4
@@ -226,23 +393,69 @@ def parse_image(blob: bytes) -> Tuple[dict, Dict[str, np.ndarray]]:
         out[name] = unpack_mfma(flat, d0, d1, d2) if kind == KIND_PACKED else flat[:d0 * d1 * d2].reshape([d for d in (d0, d1, d2)]).squeeze()
         if kind == KIND_PLAIN and out[name].ndim == 0:
             out[name] = out[name].reshape(1)
-    for k in ("adj_col", "adj_val", "pe_in", "pe_score"):
+    for k in [k for k in ("adj_col", "adj_val", "pe_in", "pe_score") if k in out]:
         out[k] = out[k].reshape(geo["V"] if k.startswith("adj") else geo["ntok"], -1)
     for k in ("b0.gw", "b0.rw"):
         out[k] = out[k].reshape(geo["H"], 1, 2)
     return geo, out
 
 
-def image_from_state_dict(sd, config: Optional[dict] = None) -> bytes:
-    return build_image(*fold_state_dict(sd, config))
+def image_from_state_dict(sd, config: Optional[dict] = None, variant: Optional[int] = None) -> bytes:
+    return build_image(*fold_state_dict(sd, config, variant=variant))
+
+
+def load_config_file(path) -> Optional[dict]:
+    """a config path -> dict: ``.yaml`` / ``.yml`` through PyYAML (imported here, only when asked for), anything else as JSON"""
+    if not os.path.exists(path):
+        return None
+    with open(path) as f:
+        if str(path).lower().endswith((".yaml", ".yml")):
+            import yaml
+            return yaml.safe_load(f)
+        return json.load(f)
+
+
+def state_dict_from_checkpoint(ck: dict) -> dict:
+    """``model_state_dict``, the split ``gcae_state_dict`` + ``transformer_state_dict`` pair, or the bare state dict itself"""
+    if "model_state_dict" in ck:
+        return ck["model_state_dict"]
+    if "gcae_state_dict" in ck or "transformer_state_dict" in ck:
+        if not ("gcae_state_dict" in ck and "transformer_state_dict" in ck):
+            raise ValueError("Shopformer checkpoint: the split form needs both 'gcae_state_dict' and 'transformer_state_dict'")
+        sd = {"gcae." + k: v for k, v in ck["gcae_state_dict"].items()}
+        sd.update({"transformer." + k: v for k, v in ck["transformer_state_dict"].items()})
+        return sd
+    return ck
+
+
+def image_from_checkpoint(path: str, config=None, variant: Optional[int] = None) -> bytes:
+    import torch
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    if config is None and isinstance(ck, dict) and is_variant_2(ck.get("config")):
+        config = ck["config"]
+    if config is None:
+        config = os.path.join(os.path.dirname(os.path.abspath(path)), "config.json")
+    if isinstance(config, (str, os.PathLike)):
+        config = load_config_file(config)
+    return image_from_state_dict(state_dict_from_checkpoint(ck), config, variant=variant)
 
 
 # ---------------------------------------------------------------------------------------------- the model
 class ShopformerInfo(C.Structure):
     _fields_ = [("num_keypoints", C.c_int), ("seq_len", C.c_int), ("hidden_channels", C.c_int), ("latent_channels", C.c_int),
                 ("heads", C.c_int), ("layers", C.c_int), ("n_tokens", C.c_int), ("d_model", C.c_int), ("group", C.c_int),
-                ("lds_bytes", C.c_int), ("reserved", C.c_int * 2), ("n_params", C.c_longlong),
+                ("lds_bytes", C.c_int), ("variant", C.c_int), ("group_transformer", C.c_int), ("n_params", C.c_longlong),
                 ("macs_per_window", C.c_longlong), ("launches", C.c_longlong)]
+
+
+class ShopformerOutputs(C.Structure):
+    """mi355_shopformer_outputs_t: optional output pointers of the *_ex entry points (host or device, as the call takes them)"""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int), ("scores", C.c_void_p), ("token_scores", C.c_void_p),
+                ("tokens", C.c_void_p), ("recon", C.c_void_p)]
+
+
+def _outputs(scores=None, token_scores=None, tokens=None, recon=None) -> ShopformerOutputs:
+    return ShopformerOutputs(C.sizeof(ShopformerOutputs), 0, scores or None, token_scores or None, tokens or None, recon or None)
 
 
 class Shopformer:
@@ -258,6 +471,9 @@ class Shopformer:
         self.info = self._info()
         self.seq_len, self.num_keypoints = self.info.seq_len, self.info.num_keypoints
         self.n_tokens, self.d_model = self.info.n_tokens, self.info.d_model
+        self.variant = int(self.geometry.get("variant", 1))
+        self.token_dim = int(self.geometry.get("Din", self.d_model))        # width of tokens / reconstructed_tokens
+        self.neck = self.variant == 2 and self.num_keypoints == 18           # the shopformer_2 loader synthesises joint 17
 
     def _info(self) -> ShopformerInfo:
         info = ShopformerInfo()
@@ -270,24 +486,16 @@ class Shopformer:
         return int(self._info().launches)
 
     @classmethod
-    def from_state_dict(cls, sd, config: Optional[dict] = None, device: int = 0) -> "Shopformer":
-        return cls(image_from_state_dict(sd, config), device=device)
+    def from_state_dict(cls, sd, config: Optional[dict] = None, device: int = 0, variant: Optional[int] = None) -> "Shopformer":
+        return cls(image_from_state_dict(sd, config, variant=variant), device=device)
 
     @classmethod
-    def from_checkpoint(cls, path: str, config=None, device: int = 0) -> "Shopformer":
+    def from_checkpoint(cls, path: str, config=None, device: int = 0, variant: Optional[int] = None) -> "Shopformer":
         """``torch.save({'model_state_dict': ...})`` as the reference's train.py writes it; ``config``: a dict, a path, or None for the
-        ``config.json`` beside the checkpoint (absent: the reference's defaults), as its inference.py resolves it"""
-        import torch
-        if config is None:
-            config = os.path.join(os.path.dirname(os.path.abspath(path)), "config.json")
-        if isinstance(config, (str, os.PathLike)):
-            if os.path.exists(config):
-                with open(config) as f:
-                    config = json.load(f)
-            else:
-                config = None
-        ck = torch.load(path, map_location="cpu", weights_only=True)
-        return cls.from_state_dict(ck["model_state_dict"] if "model_state_dict" in ck else ck, config, device=device)
+        ``config.json`` beside the checkpoint (absent: the reference's defaults), as its inference.py resolves it.  A ``shopformer_2``
+        checkpoint carries its nested config under ``config`` (used when none is given); ``config`` may also be a YAML path; the split
+        ``gcae_state_dict`` / ``transformer_state_dict`` form is accepted as its evaluate.py accepts it."""
+        return cls(image_from_checkpoint(path, config, variant), device=device)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -305,27 +513,56 @@ class Shopformer:
         return w
 
     def forward(self, windows, outputs: bool = True) -> Dict[str, np.ndarray]:
+        """-> ``normality_score`` [N]; with ``outputs`` also ``tokens`` and ``reconstructed_tokens`` [N, n_tokens, token_dim] and, for
+        the shopformer_2 variant, ``token_scores`` [N, n_tokens]"""
         w = self._check(windows)
         n = len(w)
         score = np.empty(n, np.float32)
-        tok = np.empty((n, self.n_tokens, self.d_model), np.float32) if outputs else None
-        rec = np.empty((n, self.n_tokens, self.d_model), np.float32) if outputs else None
-        if n:
+        tok = np.empty((n, self.n_tokens, self.token_dim), np.float32) if outputs else None
+        rec = np.empty((n, self.n_tokens, self.token_dim), np.float32) if outputs else None
+        ts = np.empty((n, self.n_tokens), np.float32) if outputs and self.variant == 2 else None
+        if n and self.variant == 2:
+            o = _outputs(score.ctypes.data, ts.ctypes.data if ts is not None else None, tok.ctypes.data if outputs else None,
+                         rec.ctypes.data if outputs else None)
+            _lib.check(_lib.lib().mi355_shopformer_score_ex(self._h, w.ctypes.data, n, C.byref(o)))
+        elif n:
             _lib.check(_lib.lib().mi355_shopformer_score(self._h, w.ctypes.data, n, score.ctypes.data,
                                                          tok.ctypes.data if outputs else None, rec.ctypes.data if outputs else None))
         out = {"normality_score": score}
         if outputs:
             out["tokens"], out["reconstructed_tokens"] = tok, rec
+        if ts is not None:
+            out["token_scores"] = ts
         return out
 
-    def score(self, windows) -> np.ndarray:
-        return self.forward(windows, outputs=False)["normality_score"]
+    def score(self, windows, reduction: str = "mean") -> np.ndarray:
+        """``reduction='mean'`` -> [N]; ``'none'`` -> [N, n_tokens] (the shopformer_2 variant's per-token scores)"""
+        if reduction == "mean":
+            return self.forward(windows, outputs=False)["normality_score"]
+        if reduction != "none":
+            raise ValueError(f"Unknown reduction: {reduction}")
+        if self.variant != 2:
+            raise ValueError("reduction='none' exists only for the shopformer_2 variant: the shopformer/ network has no per-token score")
+        w = self._check(windows)
+        ts = np.empty((len(w), self.n_tokens), np.float32)
+        if len(w):
+            o = _outputs(token_scores=ts.ctypes.data)
+            _lib.check(_lib.lib().mi355_shopformer_score_ex(self._h, w.ctypes.data, len(w), C.byref(o)))
+        return ts
 
     def predict(self, windows, threshold: float = 0.5) -> np.ndarray:
         return (self.score(windows) > threshold).astype(np.int64)
 
-    def score_device_async(self, windows_dev: int, n: int, scores_dev: int, stream: int = 0, tokens_dev: int = 0, recon_dev: int = 0) -> None:
-        """device pointers in, device pointers out, one launch on the caller's stream (0 = the null stream); returns without waiting"""
+    def score_device_async(self, windows_dev: int, n: int, scores_dev: int, stream: int = 0, tokens_dev: int = 0, recon_dev: int = 0,
+                           token_scores_dev: int = 0) -> None:
+        """device pointers in, device pointers out, enqueued on the caller's stream (0 = the null stream); returns without waiting.
+        ``token_scores_dev`` ([n, n_tokens]) is an output of the shopformer_2 variant only."""
+        if token_scores_dev or self.variant == 2:
+            if self.variant != 2:
+                raise ValueError("token_scores exist only for the shopformer_2 variant")
+            o = _outputs(scores_dev, token_scores_dev, tokens_dev, recon_dev)
+            _lib.check(_lib.lib().mi355_shopformer_score_ex_device_async(self._h, windows_dev, int(n), C.byref(o), stream or None))
+            return
         _lib.check(_lib.lib().mi355_shopformer_score_device_async(self._h, windows_dev, int(n), scores_dev, tokens_dev or None,
                                                                   recon_dev or None, stream or None))
 
@@ -344,18 +581,41 @@ def _normalise(seq: np.ndarray) -> np.ndarray:
     return seq
 
 
-def _window_tensor(poses: List[np.ndarray], num_keypoints: int) -> np.ndarray:
+def _with_neck(k: np.ndarray) -> np.ndarray:
+    """(>= 0, 3) keypoints -> (18, 3): the 17 COCO joints (zero rows if fewer came) and joint 17, the midpoint of the shoulders
+    (joints 5 and 6); a shoulder whose x and y are both ~0 is missing: the neck is then the other shoulder, or zero without both"""
+    if k.shape[0] < 17:
+        k = np.vstack([k, np.zeros((17 - k.shape[0], k.shape[1]))])
+    ls, rs = k[5], k[6]
+    neck = (ls + rs) / 2.0
+    l0, r0 = np.allclose(ls[:2], 0), np.allclose(rs[:2], 0)
+    if l0 and r0:
+        neck = np.zeros_like(ls)
+    elif l0:
+        neck = rs.copy()
+    elif r0:
+        neck = ls.copy()
+    return np.vstack([k[:17], neck.reshape(1, -1)])
+
+
+def _window_tensor(poses: List[np.ndarray], num_keypoints: int, neck: bool = False) -> np.ndarray:
+    if neck:
+        poses = [_with_neck(np.asarray(k).reshape(-1, 3)) for k in poses]
     seq = np.array([np.asarray(k).reshape(-1, 3)[:num_keypoints, :2] for k in poses])       # (V, 3) or the flat (3 V,) form
     if seq.shape[1] < num_keypoints:
         seq = np.concatenate([seq, np.zeros((seq.shape[0], num_keypoints - seq.shape[1], 2), seq.dtype)], axis=1)
     return np.transpose(_normalise(seq).astype(np.float32), (2, 0, 1))
 
 
-def windows_from_poselift(data: dict, seq_len: int = 12, stride: int = 6, max_gap: int = 5, num_keypoints: int = 17):
+def windows_from_poselift(data: dict, seq_len: int = 12, stride: int = 6, max_gap: int = 5, num_keypoints: int = 17, neck: bool = False):
     """PoseLift dict ``{frame: {person: [bbox, kpts(V, 3)]}}`` -> (windows ``[n, 2, seq_len, V]`` float32, index) with
     ``index[i] = (person_id, first_frame, last_frame)``, in the order the reference's loader emits its samples: persons in order of
     first appearance, each person's frames sorted, a window every ``stride`` of that person's frames, dropped when two consecutive
-    frames of it lie more than ``max_gap`` apart; poses with NaN / inf are left out before windowing."""
+    frames of it lie more than ``max_gap`` apart; poses with NaN / inf are left out before windowing.  ``neck=True`` (with
+    ``num_keypoints=18``): joint 17 is the neck the ``shopformer_2`` loader synthesises from the shoulders, added before normalisation;
+    without it joints beyond those delivered are zero."""
+    if neck and num_keypoints != 18:
+        raise ValueError("neck=True needs num_keypoints=18 (17 COCO joints + the neck)")
     per: Dict[int, Dict[int, np.ndarray]] = {}
     for fnum, people in data.items():
         if not people or not isinstance(people, dict):
@@ -374,7 +634,7 @@ def windows_from_poselift(data: dict, seq_len: int = 12, stride: int = 6, max_ga
             win = idx[s:s + seq_len]
             if any(b - a > max_gap for a, b in zip(win, win[1:])):
                 continue
-            xs.append(_window_tensor([fr[f] for f in win], num_keypoints))
+            xs.append(_window_tensor([fr[f] for f in win], num_keypoints, neck))
             index.append((int(pid), int(win[0]), int(win[-1])))
     x = np.stack(xs) if xs else np.zeros((0, 2, seq_len, num_keypoints), np.float32)
     return x, index
@@ -382,7 +642,8 @@ def windows_from_poselift(data: dict, seq_len: int = 12, stride: int = 6, max_ga
 
 def score_poselift(model, data: dict, stride: int = 6, max_gap: int = 5):
     """-> (scores [n], index) for every window of every person of one video's PoseLift dict"""
-    x, index = windows_from_poselift(data, seq_len=model.seq_len, stride=stride, max_gap=max_gap, num_keypoints=model.num_keypoints)
+    x, index = windows_from_poselift(data, seq_len=model.seq_len, stride=stride, max_gap=max_gap, num_keypoints=model.num_keypoints,
+                                     neck=bool(getattr(model, "neck", False)))
     return model.score(x), index
 
 
@@ -397,6 +658,7 @@ class StreamScorer:
     def __init__(self, model, stride: int = 6, max_gap: int = 5):
         self.model, self.stride, self.max_gap = model, int(stride), int(max_gap)
         self.seq_len, self.num_keypoints = model.seq_len, model.num_keypoints
+        self.neck = bool(getattr(model, "neck", False))
         self._ring: Dict[int, list] = {}
         self._seen: Dict[int, int] = {}
 
@@ -417,7 +679,7 @@ class StreamScorer:
                 fr = [f for f, _ in ring]
                 if any(b - a > self.max_gap for a, b in zip(fr, fr[1:])):
                     continue
-                xs.append(_window_tensor([p for _, p in ring], self.num_keypoints))
+                xs.append(_window_tensor([p for _, p in ring], self.num_keypoints, self.neck))
                 done.append((pid, fr[0], fr[-1]))
         if not done:
             return []

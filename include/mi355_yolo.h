@@ -408,7 +408,8 @@ typedef struct {
     int num_keypoints, seq_len, hidden_channels, latent_channels, heads, layers, n_tokens, d_model;
     int group;              /* windows per workgroup */
     int lds_bytes;          /* LDS the plan of that group uses */
-    int reserved[2];
+    int variant;            /* 1 = shopformer/ (version-1 image), 2 = shopformer_2/ (version-2 image); was reserved */
+    int group_transformer;  /* windows per workgroup of the transformer phase (variant 1: = group); was reserved */
     long long n_params, macs_per_window;
     long long launches;     /* kernel launches this handle has enqueued so far: a counter incremented beside the launch itself */
 } mi355_shopformer_info_t;
@@ -418,6 +419,22 @@ int  mi355_shopformer_info(const mi355_shopformer* h, mi355_shopformer_info_t* i
 int  mi355_shopformer_score(mi355_shopformer* h, const float* windows, int n, float* scores, float* tokens, float* recon);
 int  mi355_shopformer_score_device_async(mi355_shopformer* h, const float* windows_dev, int n, float* scores_dev, float* tokens_dev,
                                          float* recon_dev, void* stream);
+/* Version-2 images hold the reference's shopformer_2/ network: pre-norm layers, erf GELU, two tokens per window,
+ * tokens and recon [n][n_tokens][latent_channels * num_keypoints].  The functions above take them too (two launches per call:
+ * tokenizer, then the transformer over groups of up to 16 windows).  The _ex forms add the per-token scores: every pointer of the
+ * struct is optional (at least one must be set; struct_size = sizeof), token_scores [n][n_tokens] exists for version-2 images only.
+ * Host pointers for mi355_shopformer_score_ex, device pointers for the device_async form; a device_async call without a tokens
+ * output keeps the tokens in a scratch buffer of the handle, grown (hipMalloc) by the first call with a larger n. */
+typedef struct {
+    int struct_size, reserved;
+    float* scores;          /* [n] */
+    float* token_scores;    /* [n][n_tokens] */
+    float* tokens;          /* [n][n_tokens][token width] */
+    float* recon;           /* [n][n_tokens][token width] */
+} mi355_shopformer_outputs_t;
+int  mi355_shopformer_score_ex(mi355_shopformer* h, const float* windows, int n, const mi355_shopformer_outputs_t* out);
+int  mi355_shopformer_score_ex_device_async(mi355_shopformer* h, const float* windows_dev, int n, const mi355_shopformer_outputs_t* out,
+                                            void* stream);
 
 #ifdef __cplusplus
 }
