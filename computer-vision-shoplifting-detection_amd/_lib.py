@@ -26,6 +26,7 @@ class Opts(C.Structure):
 # mi355_opts.flags (include/mi355_yolo.h)
 OPT_NO_FUSE_UPSAMPLE, OPT_NO_FUSE_1X1, OPT_NO_FUSE_TAIL, OPT_NO_GROUPS = 0x01, 0x02, 0x04, 0x08
 OPT_NO_MEM_REUSE, OPT_HIP_GRAPH, OPT_NO_DIRECT_ROWS, OPT_NO_PASS_TUNE = 0x10, 0x20, 0x40, 0x80
+OPT_NO_SPARSE_BOX = 0x100
 # launch-plan files shipped with the package: the tuned choices of the benchmarked workloads on MI355X (plans/README.md)
 PLAN_DIR = os.path.join(HERE, "plans")
 
@@ -78,6 +79,7 @@ SIGNATURES = {
                                     _P(C.c_longlong), C.c_int, _i32p, _P(C.c_longlong), _P(C.c_longlong)]),
     "mi355_yolo_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "mi355_yolo_last_timing": (C.c_int, [C.c_void_p, _P(Timing)]),
+    "mi355_yolo_sparse_stats": (C.c_int, [C.c_void_p, _P(C.c_longlong)]),
     "mi355_op_dwconv2d": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "mi355_op_psa_attention": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -88,6 +88,7 @@ struct ConvKArgs {
     FastDiv fd_tx, fd_ty, fd_gy;   // conv_igemm_f32: scalar division by tiles_x, tiles_y, gridDim.y
     int img_src, img_dst, img_res; // conv_igemm_f32: elements per image of the source / destination / residual slices' buffers (H * W * cs)
     int THin, st_rpi, st_nseg; float inv_row_slots;   // conv_igemm_f16 staging: halo rows, rows / row segments per 256-thread pass, 1 / (16-byte slots per halo row)
+    const int* gate;           // conv_igemm_f32 / conv_splitk_f32: when non-null the launch leaves at once unless *gate != 0 (dense fall-back of the sparse box branch)
 };
 // A planned launch: kernel instance, grid, LDS bytes and kernel arguments.  Planning (tile / wave-arrangement
 // search) is done once per (op, shape) by the engine; run_conv only enqueues.
@@ -191,9 +192,12 @@ struct DecodeArgs {
     int B, A, nc, nkpt, kdim;
     float* pred;        // [B][A][no] anchor-major decoded tensor (xywh, scores, kpts), no = 4+nc+nkpt*kdim
     float2* best;       // [B][A] (best score, best class as float)
+    const int* gate = nullptr;      // part 2 (box stage alone): runs only when *gate != 0
+    int* fallback_count = nullptr;  // part 2: counts the launches that did run (statistics of the sparse box branch)
 };
 // full = also store the nc class scores into pred (raw-head entry point); NMS itself only needs box/kpts/best
-const char* launch_decode(const DecodeArgs& a, bool full, hipStream_t st);
+// part: 0 = the whole row, 1 = score stage (best[], keypoints), 2 = box stage, gated
+const char* launch_decode(const DecodeArgs& a, bool full, hipStream_t st, int part = 0);
 // pred in Ultralytics layout [B][no][A] -> anchor-major [B][A][no] plus best[]; used by mi355_op_nms
 const char* launch_best_from_pred(const float* pred_anchor_major, int B, int A, int no, int nc, float2* best,
                                   hipStream_t st);
@@ -202,6 +206,27 @@ const char* launch_transpose_pred(const float* in, float* out, int B, int rows, 
 // The host then copies sum(counts) rows instead of n * max_det (35 MB -> ~3 MB per 512-frame step).
 const char* launch_compact_rows(const void* rows, const int* counts, int n, int max_det, int row_words, int* offsets, void* packed,
                                 hipStream_t st);
+
+// ---- sparse box branch, conv_f32_sparse.hip ---------------------------------------------------------------
+// One head level: cv2.i.0 (wA: the first 64 couts of the packed merged conv, Cin = 16 * cib) reads the neck map `src` and
+// writes `mid` (64 channels); cv2.i.1 (wB, 3x3 64 -> 64) and cv2.i.2 (wC, 1x1 64 -> 64 box logits) follow.  List entries are
+// pixel indices b * H * W + y * W + x of the chunk's map.
+struct SparseLevel {
+    const float* src; int src_cs, cib;
+    float* mid; int mid_cs;
+    const float* wA; const float* biasA; const float* wB; const float* biasB; const float* wC; const float* biasC;
+    int H, W, stride, anchor0;
+    int* dil; int* cand; int cap_dil, cap_cand;
+};
+struct SparseArgs {
+    SparseLevel lv[3]; int n_levels;
+    int B, A, no, act;
+    float* pred; const float2* best;
+    float conf; const unsigned* class_mask;
+    int* state;        // device ints: [0, 3) dilated counts, [4, 7) candidate counts, [8] = 1 when a list overflowed (dense fall-back runs)
+};
+const char* launch_sparse_lists(const SparseArgs& a, hipStream_t st);
+const char* launch_sparse_box(const SparseArgs& a, hipStream_t st);
 
 struct NmsArgs {
     const float* pred; const float2* best;     // as written by decode

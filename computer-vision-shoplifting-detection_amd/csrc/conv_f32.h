@@ -495,6 +495,7 @@ __device__ __forceinline__ void conv_igemm_f32_body(const KA& a_in, float* lds, 
 template <int KS, int STRIDE, int PT, int CT, int WP, bool F2 = false>
 __global__ __launch_bounds__(256, (PT * CT == 4 ? MI355_V1_MINWAVES : PT * CT == 8 ? MI355_V1_MINWAVES8 : PT * CT >= 15 ? MI355_V1_MINWAVES16 : 1)) void conv_igemm_f32(ConvKArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    if (a.gate && *a.gate == 0) return;                  // block-uniform: one scalar load and a branch
     conv_igemm_f32_body<KS, STRIDE, PT, CT, WP, F2>(a, lds, MI355_BLOCK_ID());
 }
 
@@ -654,6 +655,7 @@ __device__ __forceinline__ void conv_splitk_f32_body(const KA& a, float* lds, co
 template <int KS, int STRIDE, int PT, int CT>
 __global__ __launch_bounds__(256) void conv_splitk_f32(ConvKArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    if (a.gate && *a.gate == 0) return;
     conv_splitk_f32_body<KS, STRIDE, PT, CT>(a, lds, MI355_BLOCK_ID());
 }
 

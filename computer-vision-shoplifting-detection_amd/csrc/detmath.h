@@ -70,4 +70,33 @@ __device__ __forceinline__ float det_div_ge1(float v, float d) {
 __device__ __forceinline__ float det_silu(float v) { return det_div_ge1(v, 1.0f + det_expf_silu(-v)); }
 __device__ __forceinline__ float det_sigmoid(float v) { return 1.0f / (1.0f + det_expf(-v)); }
 
+// One DFL side (block.py:DFL over 16 bins): softmax of the 16 logits, then the expectation over 0..15, evaluated sequentially in
+// the canonical operation order.  Shared by the dense decode kernel and the epilogue of the sparse box branch, so that the two
+// cannot drift apart.  FP contraction is off inside, whatever the including file sets.
+__device__ __forceinline__ float det_dfl_side(float (&v)[16]) {
+#pragma clang fp contract(off)
+    float m = v[0];
+#pragma unroll
+    for (int j = 1; j < 16; ++j) m = fmaxf(m, v[j]);
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) { v[j] = det_expf(v[j] - m); sum += v[j]; }
+    float d = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) d += (v[j] / sum) * (float)j;
+    return d;
+}
+
+// utils/tal.py:dist2bbox(xywh=True) times the level's stride, from the four DFL distances (l, t, r, b) of the anchor at (ax, ay)
+__device__ __forceinline__ float4 det_dist2bbox(float d0, float d1, float d2, float d3, float ax, float ay, float st) {
+#pragma clang fp contract(off)
+    const float x1 = ax - d0, y1 = ay - d1, x2 = ax + d2, y2 = ay + d3;
+    float4 o;
+    o.x = ((x1 + x2) / 2.0f) * st;
+    o.y = ((y1 + y2) / 2.0f) * st;
+    o.z = (x2 - x1) * st;
+    o.w = (y2 - y1) * st;
+    return o;
+}
+
 }  // namespace mi355

@@ -111,6 +111,21 @@ int mi355_yolo_last_timing(const mi355_yolo* h, mi355_timing* t) {
     return MI355_OK;
 }
 
+int mi355_yolo_sparse_stats(mi355_yolo* h, long long* out10) {
+    if (!h || !out10) return fail(MI355_EINVAL, "null argument");
+    for (int i = 0; i < 10; ++i) out10[i] = 0;
+    out10[0] = h->sparse_shape ? 1 : -(long long)h->sparse_why; out10[1] = h->sp_passes;
+    if (!h->sp_state) return MI355_OK;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    int st[16];
+    HIPCHK(hipMemcpy(st, h->sp_state, sizeof(st), hipMemcpyDeviceToHost));
+    out10[2] = st[12];
+    for (int l = 0; l < 3; ++l) { out10[3 + l] = st[l]; out10[6 + l] = st[4 + l]; }
+    out10[9] = st[8];
+    return MI355_OK;
+}
+
 int mi355_yolo_raw_head(mi355_yolo* h, const uint8_t* bgr, int n, int height, int width, int row_stride, int imgsz,
                         float* out, int* out_channels, int* out_anchors) {
     if (!h || !out_channels || !out_anchors) return fail(MI355_EINVAL, "null argument");

@@ -194,6 +194,31 @@ struct mi355_yolo {
     std::vector<GroupLaunch> groups;
     std::vector<int> group_sel;
     int use_groups = 1, group_max_batch = 5;
+    // Sparse box branch (conv_f32_sparse.hip): the head's box chain cv2.i.0 -> cv2.i.1 -> cv2.i.2 -> DFL runs at the
+    // anchors that reach NMS only.  sp_m / sp_b1 / sp_b2[l] = the ops of level l (cv2.i.0 alone or merged with its siblings, cv2.i.1,
+    // cv2.i.2), found from the program when the weights are loaded (sp_levels = 0: the program has no such head).  sparse_shape:
+    // the current shape runs it (decided per shape like the other fusions; MI355_SPARSE_BOX=0/1 overrides the frames-per-pass
+    // threshold).  sp_cls = the merged conv without its box couts, sp_box = its box couts alone and sp_b1 = cv2.i.1 (+ fused
+    // cv2.i.2) as gated launches: they leave at once unless a position list overflowed its capacity in this chunk.
+    int sp_levels = 0, sp_m[3] = {-1, -1, -1}, sp_b1[3] = {-1, -1, -1}, sp_b2[3] = {-1, -1, -1};
+    std::vector<char> sp_skip, sp_late;       // per op: not launched in a sparse pass; per buffer: read by the sparse tail, after the last op of a pass
+    std::vector<char> late_read;              // sp_late for the shapes that may run the sparse tail (plan_memory), empty otherwise
+    bool sparse_shape = false; int sparse_why = 1;   // why the current shape keeps the dense head (prepare_sparse_shape), 0 = it does not
+    int sparse_min_batch = 32;          // frames per pass from which the sparse branch wins
+    float sparse_cap = 1.0f;            // share of a level's positions the lists hold; beyond it the dense launches run
+    ConvLaunch sp_cls[3], sp_box[3], sp_b1l[3]; bool sp_has_cls[3] = {false, false, false};
+    int* sp_state = nullptr;            // device: 12 ints of SparseArgs.state + [12] dense fall-backs so far
+    int* sp_lists = nullptr; size_t sp_lists_ints = 0;
+    int sp_cap[3] = {0, 0, 0}; size_t sp_off_dil[3] = {0, 0, 0}, sp_off_cand[3] = {0, 0, 0};   // list capacities / offsets into sp_lists of the current shape
+    float pass_conf = 0.25f; const unsigned* pass_cmask = nullptr;   // the call's candidate filter (infer_impl sets them before its chunks)
+    long long sp_passes = 0;
+    // Feedback from the data, outside the pass: every sparse chunk's counts are copied asynchronously to pinned
+    // memory (h_sp, 64 slots) and read after a synchronous call's own final stream synchronisation; when a list overflowed or a
+    // level's dilated share exceeded sparse_max_share (where the sparse kernels stop winning) the following calls with the same
+    // conf and class filter run the dense head, and every 64th of them probes the sparse one again.  Off under MI355_SPARSE_BOX=0/1
+    // (A/B runs want one path); asynchronous device-output calls neither update nor reset it.
+    int* h_sp = nullptr; long long h_sp_pos[64][3] = {}; int sp_slot = 0; float sp_last_conf = -1.f; unsigned long long sp_last_filter = 0;
+    bool sp_prefer_dense = false, sp_dense_now = false; int sp_dense_calls = 0; float sparse_max_share = 0.5f;
     float* pred = nullptr; float2* best = nullptr; unsigned long long* keys = nullptr;
     int A = 0, Apow2 = 0;
     uint8_t* lbox = nullptr;            // letterboxed frames of one chunk (also the stable stem input of the graph path)
@@ -255,6 +280,10 @@ struct DevMem {   // RAII for the one-shot operator entry points
 // engine_load.hip: .mi355w image -> op program, weights on the device, dependency DAG + stream assignment
 int parse_blob(mi355_yolo* h, const uint8_t* blob, size_t n);
 int create_impl(const uint8_t* blob, size_t nbytes, int device_id, const mi355_opts* opts, mi355_yolo** out);
+// engine_run.hip: the sparse box branch: program analysis (at load), per-shape launches, statistics
+void detect_sparse_head(mi355_yolo* h);
+bool sparse_wanted(const mi355_yolo* h, int nb);
+int prepare_sparse_shape(mi355_yolo* h, int nb, int Hl, int Wl);
 // engine_memory.hip: liveness-based placement of the activation buffers in ONE arena (host arithmetic only)
 void plan_memory(mi355_yolo* h, int nb, int Hl, int Wl, std::vector<size_t>* off_out, std::vector<size_t>* bytes_out,
                  size_t* arena_out, size_t* plain_out);

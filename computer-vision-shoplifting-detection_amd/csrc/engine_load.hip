@@ -27,6 +27,7 @@ mi355_yolo::~mi355_yolo() {
     for (auto& c : dconv) { if (c.wpk) (void)hipFree(c.wpk); if (c.bias) (void)hipFree(c.bias); if (c.w_raw) (void)hipFree(c.w_raw); if (c.w_frag) (void)hipFree(c.w_frag); }
     if (lut) (void)hipFree(lut);
     if (zeros) (void)hipFree(zeros);
+    if (sp_state) (void)hipFree(sp_state); if (sp_lists) (void)hipFree(sp_lists); if (h_sp) (void)hipHostFree(h_sp);
     if (d_in) (void)hipFree(d_in);
     if (d_rows) (void)hipFree(d_rows); if (d_counts) (void)hipFree(d_counts);
     if (d_packed) (void)hipFree(d_packed); if (d_offsets) (void)hipFree(d_offsets);
@@ -254,6 +255,7 @@ int parse_blob(mi355_yolo* h, const uint8_t* blob, size_t n) {
     if (const char* e = getenv("MI355_GROUPS")) h->use_groups = atoi(e);
     if (const char* e = getenv("MI355_MEM_REUSE")) h->mem_reuse = atoi(e);
     if (const char* e = getenv("MI355_GROUP_MAX_BATCH")) h->group_max_batch = atoi(e);
+    detect_sparse_head(h);
     return build_schedule(h);
 }
 
@@ -360,6 +362,9 @@ int create_impl(const uint8_t* blob, size_t nbytes, int device_id, const mi355_o
     // A/B overrides (tools/*.sh): never needed to configure the product
     if (const char* e = getenv("MI355_AUTOTUNE")) h->autotune = std::max(0, atoi(e));
     if (const char* e = getenv("MI355_GRAPH")) h->use_graph = atoi(e);
+    if (const char* e = getenv("MI355_SPARSE_MIN_BATCH")) h->sparse_min_batch = atoi(e);
+    if (const char* e = getenv("MI355_SPARSE_MAX_SHARE")) h->sparse_max_share = (float)atof(e);
+    if (const char* e = getenv("MI355_SPARSE_CAP")) h->sparse_cap = std::min(1.0f, std::max(0.001f, (float)atof(e)));
     if (const char* e = getenv("MI355_FAST_ACT")) h->fast_act = atoi(e) != 0 && !h->half;
     if (const char* e = getenv("MI355_PLAN_DIR")) h->plan_dir = e;
     if (const char* e = getenv("MI355_PLAN_CACHE")) { h->plan_cache_on = std::strcmp(e, "0") != 0 && *e; if (h->plan_cache_on) h->plan_cache_dir = e; }

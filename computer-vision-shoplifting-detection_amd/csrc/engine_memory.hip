@@ -7,6 +7,8 @@ namespace mi355 {
 void plan_memory(mi355_yolo* h, int nb, int Hl, int Wl, std::vector<size_t>* off_out, std::vector<size_t>* bytes_out,
                         size_t* arena_out, size_t* plain_out) {
     const size_t nbufs = h->bufs.size();
+    // only a shape that may run the sparse box tail pays for it (a host-only plan follows the same rule as the engine)
+    if (sparse_wanted(h, nb)) h->late_read = h->sp_late; else h->late_read.clear();
     h->dbuf_cs.assign(nbufs, 0); h->dbuf_es.assign(nbufs, 4);
     std::vector<size_t> bytes(nbufs, 0);
     std::vector<char> pinned(nbufs, 0);
@@ -46,6 +48,7 @@ void plan_memory(mi355_yolo* h, int nb, int Hl, int Wl, std::vector<size_t>* off
     auto is_anc = [&](int a, int of) { return (h->anc[of][a >> 6] >> (a & 63)) & 1ull; };
     auto may_share = [&](size_t a, size_t b) {          // may b (written later) take a's bytes?
         if (pinned[a] || pinned[b] || writers[b].empty() || users[a].empty()) return false;
+        if (!h->late_read.empty() && h->late_read[a]) return false;     // the sparse box branch reads a behind the last op of the pass
         for (int w : writers[b])
             for (int u : users[a]) if (!is_anc(u, w)) return false;
         return true;

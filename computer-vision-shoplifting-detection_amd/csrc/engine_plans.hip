@@ -114,6 +114,7 @@ int ensure_shape(mi355_yolo* h, int nb, int Hl, int Wl) {
         h->alloc_nb = nb; h->cur_H = Hl; h->cur_W = Wl;
     }
     // ---- launch plans for nb frames per pass on the existing buffers ----
+    h->sparse_shape = false;            // (the stopwatch below times the dense head; prepare_sparse_shape decides at the end)
     h->cur_nb = 0;                      // a rebuild that fails half-way is retried by the next call instead of running stale plans
     for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.second);      // captured launches embed the old plans
     h->graphs.clear();
@@ -365,7 +366,8 @@ int ensure_shape(mi355_yolo* h, int nb, int Hl, int Wl) {
     // ---- grouped launches of the single-stream regime: list-schedule the launched ops into steps, then decide per step ----
     h->groups.clear(); h->steps.clear();
     h->group_sel.assign(n_ops, -1);
-    const bool stepwise = h->use_groups && !h->half && nb <= h->group_max_batch && nb < h->streams_min_batch;
+    // (a shape that runs the sparse box branch keeps its ops out of grouped launches: two of them are not launched as planned)
+    const bool stepwise = h->use_groups && !h->half && nb <= h->group_max_batch && nb < h->streams_min_batch && !sparse_wanted(h, nb);
     auto launched = [&](int i) { return !(h->ops[i].type == OP_UPSAMPLE && h->fused_away[i]) && !h->skip_op[i]; };
     auto list_of = [&](int i) -> const std::vector<ConvLaunch>& {      // the candidate list op i's current plan was taken from
         return (h->fuse2[i] >= 0 && h->skip_op[h->fuse2[i]]) ? cands_f[i] : chosen[i] >= kUpBase ? cands_u[i] : cands[i];
@@ -597,18 +599,22 @@ int ensure_shape(mi355_yolo* h, int nb, int Hl, int Wl) {
         if (h->plan_source == 3) save_plan_choices(h, nb, Hl, Wl, n_cands, fp, chosen, gsel);
     }
     h->cur_nb = nb;
+    { const int rc = prepare_sparse_shape(h, nb, Hl, Wl); if (rc) return rc; }
     h->plan_hash = fnv1a(fnv1a(fp, chosen.data(), chosen.size() * sizeof(int)), h->group_sel.data(), h->group_sel.size() * sizeof(int));   // candidates + choices: identifies the launch sequence
     h->plan_launches = 0;
     if (!h->steps.empty()) {
         for (const auto& st : h->steps) h->plan_launches += (int)st.singles.size() + (st.group >= 0);
     } else {
-        for (size_t i = 0; i < h->ops.size(); ++i) h->plan_launches += launched((int)i);
+        for (size_t i = 0; i < h->ops.size(); ++i) h->plan_launches += launched((int)i) && !(h->sparse_shape && h->sp_skip[i]);
     }
+    // the sparse tail's conv launches (plan_launches counts stem .. last conv): 2 gated dense convs per level, stages A and B
+    if (h->sparse_shape) h->plan_launches += 2 + 2 * h->sp_levels;
     if (getenv("MI355_SCHED_LOG")) {      // launch order of a pass for tools/layer_report.py: position, op index, stream, launched
         for (size_t pos = 0; pos < h->sched_order.size(); ++pos) {
             const int idx = h->sched_order[pos];
-            fprintf(stderr, "[sched] %zu %d %d %d\n", pos, idx, h->op_stream[idx], !(h->ops[idx].type == OP_UPSAMPLE && h->fused_away[idx]) && !h->skip_op[idx]);
+            fprintf(stderr, "[sched] %zu %d %d %d\n", pos, idx, h->op_stream[idx], !(h->ops[idx].type == OP_UPSAMPLE && h->fused_away[idx]) && !h->skip_op[idx] && !(h->sparse_shape && h->sp_skip[idx]));
         }
+        fprintf(stderr, "[sparse] %d %d\n", h->sparse_shape ? 1 : 0, h->sp_levels);
     }
     return MI355_OK;
 }

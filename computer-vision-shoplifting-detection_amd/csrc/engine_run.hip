@@ -4,6 +4,113 @@
 
 namespace mi355 {
 
+// ---- sparse box branch: which ops form the box chain of every head level (program structure, decided at load time) ----
+void detect_sparse_head(mi355_yolo* h) {
+    h->sp_levels = 0;
+    h->sp_skip.assign(h->ops.size(), 0); h->sp_late.assign(h->bufs.size(), 0);
+    if (h->half || (h->opt_flags & MI355_OPT_NO_SPARSE_BOX) || h->levels.empty() || h->levels.size() > 3 || h->hdr.reg_max != 16) return;
+    const int n = (int)h->ops.size();
+    auto conv_op = [&](int i, int k) { const FileOp& o = h->ops[i]; return o.type == OP_CONV && (int)h->convs[o.conv].k == k && h->convs[o.conv].s == 1 && o.res_buf < 0; };
+    int m[3], b1[3], b2[3];
+    for (size_t l = 0; l < h->levels.size(); ++l) {
+        const FileLevel& lv = h->levels[l];
+        m[l] = b1[l] = b2[l] = -1;
+        for (int i = 0; i < n; ++i)
+            if (conv_op(i, 1) && h->ops[i].dst_buf == (int)lv.buf && h->ops[i].dst_choff == (int)lv.box_off && h->ops[i].dst_c == 64 && h->ops[i].src_c == 64 && h->ops[i].act == 0) b2[l] = i;
+        if (b2[l] < 0) return;
+        const FileOp& o2 = h->ops[b2[l]];
+        for (int i = 0; i < n; ++i)
+            if (conv_op(i, 3) && h->ops[i].dst_buf == o2.src_buf && h->ops[i].dst_choff == o2.src_choff && h->ops[i].dst_c == 64 && h->ops[i].src_c == 64 && h->convs[h->ops[i].conv].pad == 1) b1[l] = i;
+        if (b1[l] < 0) return;
+        const FileOp& o1 = h->ops[b1[l]];
+        for (int i = 0; i < n; ++i)
+            if (conv_op(i, 3) && h->ops[i].dst_buf == o1.src_buf && h->ops[i].dst_choff == o1.src_choff && h->ops[i].dst_c >= 64 &&
+                (h->ops[i].src_c % 16) == 0 && h->convs[h->ops[i].conv].pad == 1 && h->ops[i].act == o1.act) m[l] = i;
+        if (m[l] < 0) return;
+        // nobody but cv2.i.1 reads the box slice of cv2.i.0's output, nobody but cv2.i.2 reads cv2.i.1's
+        for (int j = 0; j < n; ++j) {
+            const FileOp& o = h->ops[j];
+            if (o.type == OP_STEM) continue;
+            auto touches = [&](int buf, int off, int c) { return (o.src_buf == buf && o.src_choff < off + c && off < o.src_choff + o.src_c) ||
+                                                                 (o.res_buf == buf && o.res_choff < off + c && off < o.res_choff + o.dst_c); };
+            if (j != b1[l] && touches(o1.src_buf, o1.src_choff, 64)) return;
+            if (j != b2[l] && touches(o2.src_buf, o2.src_choff, 64)) return;
+        }
+    }
+    h->sp_levels = (int)h->levels.size();
+    for (int l = 0; l < h->sp_levels; ++l) {
+        h->sp_m[l] = m[l]; h->sp_b1[l] = b1[l]; h->sp_b2[l] = b2[l];
+        h->sp_skip[b1[l]] = h->sp_skip[b2[l]] = 1;
+        if (h->ops[m[l]].dst_c == 64) h->sp_skip[m[l]] = 1;          // an unmerged cv2.i.0 is box work as a whole
+        h->sp_late[h->ops[m[l]].src_buf] = 1; h->sp_late[h->ops[m[l]].dst_buf] = 1;
+    }
+}
+
+bool sparse_wanted(const mi355_yolo* h, int nb) {
+    if (h->sp_levels <= 0 || h->half || h->use_graph) return false;
+    if (const char* e = getenv("MI355_SPARSE_BOX")) return atoi(e) != 0;
+    return nb >= h->sparse_min_batch;
+}
+
+// a planned 3x3 launch over the cout tiles [t0, t0 + nt) of its conv: offsets into the packed weights, the bias and the
+// destination slice, and a grid over fewer cout groups -- the op program, the weight file and the plan files stay as they are
+static ConvLaunch cout_subrange(const ConvLaunch& l0, int t0, int nt) {
+    ConvLaunch l = l0;
+    l.a.wpk += (size_t)t0 * 9 * l.a.cib * 256; l.a.bias += t0 * 16; l.a.dst += t0 * 16;
+    l.a.Cout = std::min(nt * 16, l0.a.Cout - t0 * 16); l.a.n_ctiles = nt;
+    const int per = l.CT * (l.version == 6 ? 1 : 4 / l.WP);
+    l.a.cgroups = std::max(1, std::min(l0.a.cgroups, (nt + per - 1) / per));
+    l.grid_y = (unsigned)((nt + per * l.a.cgroups - 1) / (per * l.a.cgroups));
+    l.a.fd_gy = make_fastdiv(std::max(1u, l.grid_y));
+    l.flops = l0.flops * nt / std::max(1, l0.a.n_ctiles);
+    return l;
+}
+
+int prepare_sparse_shape(mi355_yolo* h, int nb, int Hl, int Wl) {
+    h->sparse_shape = false;
+    // sparse_why (plan_info): 0 runs, 1 the program has no such head / half / switched off, 2 below the frames-per-pass threshold
+    // (or MI355_SPARSE_BOX=0, hipGraph), 3 the shape's tuned plan of cv2.i.1 is not the fused 3x3 + 1x1 launch, 4 the plan of
+    // cv2.i.0 is not one of the gated 3x3 kernels (v1 / v6)
+    h->sparse_why = h->sp_levels <= 0 || h->half ? 1 : 2;
+    if (!sparse_wanted(h, nb)) return MI355_OK;
+    for (int l = 0; l < h->sp_levels; ++l) {
+        const int m = h->sp_m[l], b1 = h->sp_b1[l], b2 = h->sp_b2[l];
+        const ConvLaunch& pm = h->plans[m]; const ConvLaunch& p1 = h->plans[b1];
+        // the dense fall-back must be launches of the gated kernels: cv2.i.1 with cv2.i.2 fused behind it, plain 3x3 kernels
+        if (h->fuse2[b1] != b2 || !h->skip_op[b2] || !p1.a.w2 || p1.version != 1) { h->sparse_why = 3; return MI355_OK; }
+        if ((pm.version != 1 && pm.version != 6) || pm.a.w2 || pm.a.res || h->skip_op[m]) { h->sparse_why = 4; return MI355_OK; }
+    }
+    if (!h->sp_state) {
+        HIPCHK(hipMalloc(&h->sp_state, 16 * sizeof(int)));
+        HIPCHK(hipMemset(h->sp_state, 0, 16 * sizeof(int)));
+    }
+    size_t ints = 0;
+    for (int l = 0; l < h->sp_levels; ++l) {
+        const FileLevel& lv = h->levels[l];
+        const long long pos = (long long)nb * (Hl / lv.stride) * (Wl / lv.stride);
+        h->sp_cap[l] = (int)std::min<long long>(pos, std::max<long long>(64, (long long)std::ceil((double)h->sparse_cap * (double)pos)));
+        h->sp_off_dil[l] = ints; ints += (size_t)h->sp_cap[l];
+        h->sp_off_cand[l] = ints; ints += (size_t)h->sp_cap[l];
+    }
+    if (ints > h->sp_lists_ints) {
+        if (h->sp_lists) (void)hipFree(h->sp_lists);
+        h->sp_lists = nullptr; h->sp_lists_ints = 0;
+        HIPCHK(hipMalloc(&h->sp_lists, ints * sizeof(int))); h->sp_lists_ints = ints;
+    }
+    for (int l = 0; l < h->sp_levels; ++l) {
+        const int m = h->sp_m[l];
+        const int nt = h->plans[m].a.n_ctiles;
+        h->sp_has_cls[l] = nt > 4;
+        if (nt > 4) { h->sp_cls[l] = cout_subrange(h->plans[m], 4, nt - 4); h->sp_box[l] = cout_subrange(h->plans[m], 0, 4); }
+        else h->sp_box[l] = h->plans[m];
+        h->sp_box[l].a.gate = h->sp_state + 8;
+        h->sp_b1l[l] = h->plans[h->sp_b1[l]];
+        h->sp_b1l[l].a.gate = h->sp_state + 8;
+    }
+    h->sparse_shape = true; h->sparse_why = 0;
+    return MI355_OK;
+}
+
 // run the net (+decode) on nb frames that sit in `frames_dev` (original size h0 x w0, dense).
 // Launch-bound regime: the stem..decode sequence (60-100 launches) is captured once per chunk size into a hipGraph
 // and replayed; the frames are first copied into the engine's own staging buffer so the captured pointers stay valid.
@@ -44,8 +151,14 @@ int run_chunk(mi355_yolo* h, Prof& pf, const uint8_t* frames_dev, int nb, const 
 }
 
 int launch_net(mi355_yolo* h, Prof& pf, const uint8_t* stem_in, int nb, const Geometry& g, bool full_pred) {
+    // sparse box branch: the box chain's ops are not launched here (cv2.i.0 merged with its siblings runs without its box couts)
+    const bool sparse = h->sparse_shape && !full_pred && !h->sp_dense_now;
+    auto sparse_level_of = [&](size_t i) { for (int l = 0; l < h->sp_levels; ++l) if (h->sp_m[l] == (int)i) return l; return -1; };
+    // a 3x3 launch planned for cur_nb frames on a tail chunk of nb: same buffers, fewer tiles (one block per tile in the v1 / v6 kernels)
+    auto tail3 = [&](ConvLaunch l) { if (nb != h->cur_nb) { l.a.n_tiles_total = (int)((long)nb * l.a.tiles_x * l.a.tiles_y); l.grid_x = (unsigned)l.a.n_tiles_total; } return l; };
     auto launch_op = [&](size_t i, hipStream_t st) -> int {
         const FileOp& o = h->ops[i];
+        if (sparse && h->sp_skip[i]) return MI355_OK;
         const int sd_out = h->bufs[o.dst_buf].stride_div;
         float* dst = h->view(o.dst_buf, o.dst_choff);
         if (o.type == OP_STEM) {
@@ -61,7 +174,8 @@ int launch_net(mi355_yolo* h, Prof& pf, const uint8_t* stem_in, int nb, const Ge
             pf.end();
         } else if (o.type == OP_CONV) {
             if (h->skip_op[i]) return MI355_OK;         // a pointwise conv that runs inside its producer's launch
-            ConvLaunch l = h->plans[i];
+            const int spl = sparse ? sparse_level_of(i) : -1;
+            ConvLaunch l = spl >= 0 ? h->sp_cls[spl] : h->plans[i];
             if (nb != h->cur_nb) {             // tail chunk: same buffers, fewer frames
                 if (h->convs[o.conv].k == 1 && l.version == 3) {
                     const int sd_in = h->bufs[o.src_buf].stride_div;
@@ -161,7 +275,7 @@ int launch_net(mi355_yolo* h, Prof& pf, const uint8_t* stem_in, int nb, const Ge
                 HIPCHK(hipStreamWaitEvent(st, h->op_done[dep], 0));
             }
             const int rc = launch_op((size_t)idx, st); if (rc) return rc;
-            if (h->skip_op[idx]) continue;              // its event was recorded behind the producer's (fused) launch
+            if (h->skip_op[idx] || (sparse && h->sp_skip[idx])) continue;              // its event was recorded behind the producer's (fused) launch
             if (h->op_signals[idx] && !(h->ops[idx].type == OP_UPSAMPLE && h->fused_away[idx])) HIPCHK(hipEventRecord(h->op_done[idx], st));
             if (h->fuse2[idx] >= 0 && h->skip_op[h->fuse2[idx]] && h->op_signals[h->fuse2[idx]])
                 HIPCHK(hipEventRecord(h->op_done[h->fuse2[idx]], st));
@@ -180,9 +294,60 @@ int launch_net(mi355_yolo* h, Prof& pf, const uint8_t* stem_in, int nb, const Ge
     }
     d.B = nb; d.A = h->A; d.nc = h->hdr.nc; d.nkpt = h->hdr.nkpt; d.kdim = h->hdr.kdim;
     d.pred = h->pred; d.best = h->best;
+    if (!sparse) {
+        if (pf.begin(K_DECODE)) return fail(MI355_EHIP, "event");
+        KCHK(launch_decode(d, full_pred, h->stream));
+        pf.end();
+        return MI355_OK;
+    }
+    // ---- sparse tail: score stage -> position lists -> (gated dense box branch) -> box branch at the listed positions.
+    // Everything is enqueued; which of the two forms does the work is decided on the device (SparseArgs.state[8]).
+    SparseArgs sa{};
+    sa.n_levels = h->sp_levels; sa.B = nb; sa.A = h->A; sa.no = h->no(); sa.pred = h->pred; sa.best = h->best;
+    sa.conf = h->pass_conf; sa.class_mask = h->pass_cmask; sa.state = h->sp_state;
+    for (int l = 0; l < h->sp_levels; ++l) {
+        const FileOp& om = h->ops[h->sp_m[l]]; const FileOp& o1 = h->ops[h->sp_b1[l]]; const FileOp& o2 = h->ops[h->sp_b2[l]];
+        SparseLevel& L = sa.lv[l];
+        L.src = h->view(om.src_buf, om.src_choff); L.src_cs = h->dbuf_cs[om.src_buf]; L.cib = om.src_c / 16;
+        L.mid = h->view(om.dst_buf, om.dst_choff); L.mid_cs = h->dbuf_cs[om.dst_buf];
+        L.wA = h->dconv[om.conv].wpk; L.biasA = h->dconv[om.conv].bias;
+        L.wB = h->dconv[o1.conv].wpk; L.biasB = h->dconv[o1.conv].bias;
+        L.wC = h->dconv[o2.conv].wpk; L.biasC = h->dconv[o2.conv].bias;
+        L.H = d.lv[l].H; L.W = d.lv[l].W; L.stride = d.lv[l].stride; L.anchor0 = d.lv[l].anchor0;
+        // the cap is a share of THIS chunk's positions: a tail chunk uses the head of the full chunk's lists
+        const long long pos = (long long)nb * L.H * L.W;
+        const int cap_nb = (int)std::min<long long>(pos, std::max<long long>(64, (long long)std::ceil((double)h->sparse_cap * (double)pos)));
+        L.dil = h->sp_lists + h->sp_off_dil[l]; L.cand = h->sp_lists + h->sp_off_cand[l]; L.cap_dil = L.cap_cand = std::min(h->sp_cap[l], cap_nb);
+        sa.act = h->plans[h->sp_b1[l]].a.act;
+    }
     if (pf.begin(K_DECODE)) return fail(MI355_EHIP, "event");
-    KCHK(launch_decode(d, full_pred, h->stream));
+    KCHK(launch_decode(d, false, h->stream, 1));
+    HIPCHK(hipMemsetAsync(h->sp_state, 0, 12 * sizeof(int), h->stream));
+    KCHK(launch_sparse_lists(sa, h->stream));
     pf.end();
+    for (int l = 0; l < h->sp_levels; ++l) {
+        if (pf.begin(K_CONV)) return fail(MI355_EHIP, "event");
+        KCHK(run_conv(tail3(h->sp_box[l]), h->stream));
+        pf.end();
+        if (pf.begin(K_CONV)) return fail(MI355_EHIP, "event");
+        KCHK(run_conv(tail3(h->sp_b1l[l]), h->stream));
+        pf.end();
+    }
+    d.gate = h->sp_state + 8; d.fallback_count = h->sp_state + 12;
+    if (pf.begin(K_DECODE)) return fail(MI355_EHIP, "event");
+    KCHK(launch_decode(d, false, h->stream, 2));
+    pf.end();
+    if (pf.begin(K_CONV)) return fail(MI355_EHIP, "event");
+    KCHK(launch_sparse_box(sa, h->stream));
+    pf.end();
+    // this chunk's counts travel to pinned host memory behind the kernels (no wait here): infer_impl judges them after the call's
+    // own final synchronisation
+    if (h->h_sp) {
+        const int slot = h->sp_slot++ % 64;
+        HIPCHK(hipMemcpyAsync(h->h_sp + 12 * slot, h->sp_state, 12 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        for (int l = 0; l < 3; ++l) h->h_sp_pos[slot][l] = l < h->sp_levels ? (long long)nb * sa.lv[l].H * sa.lv[l].W : 0;
+    }
+    ++h->sp_passes;
     return MI355_OK;
 }
 
@@ -336,6 +501,28 @@ int infer_impl(mi355_yolo* h, const uint8_t* src, bool src_on_device, int n, int
         HIPCHK(hipHostGetDevicePointer((void**)&host_rows_dev, h->h_rows, 0));
         HIPCHK(hipHostGetDevicePointer((void**)&host_counts_dev, h->h_counts, 0));
     }
+    h->pass_conf = conf; h->pass_cmask = cmask;       // the sparse box branch filters its positions as nms_collect will
+    // Call-to-call feedback: where the previous synchronous call's data did not favour the sparse kernels the dense
+    // head runs, and every 64th such call probes the sparse one again; a call with another conf or class filter starts afresh.
+    const bool sp_adaptive = h->sparse_shape && !getenv("MI355_SPARSE_BOX");
+    unsigned long long filt = 1469598103934665603ull;
+    for (int i = 0; i < n_classes; ++i) filt = (filt ^ (unsigned)classes[i]) * 1099511628211ull;
+    if (conf != h->sp_last_conf || filt != h->sp_last_filter) { h->sp_prefer_dense = false; h->sp_dense_calls = 0; }
+    h->sp_last_conf = conf; h->sp_last_filter = filt;
+    h->sp_dense_now = sp_adaptive && h->sp_prefer_dense && (++h->sp_dense_calls % 64) != 0;
+    if (sp_adaptive && !h->h_sp) HIPCHK(hipHostMalloc(&h->h_sp, 64 * 12 * sizeof(int)));
+    h->sp_slot = 0;
+    auto sparse_feedback = [&]() -> int {             // behind the call's final synchronisation: nothing of it is inside a pass
+        if (!sp_adaptive || h->sp_dense_now || !h->h_sp) return MI355_OK;
+        bool over = false;
+        for (int c = 0; c < std::min(h->sp_slot, 64); ++c) {          // every chunk of the call (the last 64 of a longer one)
+            const int* st = h->h_sp + 12 * c;
+            over |= st[8] != 0;
+            for (int l = 0; l < h->sp_levels; ++l) over |= (double)st[l] > (double)h->sparse_max_share * (double)h->h_sp_pos[c][l];
+        }
+        h->sp_prefer_dense = over; h->sp_dense_calls = 0;
+        return MI355_OK;
+    };
     Prof pf{h};
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     for (int s = 0, ci = 0; s < n; s += nb, ++ci) {
@@ -397,6 +584,7 @@ int infer_impl(mi355_yolo* h, const uint8_t* src, bool src_on_device, int n, int
             out_counts[i] = c;
             std::memcpy(out_rows + (size_t)i * cap, h->h_rows + (size_t)i * max_det, (size_t)c * sizeof(mi355_det));
         }
+        rc = sparse_feedback(); if (rc) return rc;
         return collect_timing(h, pf, n);
     }
     // rows -> host: compact on the GPU first (a frame keeps counts[i] of its max_det slots; copying the slots would be 35 MB
@@ -422,6 +610,7 @@ int infer_impl(mi355_yolo* h, const uint8_t* src, bool src_on_device, int n, int
         std::memcpy(out_rows + (size_t)i * cap, h->h_rows + at, (size_t)c * sizeof(mi355_det));
         at += (size_t)h->h_counts[i];
     }
+    rc = sparse_feedback(); if (rc) return rc;
     return collect_timing(h, pf, n);
 }
 

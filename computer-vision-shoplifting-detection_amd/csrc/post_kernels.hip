@@ -25,8 +25,14 @@ namespace mi355 {
 // maximum and the (score, first argmax) pair are combined with wave shuffles.  (Round 1's LDS-staged one-lane-per-anchor
 // kernels staged 336 bytes per anchor and so ran at 1.5 waves per SIMD: 0.78 vs 0.36 ms per 256 frames; removed.)  A DFL
 // side is evaluated sequentially by one lane in the canonical operation order.
-template <bool FULL>
+// PART: 0 = the whole row; 1 = the score stage alone (classes -> best[], keypoints: what the candidate filter needs, no box);
+// 2 = the box alone, and only when *a.gate != 0 (the dense fall-back of the sparse box branch: engine_run.hip).
+template <bool FULL, int PART = 0>
 __global__ __launch_bounds__(256) void decode_kernel_quad(DecodeArgs a) {
+    if (PART == 2) {
+        if (*a.gate == 0) return;
+        if (blockIdx.x == 0 && threadIdx.x == 0 && a.fallback_count) atomicAdd(a.fallback_count, 1);
+    }
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)a.B * a.A;
     const long ag0 = gid >> 2;
@@ -48,35 +54,22 @@ __global__ __launch_bounds__(256) void decode_kernel_quad(DecodeArgs a) {
     const int lane = threadIdx.x & 63, qbase = lane & ~3;
 
     // ---- box: side s
-    float d;
-    {
+    if (PART != 1) {
         float v[16];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float4 q4 = *(const float4*)(src + lv.box_off + 16 * s + 4 * j);
             v[4 * j] = q4.x; v[4 * j + 1] = q4.y; v[4 * j + 2] = q4.z; v[4 * j + 3] = q4.w;
         }
-        float m = v[0];
-#pragma unroll
-        for (int j = 1; j < 16; ++j) m = fmaxf(m, v[j]);
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) { v[j] = det_expf(v[j] - m); sum += v[j]; }
-        d = 0.f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) d += (v[j] / sum) * (float)j;
+        const float d = det_dfl_side(v);
+        const float d0 = __shfl(d, qbase), d1 = __shfl(d, qbase + 1), d2 = __shfl(d, qbase + 2), d3 = __shfl(d, qbase + 3);
+        if (live && s == 0) {
+            const float4 o = det_dist2bbox(d0, d1, d2, d3, ax, ay, st);
+            if ((no & 3) == 0) *(float4*)out = o;
+            else { out[0] = o.x; out[1] = o.y; out[2] = o.z; out[3] = o.w; }
+        }
     }
-    const float d0 = __shfl(d, qbase), d1 = __shfl(d, qbase + 1), d2 = __shfl(d, qbase + 2), d3 = __shfl(d, qbase + 3);
-    if (live && s == 0) {
-        const float x1 = ax - d0, y1 = ay - d1, x2 = ax + d2, y2 = ay + d3;
-        float4 o;
-        o.x = ((x1 + x2) / 2.0f) * st;
-        o.y = ((y1 + y2) / 2.0f) * st;
-        o.z = (x2 - x1) * st;
-        o.w = (y2 - y1) * st;
-        if ((no & 3) == 0) *(float4*)out = o;
-        else { out[0] = o.x; out[1] = o.y; out[2] = o.z; out[3] = o.w; }
-    }
+    if (PART == 2) return;
     // ---- classes: lane s owns classes c = s, s + 4, s + 8, ... (or whole float4 groups, below)
     {
         const float* cl = src + lv.cls_off;
@@ -155,12 +148,15 @@ __global__ __launch_bounds__(256) void decode_kernel_quad(DecodeArgs a) {
     }
 }
 
-const char* launch_decode(const DecodeArgs& a, bool full, hipStream_t st) {
+const char* launch_decode(const DecodeArgs& a, bool full, hipStream_t st, int part) {
     for (int l = 0; l < a.n_levels; ++l)
         if ((a.lv[l].cs & 3) || (a.lv[l].box_off & 3)) return "decode: box logits must be 16-byte aligned";
+    if (part == 2 && !a.gate) return "decode: the gated box stage needs its gate";
     const long lanes = (long)a.B * a.A * 4;
     const dim3 g((unsigned)((lanes + 255) / 256));
-    if (full) hipLaunchKernelGGL(decode_kernel_quad<true>, g, dim3(256), 0, st, a);
+    if (part == 1)      hipLaunchKernelGGL((decode_kernel_quad<false, 1>), g, dim3(256), 0, st, a);
+    else if (part == 2) hipLaunchKernelGGL((decode_kernel_quad<false, 2>), g, dim3(256), 0, st, a);
+    else if (full) hipLaunchKernelGGL(decode_kernel_quad<true>, g, dim3(256), 0, st, a);
     else      hipLaunchKernelGGL(decode_kernel_quad<false>, g, dim3(256), 0, st, a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? nullptr : hipGetErrorString(e);

@@ -416,6 +416,16 @@ class YOLO:
         return {"plan_hash": f"{hsh.value:016x}", "plan_source": ("static", "memory", "cache", "tuned", "file")[src.value] if 0 <= src.value <= 4 else str(src.value),
                 "launches_per_pass": nl.value, "activation_bytes": ab.value, "activation_bytes_unshared": au.value}
 
+    def sparse_stats(self) -> dict:
+        """The sparse box branch of the shape last run: whether it is on, passes that enqueued it, passes in which a position list
+        overflowed (the dense box branch did the work), and the last pass's dilated / candidate positions per head level."""
+        v = (C.c_longlong * 10)()
+        _lib.check(_lib.lib().mi355_yolo_sparse_stats(getattr(self, "_last_handle", self._h), v))
+        why = ("", "no such head, half or switched off", "below the frames-per-pass threshold", "plan of cv2.i.1 is not the fused 3x3 + 1x1 launch",
+               "plan of cv2.i.0 is not a gated 3x3 kernel")
+        return {"enabled": v[0] == 1, "dense_because": "" if v[0] == 1 else why[min(4, max(1, -int(v[0])))], "passes": int(v[1]), "dense_fallbacks": int(v[2]), "dilated": [int(v[3]), int(v[4]), int(v[5])],
+                "candidates": [int(v[6]), int(v[7]), int(v[8])], "last_overflow": bool(v[9])}
+
     def set_profiling(self, on: bool = True) -> None:
         _lib.check(_lib.lib().mi355_yolo_set_profiling(self._h, int(on)))
         if self._h_other.value:

@@ -55,6 +55,7 @@ typedef struct mi355_yolo mi355_yolo;   /* opaque engine handle */
 #define MI355_OPT_HIP_GRAPH         0x20   /* replay stem..decode of a chunk as a hipGraph (measured slower on ROCm 7.2; off) */
 #define MI355_OPT_NO_DIRECT_ROWS    0x40   /* small calls: copy rows to the host instead of writing them from the NMS kernel */
 #define MI355_OPT_NO_PASS_TUNE      0x80   /* autotuner: skip the whole-pass re-check of fusion / group decisions */
+#define MI355_OPT_NO_SPARSE_BOX     0x100  /* fp32: always compute the head's box branch at every anchor (never at the NMS candidates only) */
 typedef struct mi355_opts {
     int struct_size;
     int batch_chunk;      /* frames pushed through the net per pass (default 64); larger batches are looped */
@@ -196,6 +197,11 @@ int  mi355_memory_plan(const void* blob, size_t nbytes, int n, int height, int w
 /* Per-kernel-kind timing costs two HIP events per launch; off by default (total_ms is always measured). */
 int  mi355_yolo_set_profiling(mi355_yolo* h, int on);
 int  mi355_yolo_last_timing(const mi355_yolo* h, mi355_timing* t);
+/* Statistics of the sparse box branch (waits for the engine's stream): out[0] = 1 when the current shape runs it (else minus the reason: 1 no such head / half / switched off, 2 below the
+ * frames-per-pass threshold or hipGraph, 3 / 4 the shape's tuned plan of cv2.i.1 / cv2.i.0 is not a kernel the gated dense fall-back exists for), out[1] = passes that
+ * enqueued it so far, out[2] = those in which a position list overflowed and the dense box branch ran instead, out[3..5] / out[6..8] =
+ * dilated / candidate positions per head level in the last pass, out[9] = that pass's overflow flag. */
+int  mi355_yolo_sparse_stats(mi355_yolo* h, long long* out10);
 
 /* ---- single-operator entry points (host pointers; used by the parity tests to isolate a kernel) -------- */
 

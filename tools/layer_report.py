@@ -19,6 +19,19 @@ rows = [r for r in csv.DictReader(open(path)) if "mi355" in r["Kernel_Name"]]
 rows.sort(key=lambda r: int(r["Dispatch_Id"]))              # host enqueue order (kernels of different streams overlap in time)
 kind = {OP_STEM: "stem", OP_CONV: "conv", OP_UPSAMPLE: "upsample2x", OP_SPPF_POOL: "sppf_pools"}
 tail = ["decode_kernel"]          # ... followed by the NMS launches (nms_sort + nms_greedy, or the multi-launch sort of big maps), folded into one row
+tail_label = ["decode_kernel"]
+# A shape that runs the sparse box branch ("[sparse] 1 <levels>" in the engine log): the box chain's ops are
+# not launched ("[sched]" marks them 0) and the tail is score stage, position lists, per level the two gated dense launches (they leave
+# at once unless a list overflowed), the gated box decode, and the two sparse stages.
+sparse_levels = 0
+if len(sys.argv) > 6 and os.path.exists(sys.argv[6]):
+    for l in open(sys.argv[6]):
+        if l.startswith("[sparse] "): sparse_levels = int(l.split()[2]) if l.split()[1] == "1" else 0
+if sparse_levels:
+    tail = ["decode_kernel", "sparse_lists"] + ["conv"] * (2 * sparse_levels) + ["decode_kernel", "sparse_conv_a", "sparse_conv_b"]
+    tail_label = ["score stage (decode part 1)", "sparse_lists"]
+    for lv in range(sparse_levels): tail_label += [f"cv2.{lv}.0 box couts (gated dense)", f"cv2.{lv}.1+cv2.{lv}.2 (gated dense)"]
+    tail_label += ["box decode (gated dense)", "sparse stage A: cv2.i.0 at dilated positions", "sparse stage B: cv2.i.1+cv2.i.2+DFL at candidates"]
 orders = [list(range(len(prog.ops)))]                       # program order (profiling passes) ...
 launched = {i: True for i in range(len(prog.ops))}
 if sched_log and os.path.exists(sched_log):
@@ -106,7 +119,7 @@ while i < len(rows):
     else:
         i += 1
 prog_l = [k for k in range(len(prog.ops)) if launched[k]]
-seq = [kind[prog.ops[k].type] for k in prog_l] + tail + ["nms"]
+seq = [kind[prog.ops[k].type] for k in prog_l] + tail_label + ["nms"]
 passes = [p for p in passes if len(p) == len(seq)]
 print(f"{len(passes)} passes of {len(seq)} launches matched ({model}, chunk {chunk})")
 tot = 0.0
@@ -120,9 +133,12 @@ for j, name in enumerate(seq):
     if j < len(prog_l) and prog.ops[prog_l[j]].type in (OP_CONV, OP_STEM):
         op = prog.ops[prog_l[j]]; c = prog.convs[op.conv]
         hw = (size // c.stride_div) ** 2
-        fl = 2.0 * c.cout * c.cin * c.k * c.k * hw * chunk
-        by = es * chunk * (c.cin * hw * c.s * c.s + c.cout * hw)
-        print(f"{c.name[:40]:40s} {tmpl:24s} {f'{c.cin}->{c.cout} k{c.k}s{c.s} @{size//c.stride_div}':30s} "
+        cout = c.cout
+        if sparse_levels and "+" in c.name and ".cv2." in c.name:      # merged sibling conv of a head level: launched without its 64 box couts
+            cout -= 64
+        fl = 2.0 * cout * c.cin * c.k * c.k * hw * chunk
+        by = es * chunk * (c.cin * hw * c.s * c.s + cout * hw)
+        print(f"{(c.name + (' [class couts only]' if cout != c.cout else ''))[:40]:40s} {tmpl:24s} {f'{c.cin}->{c.cout} k{c.k}s{c.s} @{size//c.stride_div}':30s} "
               f"{r['Grid_Size_X'] + 'x' + r['Grid_Size_Y']:>12s} {r['LDS_Block_Size']:>6s} {int(r['VGPR_Count'])+int(r['Accum_VGPR_Count']):>5d} {us:8.1f} {fl / us / 1e6:8.2f} {by / us / 1e3:7.0f}")
     else:
         print(f"{name:40s} {'':24s} {'':30s} {r['Grid_Size_X'] + 'x' + r['Grid_Size_Y']:>12s} {r['LDS_Block_Size']:>6s} {int(r['VGPR_Count'])+int(r['Accum_VGPR_Count']):>5d} {us:8.1f}")
@@ -135,7 +151,7 @@ for p in passes:
     for r in p:
         kn = r["Kernel_Name"].replace("(anonymous namespace)::", ""); kn = kn[:kn.find("(")] if "(" in kn else kn
         agg[kn][0] += 1; agg[kn][1] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-is_conv = lambda k: "conv_igemm" in k or "conv1x1_" in k or "conv_splitk" in k or "conv3x3_lw" in k
+is_conv = lambda k: "conv_igemm" in k or "conv1x1_" in k or "conv_splitk" in k or "conv3x3_lw" in k or "sparse_conv" in k
 conv_calls = sum(v[0] for k, v in agg.items() if is_conv(k)); conv_us = sum(v[1] for k, v in agg.items() if is_conv(k))
 all_us = sum(v[1] for v in agg.values())
 print(f"\nkernel summary over {len(passes)} real passes:")
