@@ -138,6 +138,13 @@ SIGNATURES = {
     "mi355_gmc_batch_seq": (C.c_ulonglong, [C.c_void_p]),
     "mi355_gmc_track_reset": (C.c_int, [C.c_void_p]),
     "mi355_gmc_track_state": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mi355_gmc_multi_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mi355_gmc_multi_destroy": (None, [C.c_void_p]),
+    "mi355_gmc_multi_begin": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _i32p, C.c_int]),
+    "mi355_gmc_multi_finish": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi355_gmc_multi_frames": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi355_gmc_multi_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "mi355_gmc_multi_state": (C.c_int, [C.c_void_p, C.c_int, _i32p, _i32p, _i32p, C.c_void_p, C.c_void_p, C.c_int]),
     "mi355_op_stem": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                 C.c_int, C.c_int, C.c_void_p]),
     "mi355_op_stem_f16": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,

@@ -37,10 +37,8 @@ __device__ __forceinline__ int reflect101(int i, int n) {          // BORDER_REF
 
 // cv2.pyrDown on uint8: separable [1 4 6 4 1] / 16 twice, reflect-101 borders, every second pixel, (s + 128) >> 8
 // blockIdx.y = frame of a batch (mi355_gmc_track_batch): planes of consecutive frames are `fstride` bytes apart (0 for one frame)
-__global__ __launch_bounds__(256) void pyr_down_kernel(const uint8_t* src, int h, int w, uint8_t* dst, int nh, int nw, size_t fstride = 0) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= nh * nw) return;
-    src += blockIdx.y * fstride; dst += blockIdx.y * fstride;
+// one output pixel of pyrDown (shared by the single-frame / batch kernel and the per-camera one below: one statement of the arithmetic)
+__device__ __forceinline__ uint8_t pyr_down_px(const uint8_t* src, int h, int w, int nw, int idx) {
     const int y = idx / nw, x = idx - y * nw;
     const int k[5] = {1, 4, 6, 4, 1};
     int s = 0;
@@ -52,7 +50,13 @@ __global__ __launch_bounds__(256) void pyr_down_kernel(const uint8_t* src, int h
         for (int j = 0; j < 5; ++j) r += k[j] * row[reflect101(2 * x + j - 2, w)];
         s += k[i] * r;
     }
-    dst[idx] = (uint8_t)((s + 128) >> 8);
+    return (uint8_t)((s + 128) >> 8);
+}
+__global__ __launch_bounds__(256) void pyr_down_kernel(const uint8_t* src, int h, int w, uint8_t* dst, int nh, int nw, size_t fstride = 0) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= nh * nw) return;
+    src += blockIdx.y * fstride; dst += blockIdx.y * fstride;
+    dst[idx] = pyr_down_px(src, h, w, nw, idx);
 }
 
 struct LkArgs {
@@ -64,6 +68,11 @@ struct LkArgs {
     // batch of frame pairs (blockIdx.y = pair; mi355_gmc_track_batch): pair p tracks n_arr[p] points from plane p into plane p + 1, the
     // planes of consecutive frames `pair_stride` bytes apart, its points / results at p * max_pts.  One pair: all zero / null.
     size_t pair_stride; int max_pts; const int* n_arr;
+    // the view lk_point reads its frame pair through (the per-camera kernel has another: LkCamView)
+    __device__ __forceinline__ const uint8_t* prev_at(int l) const { return prev[l]; }
+    __device__ __forceinline__ const uint8_t* cur_at(int l) const { return cur[l]; }
+    __device__ __forceinline__ int h_at(int l) const { return h[l]; }
+    __device__ __forceinline__ int w_at(int l) const { return w[l]; }
 };
 
 // Sum over the 64 lanes, the same bits in every lane.  Four row_shr steps inside each row of 16 lanes (data-parallel-primitive moves:
@@ -216,22 +225,9 @@ __device__ __forceinline__ void setup_patches(const uint8_t* img, int h, int w, 
 #define MI355_LK_WAVES 4
 #endif
 constexpr int kLkWaves = MI355_LK_WAVES;
-__global__ __launch_bounds__(64 * kLkWaves) void lk_kernel(LkArgs a) {
-    __shared__ uint8_t region[kLkWaves][(kRegMax * kRegMax + 15) & ~15];
-    __shared__ LkScratch scratch[kLkWaves];
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * kLkWaves + (threadIdx.x >> 6);
-    const int pair = blockIdx.y;
-    if (i >= (a.n_arr ? a.n_arr[pair] : a.n)) return;
-    {
-        const size_t po = (size_t)pair * a.pair_stride;
-#pragma unroll
-        for (int l = 0; l < kMaxLevels; ++l) { a.prev[l] += po; a.cur[l] += po; }
-        const size_t qo = (size_t)pair * (size_t)a.max_pts;
-        a.pts += 2 * qo; a.next += 2 * qo; a.status += qo;
-    }
-    uint8_t* reg = region[threadIdx.x >> 6];
-    LkScratch& sc = scratch[threadIdx.x >> 6];
+// point i of the frame pair `a` describes, on this wavefront (reg / sc: its LDS)
+template <class A>
+__device__ __forceinline__ void lk_point(const A& a, int i, int lane, uint8_t* reg, LkScratch& sc) {
     const int win = a.win, half = win / 2, W2 = win * win;
     const int per = (W2 + 63) / 64;
     const int R = win + 1 + 2 * kMargin;
@@ -248,7 +244,7 @@ __global__ __launch_bounds__(64 * kLkWaves) void lk_kernel(LkArgs a) {
         koff[j] = (j < per && k < W2) ? r * R + c : -1;
     }
     for (int l = a.top; l >= 0; --l) {
-        const int h = a.h[l], w = a.w[l];
+        const int h = a.h_at(l), w = a.w_at(l);
         const double px = p0x / (double)(1 << l), py = p0y / (double)(1 << l);
         if (l == a.top) { nx = px; ny = py; } else { nx *= 2.0; ny *= 2.0; }
         const double tlx = floor(px - half), tly = floor(py - half);
@@ -257,11 +253,11 @@ __global__ __launch_bounds__(64 * kLkWaves) void lk_kernel(LkArgs a) {
         const double cx = fmin(fmax(px, (double)-half), (double)(w - 1 + half));
         const double cy = fmin(fmax(py, (double)-half), (double)(h - 1 + half));
 #if MI355_LK_GLOBAL_SETUP
-        patch<0>(a.prev[l], h, w, cx, cy, win, lane, I, per);
-        patch<1>(a.prev[l], h, w, cx, cy, win, lane, Ix, per);
-        patch<2>(a.prev[l], h, w, cx, cy, win, lane, Iy, per);
+        patch<0>(a.prev_at(l), h, w, cx, cy, win, lane, I, per);
+        patch<1>(a.prev_at(l), h, w, cx, cy, win, lane, Ix, per);
+        patch<2>(a.prev_at(l), h, w, cx, cy, win, lane, Iy, per);
 #else
-        setup_patches(a.prev[l], h, w, cx, cy, win, lane, sc.box, sc.pI, sc.pIx, sc.pIy, I, Ix, Iy, per);
+        setup_patches(a.prev_at(l), h, w, cx, cy, win, lane, sc.box, sc.pI, sc.pIx, sc.pIy, I, Ix, Iy, per);
 #endif
         double a11 = 0, a12 = 0, a22 = 0;
 #pragma unroll
@@ -289,7 +285,7 @@ __global__ __launch_bounds__(64 * kLkWaves) void lk_kernel(LkArgs a) {
             if (!have_region || ix < rx || iy < ry || ix > rx + 2 * kMargin || iy > ry + 2 * kMargin) {
                 __builtin_amdgcn_wave_barrier();                   // every lane is done reading the old region
                 rx = ix - kMargin; ry = iy - kMargin;
-                fill_region(a.cur[l], h, w, ry, rx, R, lane, reg);
+                fill_region(a.cur_at(l), h, w, ry, rx, R, lane, reg);
                 have_region = true;
             }
             const uint8_t* r0 = reg + (iy - ry) * R + (ix - rx);
@@ -321,6 +317,23 @@ __global__ __launch_bounds__(64 * kLkWaves) void lk_kernel(LkArgs a) {
     }
 }
 
+__global__ __launch_bounds__(64 * kLkWaves) void lk_kernel(LkArgs a) {
+    __shared__ uint8_t region[kLkWaves][(kRegMax * kRegMax + 15) & ~15];
+    __shared__ LkScratch scratch[kLkWaves];
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kLkWaves + (threadIdx.x >> 6);
+    const int pair = blockIdx.y;
+    if (i >= (a.n_arr ? a.n_arr[pair] : a.n)) return;
+    {
+        const size_t po = (size_t)pair * a.pair_stride;
+#pragma unroll
+        for (int l = 0; l < kMaxLevels; ++l) { a.prev[l] += po; a.cur[l] += po; }
+        const size_t qo = (size_t)pair * (size_t)a.max_pts;
+        a.pts += 2 * qo; a.next += 2 * qo; a.status += qo;
+    }
+    lk_point(a, i, lane, region[threadIdx.x >> 6], scratch[threadIdx.x >> 6]);
+}
+
 // ---- frame preparation: cvtColor(BGR2GRAY) + resize(INTER_LINEAR) + the corner map of goodFeaturesToTrack -------------------
 // gmc.py states these in numpy (bgr_to_gray, resize_linear, good_features_to_track); the kernels evaluate the same expressions
 // in the same order (integers for luma and resize; float64 for the structure tensor, its sums taken in numpy's order), so the
@@ -328,17 +341,15 @@ __global__ __launch_bounds__(64 * kLkWaves) void lk_kernel(LkArgs a) {
 
 // gray = (1868 B + 9617 G + 4899 R + 8192) >> 14, then INTER_LINEAR with 11-bit coefficients (tables from the host: source index,
 // two taps per output column / row), both passes in cv2's fixed point: ((c0 * (h0 >> 4)) >> 16) + ((c1 * (h1 >> 4)) >> 16) + 2) >> 2
-__global__ __launch_bounds__(256) void gray_resize_kernel(const uint8_t* bgr, int H, int W, const int* xtab, const int* ytab, uint8_t* out, int oh, int ow,
-                                                          int resize, size_t in_fstride = 0, size_t out_fstride = 0) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= oh * ow) return;
-    bgr += blockIdx.y * in_fstride; out += blockIdx.y * out_fstride;
+// (one output pixel per thread; the *_px functions are shared with the per-camera kernels further down)
+__device__ __forceinline__ uint8_t gray_resize_px(const uint8_t* bgr, int H, int W, size_t row_stride, const int* xtab, const int* ytab, int ow, int resize,
+                                                  int idx) {
     const int y = idx / ow, x = idx - y * ow;
     auto gray = [&](int yy, int xx) {
-        const uint8_t* p = bgr + ((size_t)yy * W + xx) * 3;
+        const uint8_t* p = bgr + (size_t)yy * row_stride + (size_t)xx * 3;
         return (int)((p[0] * 1868 + p[1] * 9617 + p[2] * 4899 + 8192) >> 14);
     };
-    if (!resize) { out[idx] = (uint8_t)gray(y, x); return; }
+    if (!resize) return (uint8_t)gray(y, x);
     const int xi = xtab[3 * x], xa0 = xtab[3 * x + 1], xa1 = xtab[3 * x + 2];
     const int yi = ytab[3 * y], yb0 = ytab[3 * y + 1], yb1 = ytab[3 * y + 2];
     const int xj = min(xi + 1, W - 1), yj = min(yi + 1, H - 1);
@@ -346,34 +357,37 @@ __global__ __launch_bounds__(256) void gray_resize_kernel(const uint8_t* bgr, in
     const int h1 = gray(yj, xi) * xa0 + gray(yj, xj) * xa1;
     int v = (((yb0 * (h0 >> 4)) >> 16) + ((yb1 * (h1 >> 4)) >> 16) + 2) >> 2;
     v = v < 0 ? 0 : (v > 255 ? 255 : v);
-    out[idx] = (uint8_t)v;
+    return (uint8_t)v;
+}
+__global__ __launch_bounds__(256) void gray_resize_kernel(const uint8_t* bgr, int H, int W, const int* xtab, const int* ytab, uint8_t* out, int oh, int ow,
+                                                          int resize, size_t in_fstride = 0, size_t out_fstride = 0) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= oh * ow) return;
+    bgr += blockIdx.y * in_fstride; out += blockIdx.y * out_fstride;
+    out[idx] = gray_resize_px(bgr, H, W, (size_t)W * 3, xtab, ytab, ow, resize, idx);
 }
 
 // cornerMinEigenVal (3x3 Sobel scaled by 1 / (4 * block * 255), block x block box sums of the products, smaller eigenvalue) as
 // float32, and its maximum over the plane (non-negative floats order like their bit patterns)
-__global__ __launch_bounds__(256) void min_eig_kernel(const uint8_t* g, int h, int w, float* eig, unsigned* max_bits, size_t g_fstride = 0) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    g += blockIdx.y * g_fstride; eig += (size_t)blockIdx.y * h * w; max_bits += blockIdx.y;
-    float e = 0.f;
-    if (idx < h * w) {
-        const int y = idx / w, x = idx - y * w;
-        const double sc = 1.0 / (4.0 * 3.0 * 255.0);
-        auto G = [&](int yy, int xx) { return (double)g[(size_t)reflect101(yy, h) * w + reflect101(xx, w)]; };
-        double sxx = 0.0, sxy = 0.0, syy = 0.0;                 // Python's sum(): 0 + p00 + p01 + ... in (i, j) row-major order
+__device__ __forceinline__ float min_eig_px(const uint8_t* g, int h, int w, int idx) {
+    const int y = idx / w, x = idx - y * w;
+    const double sc = 1.0 / (4.0 * 3.0 * 255.0);
+    auto G = [&](int yy, int xx) { return (double)g[(size_t)reflect101(yy, h) * w + reflect101(xx, w)]; };
+    double sxx = 0.0, sxy = 0.0, syy = 0.0;                 // Python's sum(): 0 + p00 + p01 + ... in (i, j) row-major order
 #pragma unroll
-        for (int i = -1; i <= 1; ++i)
+    for (int i = -1; i <= 1; ++i)
 #pragma unroll
-            for (int j = -1; j <= 1; ++j) {
-                const int yy = reflect101(y + i, h), xx = reflect101(x + j, w);     // the product arrays are reflect-padded
-                const double dx = ((G(yy - 1, xx + 1) - G(yy - 1, xx - 1)) + 2 * (G(yy, xx + 1) - G(yy, xx - 1)) + (G(yy + 1, xx + 1) - G(yy + 1, xx - 1))) * sc;
-                const double dy = ((G(yy + 1, xx - 1) - G(yy - 1, xx - 1)) + 2 * (G(yy + 1, xx) - G(yy - 1, xx)) + (G(yy + 1, xx + 1) - G(yy - 1, xx + 1))) * sc;
-                sxx += dx * dx; sxy += dx * dy; syy += dy * dy;
-            }
-        const double a = sxx * 0.5, b = sxy, c = syy * 0.5;
-        e = (float)((a + c) - sqrt((a - c) * (a - c) + b * b));
-        eig[idx] = e;
-    }
-    // block maximum, then one atomic per block
+        for (int j = -1; j <= 1; ++j) {
+            const int yy = reflect101(y + i, h), xx = reflect101(x + j, w);     // the product arrays are reflect-padded
+            const double dx = ((G(yy - 1, xx + 1) - G(yy - 1, xx - 1)) + 2 * (G(yy, xx + 1) - G(yy, xx - 1)) + (G(yy + 1, xx + 1) - G(yy + 1, xx - 1))) * sc;
+            const double dy = ((G(yy + 1, xx - 1) - G(yy - 1, xx - 1)) + 2 * (G(yy + 1, xx) - G(yy - 1, xx)) + (G(yy + 1, xx + 1) - G(yy - 1, xx + 1))) * sc;
+            sxx += dx * dx; sxy += dx * dy; syy += dy * dy;
+        }
+    const double a = sxx * 0.5, b = sxy, c = syy * 0.5;
+    return (float)((a + c) - sqrt((a - c) * (a - c) + b * b));
+}
+// block maximum of e (every thread of the 256-thread block calls), then one atomic per block
+__device__ __forceinline__ void block_max_to(float e, unsigned* max_bits) {
     float m = e > 0.f ? e : 0.f;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
@@ -382,14 +396,20 @@ __global__ __launch_bounds__(256) void min_eig_kernel(const uint8_t* g, int h, i
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(max_bits, __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));
 }
+__global__ __launch_bounds__(256) void min_eig_kernel(const uint8_t* g, int h, int w, float* eig, unsigned* max_bits, size_t g_fstride = 0) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    g += blockIdx.y * g_fstride; eig += (size_t)blockIdx.y * h * w; max_bits += blockIdx.y;
+    float e = 0.f;
+    if (idx < h * w) {
+        e = min_eig_px(g, h, w, idx);
+        eig[idx] = e;
+    }
+    block_max_to(e, max_bits);
+}
 
 // THRESH_TOZERO at quality * max, 3x3 non-maximum suppression (a corner equals the maximum of its neighbourhood), image border excluded
-__global__ __launch_bounds__(256) void corner_mask_kernel(const float* eig, int h, int w, const unsigned* max_bits, double quality, uint8_t* ok) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= h * w) return;
-    eig += (size_t)blockIdx.y * h * w; ok += (size_t)blockIdx.y * h * w; max_bits += blockIdx.y;
+__device__ __forceinline__ uint8_t corner_mask_px(const float* eig, int h, int w, float mx, double quality, int idx) {
     const int y = idx / w, x = idx - y * w;
-    const float mx = __uint_as_float(*max_bits);
     const float thr = (float)((double)mx * quality);
     auto T = [&](int yy, int xx) {
         if (yy < 0 || yy >= h || xx < 0 || xx >= w) return -INFINITY;
@@ -403,7 +423,13 @@ __global__ __launch_bounds__(256) void corner_mask_kernel(const float* eig, int 
 #pragma unroll
         for (int j = -1; j <= 1; ++j) d = fmaxf(d, T(y + i, x + j));
     const bool keep = mx > 0.f && v != 0.f && v == d && y > 0 && y < h - 1 && x > 0 && x < w - 1;
-    ok[idx] = keep ? 1 : 0;
+    return keep ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void corner_mask_kernel(const float* eig, int h, int w, const unsigned* max_bits, double quality, uint8_t* ok) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= h * w) return;
+    eig += (size_t)blockIdx.y * h * w; ok += (size_t)blockIdx.y * h * w; max_bits += blockIdx.y;
+    ok[idx] = corner_mask_px(eig, h, w, __uint_as_float(*max_bits), quality, idx);
 }
 
 // per-device scratch, grow-only; calls are serialised (the tracker is sequential per video)
@@ -421,6 +447,23 @@ GmcCtx g_ctx[16];
 
 #define GCHK(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return -2; } } while (0)
 
+// buildOpticalFlowPyramid's level geometry, stated once for every entry point: level l + 1 is ((h + 1) / 2) x ((w + 1) / 2) and exists while
+// it is larger than the window in both directions (at most max_level levels above the plane, kMaxLevels in all).  off[l]: byte offset of
+// level l in a pyramid whose planes start 256 bytes aligned; *bytes: the pyramid's size.  Returns the number of levels.
+int pyr_geometry(int h0, int w0, int max_level, int win, int* hs, int* ws, size_t* off, size_t* bytes) {
+    int levels = 1;
+    hs[0] = h0; ws[0] = w0;
+    for (int l = 0; l < max_level && levels < kMaxLevels; ++l) {
+        const int nh = (hs[levels - 1] + 1) / 2, nw = (ws[levels - 1] + 1) / 2;
+        if (nh <= win || nw <= win) break;
+        hs[levels] = nh; ws[levels] = nw; ++levels;
+    }
+    size_t total = 0;
+    for (int l = 0; l < levels; ++l) { off[l] = total; total += ((size_t)hs[l] * ws[l] + 255) & ~(size_t)255; }
+    *bytes = total;
+    return levels;
+}
+
 }  // namespace
 
 // Same contract as mi355_gmc_pyr_lk (gmc_host.cpp) with the work done on GPU `device`: 0 = ok, -1 = bad argument, -2 = HIP error.
@@ -435,15 +478,9 @@ extern "C" int mi355_gmc_pyr_lk_device(int device, const uint8_t* prev, const ui
     GmcCtx& c = g_ctx[device];
     if (!c.stream) { GCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking)); c.device = device; }
     // level geometry (buildOpticalFlowPyramid stops at levels not larger than the window)
-    int hs[kMaxLevels], ws[kMaxLevels], levels = 1;
-    hs[0] = height; ws[0] = width;
-    for (int l = 0; l < max_level && levels < kMaxLevels; ++l) {
-        const int nh = (hs[levels - 1] + 1) / 2, nw = (ws[levels - 1] + 1) / 2;
-        if (nh <= win || nw <= win) break;
-        hs[levels] = nh; ws[levels] = nw; ++levels;
-    }
+    int hs[kMaxLevels], ws[kMaxLevels];
     size_t off[kMaxLevels], pyr_bytes = 0;
-    for (int l = 0; l < levels; ++l) { off[l] = pyr_bytes; pyr_bytes += ((size_t)hs[l] * ws[l] + 255) & ~(size_t)255; }
+    const int levels = pyr_geometry(height, width, max_level, win, hs, ws, off, &pyr_bytes);
     if (c.planes_cap < 2 * pyr_bytes) {
         if (c.d_planes) (void)hipFree(c.d_planes);
         c.d_planes = nullptr; c.planes_cap = 0;
@@ -650,15 +687,9 @@ extern "C" int mi355_gmc_step_begin(mi355_gmc* g, const uint8_t* bgr, int height
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t nb = (size_t)height * width * 3, np = (size_t)oh * ow;
     // pyramid geometry of the oh x ow plane
-    int hs[kMaxLevels], ws[kMaxLevels], levels = 1;
-    hs[0] = oh; ws[0] = ow;
-    for (int l = 0; l < max_level && levels < kMaxLevels; ++l) {
-        const int nh = (hs[levels - 1] + 1) / 2, nw = (ws[levels - 1] + 1) / 2;
-        if (nh <= win || nw <= win) break;
-        hs[levels] = nh; ws[levels] = nw; ++levels;
-    }
+    int hs[kMaxLevels], ws[kMaxLevels];
     size_t off[kMaxLevels], pyr_bytes = 0;
-    for (int l = 0; l < levels; ++l) { off[l] = pyr_bytes; pyr_bytes += al((size_t)hs[l] * ws[l]); }
+    const int levels = pyr_geometry(oh, ow, max_level, win, hs, ws, off, &pyr_bytes);
     if (g->pyr_cap < pyr_bytes) {
         for (int i = 0; i < 2; ++i) { if (g->d_pyr[i]) (void)hipFree(g->d_pyr[i]); g->d_pyr[i] = nullptr; }
         g->pyr_cap = 0; g->have_prev = false;
@@ -788,6 +819,34 @@ void linear_table(int dn, int sn, std::vector<int>& tab) {
         tab[d * 3 + 2] = (int)lrintf(fx * 2048.f);
     }
 }
+
+// The host half of a step behind the kernels (one statement, for the single object and the multi-camera one): the partial affine transform
+// prev -> cur from the tracked pairs (RANSAC, seed 0) when more than 4 survive, its translation scaled back to frame pixels -- else the
+// identity; then this frame's corners, strongest first, into prev_pts for the next step.
+void step_tail(const float* lk_pts, const float* next_pts, const uint8_t* status, int n, int downscale, const float* eig, const uint8_t* ok, int oh, int ow,
+               std::vector<float>& prev_pts, double* H) {
+    H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0;
+    if (n > 0) {
+        std::vector<double> src, dst;
+        for (int i = 0; i < n; ++i)
+            if (status[i]) {
+                src.push_back(lk_pts[2 * i]); src.push_back(lk_pts[2 * i + 1]);
+                dst.push_back(next_pts[2 * i]); dst.push_back(next_pts[2 * i + 1]);
+            }
+        const int m = (int)(src.size() / 2);
+        if (m > 4) {
+            double E[6];
+            if (mi355_gmc_affine_partial(src.data(), dst.data(), m, kRansacThr, kRansacConf, kRansacIters, 0ull, E, nullptr) == 1) {
+                std::memcpy(H, E, sizeof(E));
+                H[2] *= downscale; H[5] *= downscale;
+            }
+        }
+    }
+    // this frame becomes the previous one: its corners, strongest first
+    prev_pts.resize((size_t)kMaxCorners * 2);
+    const int nc = mi355_gmc_order_corners(eig, ok, oh, ow, kMaxCorners, prev_pts.data());
+    prev_pts.resize((size_t)std::max(nc, 0) * 2);
+}
 }  // namespace
 
 static void collect_worker(mi355_gmc* g);
@@ -871,27 +930,8 @@ static int track_collect(mi355_gmc* g, double* H_out) {
         const int rc = mi355_gmc_step_finish(g, g->cur_gray.data(), g->eig.data(), g->ok.data(), n ? g->next_pts.data() : nullptr, n ? g->status.data() : nullptr);
         if (rc) { g->have_prev_pts = false; return rc; }
     }
-    double H[6] = {1, 0, 0, 0, 1, 0};
-    if (n > 0) {
-        std::vector<double> src, dst;
-        for (int i = 0; i < n; ++i)
-            if (g->status[i]) {
-                src.push_back(g->lk_pts[2 * i]); src.push_back(g->lk_pts[2 * i + 1]);
-                dst.push_back(g->next_pts[2 * i]); dst.push_back(g->next_pts[2 * i + 1]);
-            }
-        const int m = (int)(src.size() / 2);
-        if (m > 4) {
-            double E[6];
-            if (mi355_gmc_affine_partial(src.data(), dst.data(), m, kRansacThr, kRansacConf, kRansacIters, 0ull, E, nullptr) == 1) {
-                std::memcpy(H, E, sizeof(H));
-                H[2] *= g->downscale; H[5] *= g->downscale;
-            }
-        }
-    }
-    // this frame becomes the previous one: its plane and its corners, strongest first
-    g->prev_pts.resize((size_t)kMaxCorners * 2);
-    const int nc = mi355_gmc_order_corners(g->eig.data(), g->ok.data(), oh, ow, kMaxCorners, g->prev_pts.data());
-    g->prev_pts.resize((size_t)std::max(nc, 0) * 2);
+    double H[6];
+    step_tail(g->lk_pts.data(), g->next_pts.data(), g->status.data(), n, g->downscale, g->eig.data(), g->ok.data(), oh, ow, g->prev_pts, H);
     g->prev_gray.swap(g->cur_gray);
     g->prev_h = oh; g->prev_w = ow; g->have_prev_pts = true;
     std::memcpy(H_out, H, sizeof(H));
@@ -926,15 +966,9 @@ extern "C" int mi355_gmc_track_batch(mi355_gmc* g, const uint8_t* const* frames,
     }
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t nb = (size_t)height * width * 3, np = (size_t)oh * ow;
-    int hs[kMaxLevels], ws[kMaxLevels], levels = 1;
-    hs[0] = oh; ws[0] = ow;
-    for (int l = 0; l < kLkLevels && levels < kMaxLevels; ++l) {
-        const int nh = (hs[levels - 1] + 1) / 2, nw = (ws[levels - 1] + 1) / 2;
-        if (nh <= kLkWin || nw <= kLkWin) break;
-        hs[levels] = nh; ws[levels] = nw; ++levels;
-    }
+    int hs[kMaxLevels], ws[kMaxLevels];
     size_t off[kMaxLevels], pyr_bytes = 0;
-    for (int l = 0; l < levels; ++l) { off[l] = pyr_bytes; pyr_bytes += al((size_t)hs[l] * ws[l]); }
+    const int levels = pyr_geometry(oh, ow, kLkLevels, kLkWin, hs, ws, off, &pyr_bytes);
     // does the object's previous frame precede frames[0]?  (same plane size, corners known, its pyramid on the device)
     const bool cont = g->have_prev_pts && g->prev_h == oh && g->prev_w == ow && g->have_prev && g->ph == oh && g->pw == ow && g->pyr_cap >= pyr_bytes;
     // device: [frames n x nb | pyramids (n + 1) x pyr_bytes | eig n x np x 4 | ok n x np | x table | y table | max n x 4 | pts n x kMaxCorners x 8 |
@@ -1114,5 +1148,466 @@ extern "C" int mi355_gmc_track_state(const mi355_gmc* g, int* oh, int* ow, int* 
     if (n_pts) *n_pts = n;
     if (gray_out && g->have_prev_pts) std::memcpy(gray_out, g->prev_gray.data(), g->prev_gray.size());
     if (pts_out && pts_cap > 0 && n > 0) std::memcpy(pts_out, g->prev_pts.data(), (size_t)std::min(n, pts_cap) * 8);
+    return 0;
+}
+
+// ---- several cameras, one step per tick: mi355_gmc_multi -------------------------------------------------------------------------------
+// A store has N cameras of different resolutions and every tick brings one frame of each (or of some).  N mi355_gmc objects cost N streams,
+// N worker threads and N sets of small launches; here the tick is ONE launch per stage (per pyramid level), whatever the frames' sizes: the
+// kernels read a device array of per-camera descriptors (GmcCam) and a host-built prefix table that maps a block to (camera, block of that
+// camera's plane).  The arithmetic per pixel / per point is the *_px / lk_point functions above -- the bits of N single objects.
+namespace {
+
+struct GmcCam {
+    const uint8_t* src; int H, W, row_stride, resize;       // the tick's frame on the device (dense BGR)
+    int oh, ow;                                              // plane size
+    unsigned long long xtab, ytab;                           // arena offsets of the INTER_LINEAR tables
+    unsigned long long prev, cur;                            // arena offsets of the previous / this frame's pyramid; level l at + lvl[l]
+    unsigned lvl[kMaxLevels]; int h[kMaxLevels], w[kMaxLevels]; int top;
+    unsigned long long gray, eig, ok;                        // tick-output offsets: copy of the plane, min-eigenvalue map, corner mask
+    int max_idx;                                             // its word among the tick's maxima
+    int n_pts; unsigned long long pts, next, status;         // points tracked from `prev` (tick-input offset), results (tick-output offsets)
+};
+static_assert(sizeof(GmcCam) % 8 == 0, "descriptor array stride");
+
+// prefix tables behind the descriptors, (n + 1) ints each: blocks of the plane kernels, of lk, of pyrDown into level 1 .. kMaxLevels - 1
+constexpr int kPrefixPlane = 0, kPrefixLk = 1, kPrefixLevel1 = 2, kPrefixTables = 2 + (kMaxLevels - 1);
+constexpr int prefix_level(int l) { return kPrefixLevel1 + (l - 1); }          // l = 1 .. kMaxLevels - 1
+
+struct MultiArgs {
+    const GmcCam* cams; const int* prefix;                   // this launch's prefix table
+    int n;                                                   // cameras in the array
+    uint8_t* arena; const uint8_t* tin; uint8_t* tout;
+};
+
+// this block's camera and its block number inside that camera's work; false = nothing to do.  Block-uniform: the table sits in scalar registers.
+// (A grid with one row per camera, as wide as the largest camera needs, was measured against this lookup and dropped: DESIGN 3.6b.)
+__device__ __forceinline__ bool locate(const MultiArgs& m, int& cam, int& b) {
+    const int g = blockIdx.x;
+    int lo = 0, hi = m.n;                                    // largest cam with prefix[cam] <= g (g < prefix[n] by the grid size)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (m.prefix[mid] <= g) lo = mid; else hi = mid;
+    }
+    cam = __builtin_amdgcn_readfirstlane(lo); b = g - m.prefix[cam];
+    return b < m.prefix[cam + 1] - m.prefix[cam];
+}
+
+__global__ __launch_bounds__(256) void gray_resize_multi_kernel(MultiArgs m) {
+    int cam, b;
+    if (!locate(m, cam, b)) return;
+    const GmcCam& c = m.cams[cam];
+    const int idx = b * 256 + threadIdx.x;
+    if (idx >= c.oh * c.ow) return;
+    const uint8_t v = gray_resize_px(c.src, c.H, c.W, (size_t)c.row_stride, (const int*)(m.arena + c.xtab), (const int*)(m.arena + c.ytab), c.ow, c.resize, idx);
+    (m.arena + c.cur)[idx] = v;                              // level 0 of this frame's pyramid
+    (m.tout + c.gray)[idx] = v;                              // ... and the copy that goes back to the host with the tick's results
+}
+
+__global__ __launch_bounds__(256) void min_eig_multi_kernel(MultiArgs m) {
+    int cam, b;
+    if (!locate(m, cam, b)) return;
+    const GmcCam& c = m.cams[cam];
+    const int idx = b * 256 + threadIdx.x;
+    float e = 0.f;
+    if (idx < c.oh * c.ow) {
+        e = min_eig_px(m.arena + c.cur, c.oh, c.ow, idx);
+        ((float*)(m.tout + c.eig))[idx] = e;
+    }
+    block_max_to(e, (unsigned*)m.tout + c.max_idx);
+}
+
+__global__ __launch_bounds__(256) void corner_mask_multi_kernel(MultiArgs m, double quality) {
+    int cam, b;
+    if (!locate(m, cam, b)) return;
+    const GmcCam& c = m.cams[cam];
+    const int idx = b * 256 + threadIdx.x;
+    if (idx >= c.oh * c.ow) return;
+    (m.tout + c.ok)[idx] = corner_mask_px((const float*)(m.tout + c.eig), c.oh, c.ow, __uint_as_float(((const unsigned*)m.tout)[c.max_idx]), quality, idx);
+}
+
+__global__ __launch_bounds__(256) void pyr_down_multi_kernel(MultiArgs m, int l) {          // level l - 1 -> level l of every camera that has one
+    int cam, b;
+    if (!locate(m, cam, b)) return;
+    const GmcCam& c = m.cams[cam];
+    const int idx = b * 256 + threadIdx.x;
+    if (l > c.top || idx >= c.h[l] * c.w[l]) return;
+    uint8_t* pyr = m.arena + c.cur;
+    (pyr + c.lvl[l])[idx] = pyr_down_px(pyr + c.lvl[l - 1], c.h[l - 1], c.w[l - 1], c.w[l], idx);
+}
+
+struct LkCamView {
+    const GmcCam* c; const uint8_t* arena;
+    int top, win, max_iters, width, height;
+    double eps2, min_eig;
+    const float* pts; float* next; uint8_t* status;
+    __device__ __forceinline__ const uint8_t* prev_at(int l) const { return arena + c->prev + c->lvl[l]; }
+    __device__ __forceinline__ const uint8_t* cur_at(int l) const { return arena + c->cur + c->lvl[l]; }
+    __device__ __forceinline__ int h_at(int l) const { return c->h[l]; }
+    __device__ __forceinline__ int w_at(int l) const { return c->w[l]; }
+};
+
+__global__ __launch_bounds__(64 * kLkWaves) void lk_multi_kernel(MultiArgs m, int win, int max_iters, double eps2, double min_eig) {
+    __shared__ uint8_t region[kLkWaves][(kRegMax * kRegMax + 15) & ~15];
+    __shared__ LkScratch scratch[kLkWaves];
+    int cam, b;
+    if (!locate(m, cam, b)) return;
+    const GmcCam& c = m.cams[cam];
+    const int lane = threadIdx.x & 63;
+    const int i = b * kLkWaves + (threadIdx.x >> 6);
+    if (i >= c.n_pts) return;
+    LkCamView a;
+    a.c = &c; a.arena = m.arena; a.top = c.top; a.win = win; a.max_iters = max_iters; a.width = c.ow; a.height = c.oh; a.eps2 = eps2; a.min_eig = min_eig;
+    a.pts = (const float*)(m.tin + c.pts); a.next = (float*)(m.tout + c.next); a.status = m.tout + c.status;
+    lk_point(a, i, lane, region[threadIdx.x >> 6], scratch[threadIdx.x >> 6]);
+}
+
+struct MultiCam {
+    // GMC.apply_sparseoptflow's state of this camera (as mi355_gmc holds it for one)
+    std::vector<int> xt, yt; int tkey[4] = {0, 0, 0, 0};
+    std::vector<float> prev_pts, lk_pts; std::vector<uint8_t> prev_gray;
+    int prev_h = 0, prev_w = 0; bool have_prev_pts = false;
+    // its region of the arena: [pyramid slot 0 | pyramid slot 1 | x table | y table]
+    size_t region = 0, region_cap = 0, pyr_bytes = 0;
+    int slot = 0; bool have_prev = false; int ph = 0, pw = 0; int tab_key[4] = {0, 0, 0, 0};
+    // the pending tick
+    bool active = false; int H = 0, W = 0, oh = 0, ow = 0, n = 0;
+    size_t t_frame = 0, t_pts = 0, o_gray = 0, o_eig = 0, o_ok = 0, o_next = 0, o_status = 0;
+    double Hm[6] = {1, 0, 0, 0, 1, 0}; int rc = 0;
+};
+
+}  // namespace
+
+struct mi355_gmc_multi {
+    int device = -1, n = 0; bool host = false;
+    std::vector<mi355_gmc*> single;                           // host object: one host mi355_gmc per camera
+    std::vector<MultiCam> cams;
+    hipStream_t stream = nullptr; hipEvent_t ev_up = nullptr, ev_done = nullptr;
+    uint8_t* arena = nullptr; size_t arena_cap = 0, arena_used = 0;
+    uint8_t* d_tin = nullptr; uint8_t* h_tin = nullptr; size_t tin_cap = 0;       // the tick's frames + points (pinned mirror): ONE upload
+    uint8_t* d_tout = nullptr; uint8_t* h_tout = nullptr; size_t tout_cap = 0;    // maxima + per camera gray / eig / ok / next / status: ONE download
+    uint8_t* d_desc = nullptr; uint8_t* h_desc = nullptr; size_t desc_cap = 0, desc_bytes = 0;
+    std::vector<int> active;                                  // cameras of the pending tick, in camera order
+    std::vector<std::thread> workers;
+    bool job_active = false;                                  // written by the calling thread only: a tick has been begun and not collected
+    int downscale = 2;
+};
+
+extern "C" int mi355_gmc_multi_create(int device, int n_cameras, mi355_gmc_multi** out) {
+    if (!out || device < -1 || n_cameras <= 0 || n_cameras > 4096) return -1;
+    *out = nullptr;
+    mi355_gmc_multi* g = new mi355_gmc_multi();
+    g->device = device; g->n = n_cameras; g->host = device == -1;
+    g->cams.resize((size_t)n_cameras);
+    if (g->host) {
+        g->single.assign((size_t)n_cameras, nullptr);
+        for (int i = 0; i < n_cameras; ++i) if (mi355_gmc_create(-1, &g->single[i])) { mi355_gmc_multi_destroy(g); return -1; }
+        *out = g;
+        return 0;
+    }
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&g->ev_up, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError(); mi355_gmc_multi_destroy(g); return -2;
+    }
+    *out = g;
+    return 0;
+}
+
+extern "C" void mi355_gmc_multi_destroy(mi355_gmc_multi* g) {
+    if (!g) return;
+    for (auto& t : g->workers) if (t.joinable()) t.join();
+    for (mi355_gmc* s : g->single) if (s) mi355_gmc_destroy(s);
+    if (!g->host) {
+        (void)hipSetDevice(g->device);
+        if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
+        if (g->ev_up) (void)hipEventDestroy(g->ev_up);
+        if (g->ev_done) (void)hipEventDestroy(g->ev_done);
+        if (g->arena) (void)hipFree(g->arena);
+        if (g->d_tin) (void)hipFree(g->d_tin); if (g->h_tin) (void)hipHostFree(g->h_tin);
+        if (g->d_tout) (void)hipFree(g->d_tout); if (g->h_tout) (void)hipHostFree(g->h_tout);
+        if (g->d_desc) (void)hipFree(g->d_desc); if (g->h_desc) (void)hipHostFree(g->h_desc);
+    }
+    delete g;
+}
+
+namespace {
+int multi_threads(int active) { return std::max(1, std::min(std::min(8, active), (int)std::thread::hardware_concurrency())); }
+
+// grow-only pair of a device buffer and its pinned mirror
+int grow_pair(uint8_t*& d, uint8_t*& h, size_t& cap, size_t need) {
+    if (cap >= need) return 0;
+    if (d) (void)hipFree(d); if (h) (void)hipHostFree(h);
+    d = h = nullptr; cap = 0;
+    need += need / 4;
+    GCHK(hipMalloc(&d, need)); GCHK(hipHostMalloc(&h, need)); cap = need;
+    return 0;
+}
+
+// the host half of camera ci's step, on a worker: wait for the tick's results, then step_tail
+void multi_collect(mi355_gmc_multi* g, int ci) {
+    MultiCam& c = g->cams[ci];
+    if (g->host) { c.rc = mi355_gmc_track_finish(g->single[ci], c.Hm); return; }
+    if (hipEventSynchronize(g->ev_done) != hipSuccess) { (void)hipGetLastError(); c.rc = -2; c.have_prev = false; c.have_prev_pts = false; return; }
+    const uint8_t* P = g->h_tout;
+    const size_t np = (size_t)c.oh * c.ow;
+    step_tail(c.lk_pts.data(), (const float*)(P + c.o_next), P + c.o_status, c.n, g->downscale, (const float*)(P + c.o_eig), P + c.o_ok, c.oh, c.ow, c.prev_pts, c.Hm);
+    c.prev_gray.assign(P + c.o_gray, P + c.o_gray + np);
+    c.prev_h = c.oh; c.prev_w = c.ow; c.have_prev_pts = true;
+    c.rc = 0;
+}
+
+void multi_start_workers(mi355_gmc_multi* g) {
+    const int na = (int)g->active.size(), nt = multi_threads(na);
+    g->workers.clear();
+    for (int t = 0; t < nt; ++t)
+        g->workers.emplace_back([g, t, nt, na] {
+            if (!g->host) (void)hipSetDevice(g->device);
+            for (int k = t; k < na; k += nt) multi_collect(g, g->active[k]);
+        });
+    g->job_active = true;
+}
+
+int multi_begin_device(mi355_gmc_multi* g, const uint8_t* const* frames, const int* heights, const int* widths, int downscale) {
+    GCHK(hipSetDevice(g->device));
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const int na = (int)g->active.size();
+    const int resize = downscale > 1;
+    // per camera: plane and pyramid geometry, its region of the arena, what it tracks
+    size_t t_total = 0, o_total = al((size_t)na * 4);
+    std::vector<GmcCam> desc((size_t)na);
+    std::vector<int> prefix((size_t)kPrefixTables * (na + 1), 0);
+    int max_top = 0;
+    size_t new_bytes = 0;
+    std::vector<int> placed;                                    // cameras given a new region this tick: theirs only once the arena holds it
+    for (int k = 0; k < na; ++k) {
+        const int ci = g->active[k];
+        MultiCam& c = g->cams[ci];
+        c.H = heights[ci]; c.W = widths[ci];
+        c.oh = resize ? c.H / downscale : c.H; c.ow = resize ? c.W / downscale : c.W;
+        if (resize && !(c.tkey[0] == c.H && c.tkey[1] == c.W && c.tkey[2] == c.oh && c.tkey[3] == c.ow)) {
+            linear_table(c.ow, c.W, c.xt); linear_table(c.oh, c.H, c.yt);
+            c.tkey[0] = c.H; c.tkey[1] = c.W; c.tkey[2] = c.oh; c.tkey[3] = c.ow;
+        }
+        // the previous frame's corners are tracked only into a plane of the same size (as mi355_gmc_track_begin)
+        const bool lk = c.have_prev_pts && c.prev_h == c.oh && c.prev_w == c.ow && !c.prev_pts.empty() && c.have_prev && c.ph == c.oh && c.pw == c.ow;
+        c.lk_pts.clear();
+        if (lk) c.lk_pts = c.prev_pts;
+        c.n = (int)(c.lk_pts.size() / 2);
+        GmcCam& d = desc[k];
+        std::memset(&d, 0, sizeof(d));
+        size_t off[kMaxLevels], pyr_bytes = 0;
+        const int levels = pyr_geometry(c.oh, c.ow, kLkLevels, kLkWin, d.h, d.w, off, &pyr_bytes);
+        for (int l = 0; l < levels; ++l) d.lvl[l] = (unsigned)off[l];
+        d.top = levels - 1; max_top = std::max(max_top, d.top);
+        const size_t need = 2 * pyr_bytes + al((size_t)c.ow * 12) + al((size_t)c.oh * 12);
+        if (c.region_cap < need) {                              // a larger plane than this camera ever had: a new region at the arena's end
+            c.region = al(g->arena_used + new_bytes); new_bytes = c.region + need - g->arena_used; c.region_cap = need;
+            placed.push_back(ci);
+            c.have_prev = false; c.tab_key[0] = 0; c.n = 0; c.lk_pts.clear();
+        }
+        if (c.pyr_bytes != pyr_bytes) { c.pyr_bytes = pyr_bytes; c.have_prev = false; c.tab_key[0] = 0; c.n = 0; c.lk_pts.clear(); }
+        d.H = c.H; d.W = c.W; d.row_stride = c.W * 3; d.resize = resize; d.oh = c.oh; d.ow = c.ow;
+        d.xtab = c.region + 2 * pyr_bytes; d.ytab = d.xtab + al((size_t)c.ow * 12);
+        d.prev = c.region + (size_t)c.slot * pyr_bytes; d.cur = c.region + (size_t)(c.slot ^ 1) * pyr_bytes;
+        d.n_pts = c.n; d.max_idx = k;
+        const size_t np = (size_t)c.oh * c.ow;
+        c.t_frame = t_total; t_total += al((size_t)c.H * c.W * 3);                  // frame starts 256-byte aligned: the detector reads them in place
+        c.o_gray = o_total; o_total += al(np);
+        c.o_eig = o_total; o_total += al(np * 4);
+        c.o_ok = o_total; o_total += al(np);
+        c.o_next = o_total; o_total += al((size_t)c.n * 8);
+        c.o_status = o_total; o_total += al((size_t)c.n);
+        d.gray = c.o_gray; d.eig = c.o_eig; d.ok = c.o_ok; d.next = c.o_next; d.status = c.o_status;
+    }
+    const size_t t_frames_end = t_total;
+    for (int k = 0; k < na; ++k) { MultiCam& c = g->cams[g->active[k]]; c.t_pts = t_total; desc[k].pts = c.t_pts; t_total += al((size_t)c.n * 8); }
+    std::vector<size_t> t_tab((size_t)na, 0);                   // resize tables that have to go up, staged behind the points
+    for (int k = 0; k < na; ++k) {
+        MultiCam& c = g->cams[g->active[k]];
+        if (resize && !(c.tab_key[0] == c.H && c.tab_key[1] == c.W && c.tab_key[2] == c.oh && c.tab_key[3] == c.ow)) {
+            t_tab[k] = t_total; t_total += al((size_t)c.ow * 12) + al((size_t)c.oh * 12);
+        }
+    }
+    if (new_bytes) {
+        const size_t need = g->arena_used + new_bytes;
+        if (g->arena_cap < need) {                              // grow-only: the cameras' previous pyramids move with it
+            const size_t cap = std::max(need + need / 2, (size_t)1 << 20);
+            uint8_t* a = nullptr;
+            auto unplace = [&] { for (int ci : placed) g->cams[ci].region = g->cams[ci].region_cap = 0; };
+            if (hipMalloc(&a, cap) != hipSuccess) { (void)hipGetLastError(); unplace(); return -2; }
+            if (g->arena && g->arena_used) {
+                if (hipMemcpyAsync(a, g->arena, g->arena_used, hipMemcpyDeviceToDevice, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess) {
+                    (void)hipGetLastError(); (void)hipFree(a); unplace(); return -2;
+                }
+            }
+            if (g->arena) (void)hipFree(g->arena);
+            g->arena = a; g->arena_cap = cap;
+        }
+        g->arena_used = need;
+    }
+    if (grow_pair(g->d_tin, g->h_tin, g->tin_cap, t_total)) return -2;
+    if (grow_pair(g->d_tout, g->h_tout, g->tout_cap, o_total)) return -2;
+    // descriptors (+ prefix tables): one image, uploaded only when its bytes differ from what the device holds
+    for (int k = 0; k < na; ++k) {
+        const MultiCam& c = g->cams[g->active[k]];
+        const GmcCam& d = desc[k];
+        desc[k].src = g->d_tin + c.t_frame;
+        int* p = prefix.data();
+        p[kPrefixPlane * (na + 1) + k + 1] = p[kPrefixPlane * (na + 1) + k] + (int)(((size_t)c.oh * c.ow + 255) / 256);
+        for (int l = 1; l < kMaxLevels; ++l)
+            p[prefix_level(l) * (na + 1) + k + 1] = p[prefix_level(l) * (na + 1) + k] + (l <= d.top ? (d.h[l] * d.w[l] + 255) / 256 : 0);
+        p[kPrefixLk * (na + 1) + k + 1] = p[kPrefixLk * (na + 1) + k] + (c.n + kLkWaves - 1) / kLkWaves;
+    }
+    const size_t desc_b = al((size_t)na * sizeof(GmcCam)), bytes = desc_b + al(prefix.size() * 4);
+    if (g->desc_cap < bytes) { g->desc_bytes = 0; if (grow_pair(g->d_desc, g->h_desc, g->desc_cap, bytes)) return -2; }
+    std::vector<char> img(bytes, 0);
+    std::memcpy(img.data(), desc.data(), (size_t)na * sizeof(GmcCam));
+    std::memcpy(img.data() + desc_b, prefix.data(), prefix.size() * 4);
+    // stage the frames (a few threads when they are large) and the points, then ONE upload
+    uint8_t* P = g->h_tin;
+    {
+        const int nt = multi_threads(na);
+        auto copy = [&](int k) { const int ci = g->active[k]; const MultiCam& c = g->cams[ci]; std::memcpy(P + c.t_frame, frames[ci], (size_t)c.H * c.W * 3); };
+        if (nt <= 1 || t_frames_end < ((size_t)1 << 20)) { for (int k = 0; k < na; ++k) copy(k); }
+        else {
+            std::vector<std::thread> th;
+            for (int t = 0; t < nt; ++t) th.emplace_back([&, t] { for (int k = t; k < na; k += nt) copy(k); });
+            for (auto& t : th) t.join();
+        }
+    }
+    for (int k = 0; k < na; ++k) {
+        const MultiCam& c = g->cams[g->active[k]];
+        if (c.n) std::memcpy(P + c.t_pts, c.lk_pts.data(), (size_t)c.n * 8);
+        if (t_tab[k]) { std::memcpy(P + t_tab[k], c.xt.data(), (size_t)c.ow * 12); std::memcpy(P + t_tab[k] + al((size_t)c.ow * 12), c.yt.data(), (size_t)c.oh * 12); }
+    }
+    GCHK(hipMemcpyAsync(g->d_tin, P, t_total, hipMemcpyHostToDevice, g->stream));
+    GCHK(hipEventRecord(g->ev_up, g->stream));
+    for (int k = 0; k < na; ++k) {
+        MultiCam& c = g->cams[g->active[k]];
+        if (!t_tab[k]) continue;
+        GCHK(hipMemcpyAsync(g->arena + desc[k].xtab, g->d_tin + t_tab[k], (size_t)c.ow * 12, hipMemcpyDeviceToDevice, g->stream));
+        GCHK(hipMemcpyAsync(g->arena + desc[k].ytab, g->d_tin + t_tab[k] + al((size_t)c.ow * 12), (size_t)c.oh * 12, hipMemcpyDeviceToDevice, g->stream));
+        c.tab_key[0] = c.H; c.tab_key[1] = c.W; c.tab_key[2] = c.oh; c.tab_key[3] = c.ow;
+    }
+    if (g->desc_bytes != bytes || std::memcmp(g->h_desc, img.data(), bytes) != 0) {
+        // the previous upload out of h_desc has completed: every tick is collected (ev_done) before the next begins
+        std::memcpy(g->h_desc, img.data(), bytes);
+        GCHK(hipMemcpyAsync(g->d_desc, g->h_desc, bytes, hipMemcpyHostToDevice, g->stream));
+        g->desc_bytes = bytes;
+    }
+    GCHK(hipMemsetAsync(g->d_tout, 0, (size_t)na * 4, g->stream));
+    MultiArgs m{};
+    m.cams = (const GmcCam*)g->d_desc; m.n = na; m.arena = g->arena; m.tin = g->d_tin; m.tout = g->d_tout;
+    const int* d_prefix = (const int*)(g->d_desc + desc_b);
+    auto grid_of = [&](int table) { return dim3((unsigned)prefix[(size_t)table * (na + 1) + na]); };      // blocks of a launch: the table's total
+    {
+        m.prefix = d_prefix + (size_t)kPrefixPlane * (na + 1);
+        const dim3 gr = grid_of(kPrefixPlane);
+        hipLaunchKernelGGL(gray_resize_multi_kernel, gr, dim3(256), 0, g->stream, m);
+        hipLaunchKernelGGL(min_eig_multi_kernel, gr, dim3(256), 0, g->stream, m);
+        hipLaunchKernelGGL(corner_mask_multi_kernel, gr, dim3(256), 0, g->stream, m, kQuality);
+    }
+    for (int l = 1; l <= max_top; ++l) {
+        m.prefix = d_prefix + (size_t)prefix_level(l) * (na + 1);
+        hipLaunchKernelGGL(pyr_down_multi_kernel, grid_of(prefix_level(l)), dim3(256), 0, g->stream, m, l);
+    }
+    if (prefix[(size_t)kPrefixLk * (na + 1) + na] > 0) {
+        m.prefix = d_prefix + (size_t)kPrefixLk * (na + 1);
+        hipLaunchKernelGGL(lk_multi_kernel, grid_of(kPrefixLk), dim3(64 * kLkWaves), 0, g->stream, m, kLkWin, kLkIters, kLkEps * kLkEps, kLkMinEig);
+    }
+    GCHK(hipGetLastError());
+    GCHK(hipMemcpyAsync(g->h_tout, g->d_tout, o_total, hipMemcpyDeviceToHost, g->stream));
+    GCHK(hipEventRecord(g->ev_done, g->stream));
+    for (int k = 0; k < na; ++k) { MultiCam& c = g->cams[g->active[k]]; c.slot ^= 1; c.have_prev = true; c.ph = c.oh; c.pw = c.ow; }
+    return 0;
+}
+}  // namespace
+
+// One tick: frames[i] = camera i's BGR frame of heights[i] x widths[i], or NULL when that camera delivered none (its state stays as it is).
+// Device object: stages the frames, enqueues every stage of every present camera on the object's stream and returns; the host half per
+// camera (corner ordering, RANSAC) runs on at most min(present, 8) worker threads from now on.  Host object (device -1): the same through the
+// host routines.  0 = ok, -1 = bad argument / a tick is pending, -2 = HIP error.
+extern "C" int mi355_gmc_multi_begin(mi355_gmc_multi* g, const uint8_t* const* frames, const int* heights, const int* widths, int downscale) {
+    if (!g || !frames || !heights || !widths || downscale < 1 || g->job_active) return -1;
+    g->active.clear();
+    for (int i = 0; i < g->n; ++i) {
+        g->cams[i].active = false;
+        if (!frames[i]) continue;
+        if (heights[i] <= 0 || widths[i] <= 0 || heights[i] / downscale <= 0 || widths[i] / downscale <= 0) return -1;
+        g->active.push_back(i);
+    }
+    g->downscale = downscale;
+    for (int ci : g->active) { g->cams[ci].active = true; g->cams[ci].rc = 0; }
+    if (g->active.empty()) { g->job_active = true; return 0; }
+    if (g->host) {
+        for (int ci : g->active) {
+            const int rc = mi355_gmc_track_begin(g->single[ci], frames[ci], heights[ci], widths[ci], downscale);
+            if (rc) {                                           // drop what has been begun: nothing of this tick stays pending
+                for (int cj : g->active) { if (cj == ci) break; double H[6]; (void)mi355_gmc_track_finish(g->single[cj], H); }
+                return rc;
+            }
+        }
+    } else {
+        const int rc = multi_begin_device(g, frames, heights, widths, downscale);
+        if (rc) {
+            (void)hipStreamSynchronize(g->stream); (void)hipGetLastError();
+            for (int ci : g->active) { g->cams[ci].have_prev = false; g->cams[ci].have_prev_pts = false; }
+            return rc;
+        }
+    }
+    multi_start_workers(g);
+    return 0;
+}
+
+// Collect the tick: joins the workers; H_out [n_cameras][6] row-major 2 x 3 per camera, rows of absent cameras untouched.
+extern "C" int mi355_gmc_multi_finish(mi355_gmc_multi* g, double* H_out) {
+    if (!g || !H_out || !g->job_active) return -1;
+    for (auto& t : g->workers) if (t.joinable()) t.join();
+    g->workers.clear();
+    g->job_active = false;
+    int rc = 0;
+    for (int ci : g->active) {
+        const MultiCam& c = g->cams[ci];
+        if (c.rc) { if (!rc) rc = c.rc; continue; }
+        std::memcpy(H_out + 6 * (size_t)ci, c.Hm, sizeof(c.Hm));
+    }
+    return rc;
+}
+
+// The pending tick's frames as they sit on the device (dense BGR, each start 256-byte aligned; NULL for an absent camera), after one event
+// wait for the upload -- the detector pass of the same tick reads them in place (mi355_yolo_infer_multi, frames_on_device = 1).  Valid until
+// the next mi355_gmc_multi_begin.
+extern "C" int mi355_gmc_multi_frames(mi355_gmc_multi* g, const uint8_t** dev_frames) {
+    if (!g || g->host || !g->job_active || !dev_frames) return -1;
+    GCHK(hipSetDevice(g->device));
+    if (!g->active.empty()) GCHK(hipEventSynchronize(g->ev_up));
+    for (int i = 0; i < g->n; ++i) dev_frames[i] = g->cams[i].active ? g->d_tin + g->cams[i].t_frame : nullptr;
+    return 0;
+}
+
+// Forget camera `camera`'s previous frame (-1: every camera's); a pending tick is collected and dropped.
+extern "C" int mi355_gmc_multi_reset(mi355_gmc_multi* g, int camera) {
+    if (!g || camera < -1 || camera >= g->n) return -1;
+    if (g->job_active) { std::vector<double> H((size_t)g->n * 6); (void)mi355_gmc_multi_finish(g, H.data()); }
+    for (int i = 0; i < g->n; ++i) {
+        if (camera >= 0 && i != camera) continue;
+        if (g->host) { (void)mi355_gmc_track_reset(g->single[i]); continue; }
+        MultiCam& c = g->cams[i];
+        c.have_prev_pts = false; c.prev_pts.clear(); c.prev_gray.clear(); c.prev_h = c.prev_w = 0; c.have_prev = false;
+    }
+    return 0;
+}
+
+// Camera `camera`'s previous frame as the object holds it (tests), as mi355_gmc_track_state.
+extern "C" int mi355_gmc_multi_state(const mi355_gmc_multi* g, int camera, int* oh, int* ow, int* n_pts, uint8_t* gray_out, float* pts_out, int pts_cap) {
+    if (!g || camera < 0 || camera >= g->n || g->job_active) return -1;
+    if (g->host) return mi355_gmc_track_state(g->single[camera], oh, ow, n_pts, gray_out, pts_out, pts_cap);
+    const MultiCam& c = g->cams[camera];
+    const int n = c.have_prev_pts ? (int)(c.prev_pts.size() / 2) : 0;
+    if (oh) *oh = c.have_prev_pts ? c.prev_h : 0;
+    if (ow) *ow = c.have_prev_pts ? c.prev_w : 0;
+    if (n_pts) *n_pts = n;
+    if (gray_out && c.have_prev_pts) std::memcpy(gray_out, c.prev_gray.data(), c.prev_gray.size());
+    if (pts_out && pts_cap > 0 && n > 0) std::memcpy(pts_out, c.prev_pts.data(), (size_t)std::min(n, pts_cap) * 8);
     return 0;
 }

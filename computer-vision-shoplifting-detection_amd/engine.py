@@ -156,7 +156,20 @@ class YOLO:
 
         def args(self):
             i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
-            return self.ptrs, i32(self.heights), i32(self.widths), i32(self.row_strides), int(self.on_device), len(self.frames)
+            return self.ptrs, i32(self.heights), i32(self.widths), i32(self.row_strides), int(self.on_device), self.shape[0]
+
+    class _RaggedDevice(_Ragged):
+        """Dense BGR uint8 frames of different (h, w) that already sit on the engine's GPU, known by raw pointer (YOLO.track_cameras: the
+        copies the tick's motion compensation uploaded)."""
+        def __init__(self, ptrs, shapes):
+            n = len(ptrs)
+            self.on_device, self.frames = True, None
+            self.shape = (n,)
+            self.shapes = [(int(h), int(w)) for h, w in shapes]
+            self.heights = np.array([s[0] for s in self.shapes], np.int32)
+            self.widths = np.array([s[1] for s in self.shapes], np.int32)
+            self.row_strides = np.array([3 * s[1] for s in self.shapes], np.int32)
+            self.ptrs = (C.c_void_p * n)(*[int(p) for p in ptrs])
 
     @staticmethod
     def _as_batch(source):
@@ -213,7 +226,7 @@ class YOLO:
         cp = counts.ctypes.data_as(C.POINTER(C.c_int))
         with self._lock:
             if isinstance(batch, YOLO._Ragged):
-                if batch.on_device:
+                if batch.on_device and batch.frames is not None:
                     if any(f.device.index != self.device for f in batch.frames):
                         raise ValueError("frames live on a different GPU than the engine")
                     torch.cuda.current_stream(batch.frames[0].device).synchronize()   # engine runs on its own stream
@@ -373,12 +386,84 @@ class YOLO:
             # frame_id, ages lost tracks against track_buffer and runs the Kalman predict); only the rewrite of the
             # result is skipped when no track comes back
             tracks = self._tracker.update(res.boxes.data.numpy(), frame)   # trackers/track.py: tracker.update(det, im0)
-            if len(tracks):
-                idx = tracks[:, -1].astype(int)
-                res = res[idx]
-                res.update(boxes=torch.as_tensor(tracks[:, :-1], dtype=torch.float32))
-            results.append(res)
+            results.append(self._with_tracks(res, tracks))
         return results
+
+    @staticmethod
+    def _with_tracks(res: Results, tracks: np.ndarray) -> Results:
+        """trackers/track.py:on_predict_postprocess_end: the result re-indexed to the detections that carry a track, its boxes rewritten
+        with the ids; untouched when no track came back"""
+        if len(tracks):
+            idx = tracks[:, -1].astype(int)
+            res = res[idx]
+            res.update(boxes=torch.as_tensor(tracks[:, :-1], dtype=torch.float32))
+        return res
+
+    def track_cameras(self, frames: Sequence[Optional[np.ndarray]], persist: bool = False, conf: Optional[float] = None, **kwargs
+                      ) -> List[Optional[Results]]:
+        """One tick of several cameras: ``frames[i]`` is camera i's BGR frame (any size, each camera its own) or None when it delivered
+        none; -> per camera the tracked ``Results`` of :meth:`track`, None for an absent camera (whose tracker does not step).  Ultralytics
+        tracks several streams with one tracker per stream; so does this call -- ids are per camera, each starting at 1 -- but the tick costs
+        ONE detector pass over all present frames (the mixed-shape path of :meth:`predict`) and ONE motion-compensation step
+        (``gmc.MultiGMC``), whose uploaded frames the detector reads in place.  ``persist=True`` continues the cameras' tracks (the list
+        length is the number of cameras and must not change); otherwise every camera starts afresh.  Keyword arguments: ``iou``,
+        ``classes``, ``max_det``, ``imgsz``, ``half`` as in :meth:`predict`; ``show`` / ``verbose`` are accepted and ignored; anything
+        else is a ``TypeError``."""
+        from .gmc import MultiGMC
+        from .tracker import BYTETracker
+        unknown = set(kwargs) - {"iou", "classes", "max_det", "imgsz", "half", "show", "verbose"}
+        if unknown:                                              # show / verbose are accepted and ignored, as in track()
+            raise TypeError(f"track_cameras: unsupported argument(s) {sorted(unknown)} (iou, classes, max_det, imgsz, half pass through)")
+        conf = 0.1 if conf is None else float(conf)
+        frames = list(frames)
+        n = len(frames)
+        if n == 0:
+            raise ValueError("empty list of cameras")
+        for i, f in enumerate(frames):
+            if f is None:
+                continue
+            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[-1] != 3:
+                raise ValueError("frames must be uint8 arrays of shape [H,W,3] (BGR, as cv2 delivers them), or None for an absent camera")
+            if not f.flags.c_contiguous:
+                frames[i] = np.ascontiguousarray(f)
+        cams = getattr(self, "_cameras", None)
+        if persist and cams is not None and len(cams[0]) != n:
+            raise ValueError(f"{n} frames for {len(cams[0])} tracked cameras: the list length is the number of cameras (None = absent)")
+        if cams is None or not persist:
+            # one BoT-SORT core per camera, stepped with the warp of the shared motion-compensation object (on the engine's GPU)
+            cams = self._cameras = ([BYTETracker(gmc_method=None) for _ in range(n)], MultiGMC(n, device=self.device))
+        trackers, gmc = cams
+        present = [i for i, f in enumerate(frames) if f is not None]
+        out: List[Optional[Results]] = [None] * n
+        if not present:
+            return out
+        # the tick's motion compensation (all cameras: frame preparation + optical flow, one launch per stage on a stream of its own) is
+        # enqueued before the detector pass, which reads the frames that step has just uploaded; RANSAC runs on host threads meanwhile
+        gmc.begin(frames)
+        share = os.environ.get("MI355_TRACK_SHARED_FRAME", "1") != "0"                # A/B and tests only
+        originals = [frames[i] for i in present]
+        try:
+            dev = gmc.pending_device_frames() if share else None
+            if dev is not None and any(dev[i] is None for i in present):
+                raise RuntimeError("track_cameras: the motion compensation's pending tick is not this call's")
+        except BaseException:
+            gmc.reset()
+            raise
+        if dev is not None:
+            batch = YOLO._RaggedDevice([dev[i] for i in present], [f.shape[:2] for f in originals])
+        else:
+            batch = YOLO._Ragged(originals, False)
+        imgsz = kwargs.get("imgsz", 640)
+        try:
+            res = self._predict_batch(batch, originals, conf, kwargs.get("iou", 0.7), kwargs.get("classes"), kwargs.get("max_det", 300),
+                                      int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"))
+        except BaseException:
+            gmc.reset()                                          # the enqueued tick must not be taken for the next call's frames
+            raise
+        warps = gmc.apply(frames)
+        for r, i in zip(res, present):
+            out[i] = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i]))    # an empty frame still steps
+        return out
 
     # ------------------------------------------------------------------------------------------ test hooks
     def raw_head(self, source, imgsz: int = 640, half: Optional[bool] = None) -> np.ndarray:

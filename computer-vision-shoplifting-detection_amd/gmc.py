@@ -296,3 +296,130 @@ class GMC:
         if rc != 0:
             raise ValueError(f"mi355_gmc_track_finish: error {rc}")
         return self._H.copy()
+
+
+# ------------------------------------------------------------------------------------------------- several cameras, one step per tick
+class MultiGMC:
+    """``n_cameras`` independent :class:`GMC` states stepped together: ``apply(frames) -> float64 [n_cameras, 2, 3]`` where ``frames[i]`` is
+    camera i's BGR frame of this tick (any size, each camera its own) or None when it delivered none -- the identity for that camera, whose
+    state stays as it is, and for every camera's first frame.
+
+    ``device=k``: one launch per stage for all present cameras (descriptor-driven kernels of csrc/gmc_kernels.hip, ``mi355_gmc_multi_*``), one
+    upload of the tick's frames, corner ordering and RANSAC per camera on host threads.  :meth:`begin` enqueues, :meth:`apply` collects;
+    between the two :meth:`pending_device_frames` hands the uploaded frames to the detector pass of the same tick (``YOLO.track_cameras``).
+    ``device=None``: every stage in host C++.  Either way each camera's matrices, previous plane and corners are bit for bit those of a
+    :class:`GMC` object of its own."""
+
+    def __init__(self, n_cameras: int, method: Optional[str] = "sparseOptFlow", downscale: int = 2, device: Optional[int] = None):
+        if int(n_cameras) <= 0:
+            raise ValueError("MultiGMC needs at least one camera")
+        self.n, self.device = int(n_cameras), device
+        if method in ("none", "None"):
+            method = None
+        if method not in (None, "sparseOptFlow"):
+            raise ValueError(f"GMC method {method!r} is not implemented (sparseOptFlow, the botsort.yaml default, or None)")
+        self.method, self.downscale = method, max(1, int(downscale))
+        self._h = None                         # mi355_gmc_multi object, created by the first tick
+        self._pending = None                   # the frames of the enqueued tick (kept alive; identity decides whether apply collects it)
+        self._H = np.empty((self.n, 2, 3), np.float64)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and h.value:
+            try:
+                _lib.lib().mi355_gmc_multi_destroy(h)
+            except Exception:
+                pass
+
+    def _obj(self):
+        if self._h is None:
+            h = C.c_void_p()
+            rc = _lib.lib().mi355_gmc_multi_create(-1 if self.device is None else int(self.device), self.n, C.byref(h))
+            if rc != 0:
+                raise RuntimeError(f"mi355_gmc_multi_create: error {rc} on device {self.device}")
+            self._h = h
+        return self._h
+
+    def _check(self, frames) -> None:
+        if len(frames) != self.n:
+            raise ValueError(f"MultiGMC({self.n}) takes a list of {self.n} frames (None = camera absent), got {len(frames)}")
+        for f in frames:
+            if f is not None and (not isinstance(f, np.ndarray) or f.ndim != 3 or f.shape[2] != 3):
+                raise ValueError("MultiGMC takes BGR frames [H, W, 3] (or None)")
+
+    def reset(self, camera: Optional[int] = None) -> None:
+        """Forget the previous frame of ``camera`` (None: of every camera); an enqueued tick is dropped."""
+        if camera is not None and not 0 <= int(camera) < self.n:
+            raise ValueError(f"camera {camera} out of range")
+        if self._h is not None:
+            _lib.lib().mi355_gmc_multi_reset(self._h, -1 if camera is None else int(camera))
+        self._pending = None
+
+    # ---- a camera's previous frame as the object holds it (tests) -----------------------------------------------------------------
+    def _state(self, camera: int):
+        if not 0 <= int(camera) < self.n:
+            raise ValueError(f"camera {camera} out of range")
+        if self._h is None or self._pending is not None:
+            return None, None
+        oh, ow, n = C.c_int(), C.c_int(), C.c_int()
+        _lib.lib().mi355_gmc_multi_state(self._h, int(camera), C.byref(oh), C.byref(ow), C.byref(n), None, None, 0)
+        if oh.value == 0:
+            return None, None
+        gray, pts = np.empty((oh.value, ow.value), np.uint8), np.empty((max(n.value, 1), 2), np.float32)
+        _lib.lib().mi355_gmc_multi_state(self._h, int(camera), None, None, None, gray.ctypes.data, pts.ctypes.data, len(pts))
+        return gray, pts[:n.value]
+
+    def prev_frame(self, camera: int) -> Optional[np.ndarray]:
+        return self._state(camera)[0]
+
+    def prev_points(self, camera: int) -> Optional[np.ndarray]:
+        return self._state(camera)[1]
+
+    # ---- the tick -----------------------------------------------------------------------------------------------------------------
+    def begin(self, frames) -> None:
+        """Enqueue this tick; :meth:`apply` of the same list object collects it."""
+        given, frames = frames, (frames if isinstance(frames, list) else list(frames))
+        self._check(frames)
+        if self.method is None or self._pending is given:
+            return
+        if self._pending is not None:
+            self.reset()                                         # a tick enqueued for other frames and never collected: stale
+        keep = [None if f is None else (f if (f.dtype == np.uint8 and f.flags.c_contiguous) else np.ascontiguousarray(f, dtype=np.uint8)) for f in frames]
+        ptrs = (C.c_void_p * self.n)(*[None if f is None else f.ctypes.data for f in keep])
+        hs = np.array([0 if f is None else f.shape[0] for f in keep], np.int32)
+        ws = np.array([0 if f is None else f.shape[1] for f in keep], np.int32)
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        rc = _lib.lib().mi355_gmc_multi_begin(self._obj(), ptrs, i32(hs), i32(ws), self.downscale)
+        if rc == -2:
+            raise RuntimeError(f"mi355_gmc_multi_begin: HIP error on device {self.device}")
+        if rc != 0:
+            raise ValueError(f"mi355_gmc_multi_begin: error {rc}")
+        self._pending = given
+
+    def pending_device_frames(self):
+        """Per camera the device pointer of the frame :meth:`begin` has just uploaded (dense BGR uint8 on this object's GPU, valid until the
+        next :meth:`begin`), None for an absent camera -- or None altogether (host object, nothing pending)."""
+        if self.method is None or self._pending is None or self.device is None:
+            return None
+        ptrs = (C.c_void_p * self.n)()
+        rc = _lib.lib().mi355_gmc_multi_frames(self._obj(), ptrs)
+        if rc == -2:
+            raise RuntimeError(f"mi355_gmc_multi_frames: HIP error on device {self.device}")
+        return [p if p else None for p in ptrs] if rc == 0 else None
+
+    def apply(self, frames) -> np.ndarray:
+        self._check(frames if isinstance(frames, list) else list(frames))
+        if self.method is None:
+            return np.tile(np.eye(2, 3), (self.n, 1, 1))
+        if self._pending is not None and self._pending is not frames:
+            self.reset()                                         # a tick enqueued for other frames: its results are stale
+        if self._pending is None:
+            self.begin(frames)
+        self._pending = None
+        self._H[:] = np.eye(2, 3)
+        rc = _lib.lib().mi355_gmc_multi_finish(self._h, self._H.ctypes.data)
+        if rc == -2:
+            raise RuntimeError(f"mi355_gmc_multi_finish: HIP error on device {self.device}")
+        if rc != 0:
+            raise ValueError(f"mi355_gmc_multi_finish: error {rc}")
+        return self._H.copy()

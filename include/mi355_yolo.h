@@ -364,6 +364,26 @@ int  mi355_gmc_batch_frames(mi355_gmc* g, unsigned long long after_seq, int time
                             long long* stride);
 int  mi355_gmc_track_reset(mi355_gmc* g);
 int  mi355_gmc_track_state(const mi355_gmc* g, int* oh, int* ow, int* n_pts, uint8_t* gray_out, float* pts_out, int pts_cap);
+/* Several cameras, one motion-compensation step per tick (csrc/gmc_kernels.hip): n_cameras independent GMC states in one object.  A tick is
+ * ONE launch per stage for all cameras that delivered a frame, whatever their sizes (per-camera descriptors on the device, uploaded only
+ * when their bytes change; the tick's frames staged in pinned memory and uploaded once); every camera's 2 x 3 matrix, previous plane and
+ * corners are bit for bit those of a mi355_gmc object of its own fed the same frames.  device -1: every stage in host C++, no GPU touched.
+ *   begin   frames[i] = camera i's BGR frame [heights[i]][widths[i]][3], NULL = camera absent this tick (its state is kept); enqueues on the
+ *           object's stream and returns; corner ordering + RANSAC per camera run on at most min(present, 8) worker threads from then on
+ *   finish  joins them; H_out [n_cameras][6], rows of absent cameras untouched.  Every begin is followed by exactly one finish.
+ *   frames  the pending tick's frames on the device (dense BGR, 256-byte aligned starts; NULL = absent) after one event wait: the detector
+ *           pass of the tick reads them in place (mi355_yolo_infer_multi, frames_on_device = 1).  Valid until the next begin.
+ *   reset   forgets camera `camera`'s previous frame (-1: all).  A camera whose frame size changes restarts like a mi355_gmc object.
+ *   state   camera's previous frame as held (tests), as mi355_gmc_track_state.
+ * 0 = ok, -1 = bad argument or call out of order, -2 = HIP error. */
+typedef struct mi355_gmc_multi mi355_gmc_multi;
+int  mi355_gmc_multi_create(int device, int n_cameras, mi355_gmc_multi** out);
+void mi355_gmc_multi_destroy(mi355_gmc_multi* g);
+int  mi355_gmc_multi_begin(mi355_gmc_multi* g, const uint8_t* const* frames, const int* heights, const int* widths, int downscale);
+int  mi355_gmc_multi_finish(mi355_gmc_multi* g, double* H_out);
+int  mi355_gmc_multi_frames(mi355_gmc_multi* g, const uint8_t** dev_frames);
+int  mi355_gmc_multi_reset(mi355_gmc_multi* g, int camera);
+int  mi355_gmc_multi_state(const mi355_gmc_multi* g, int camera, int* oh, int* ow, int* n_pts, uint8_t* gray_out, float* pts_out, int pts_cap);
 /* Depthwise 3x3 conv (stride 1, pad 1) + bias (+SiLU) (+residual) on channel views, fp32, as the engine runs YOLO11's
  * DWConv and Attention.pe (ultralytics nn/modules/conv.py:DWConv, Conv with groups = c).  x[n][h][w][x_cs] holds the input view at
  * channels x_off .. x_off+c-1; residual (or NULL) [n][h][w][res_cs] at res_off; y[n][h][w][y_cs] is read in, its view y_off ..
