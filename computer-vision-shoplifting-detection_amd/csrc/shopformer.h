@@ -48,4 +48,22 @@ const char* launch_shopformer(const SfParams* p_dev, int group, const float* win
 const char* launch_shopformer2(const SfParams* p_dev, int group, int group_tf, int lds_tok, int lds_tf, const float* windows, int n,
                                float* tokens, float* scores, float* token_scores, float* recon, hipStream_t stream, long long* launches);
 
+// ---- the GCAE decoder (version-3 images): its own parameter block and its own launch (shopformer_decoder.hip)
+struct SfDecParams {
+    int V, T, H, L, ntok, Din;
+    int f[4];                              // upsample factor of each layer (1 = 1x1 convolution, 2 = (2,1)/(2,1) transposed convolution)
+    int Td, interp;                        // frames the layers emit = ntok * f0 * f1 * f2 * f3; Td != T: linear interpolation along time
+    float scale;                           // (float)Td / (float)T, the source-index scale of align_corners=False
+    int G;                                 // windows per workgroup: G * ntok rows of initial_proj
+    int csT, csH;                          // LDS row strides (floats), each 4 * odd
+    int offTok, offX, offOut;              // LDS regions (floats): tokens, initial_proj's output, the layers' output frames
+    const float *ipw, *ipb;                // initial_proj, output features permuted to (joint, channel) order; packed / padded to 16
+    const float *w[4], *b[4];              // layer matrices [out][parity][in] packed, folded BatchNorm in them and in the bias
+};
+
+const char* prepare_shopformer_decoder_device();
+// one launch: tokens [n][ntok][Din] -> poses [n][2][T][V]; pose_error [n][T][V] when both it and `windows` [n][2][T][V] are given
+const char* launch_shopformer_decoder(const SfDecParams* p_dev, int group, int lds_bytes, const float* tokens, int n, float* poses,
+                                      float* pose_error, const float* windows, hipStream_t stream, long long* launches);
+
 }  // namespace mi355

@@ -1,10 +1,12 @@
 // Shopformer score path, host side: parse the weight image (cvsd_amd/shopformer.py:build_image), upload it, plan LDS, and the C ABI
 // mi355_shopformer_* of include/mi355_yolo.h.  One kernel launch per call whatever the number of windows for variant 1, two for variant 2
 // (version-2 images): tokenizer, then the transformer over row groups of up to 16 windows (shopformer_kernels.hip).
+// Version-3 images hold either variant plus the GCAE decoder: one more launch (shopformer_decoder.hip), only when asked.
 #include "engine_internal.h"
 #include "shopformer.h"
 
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -25,10 +27,19 @@ struct mi355_shopformer {
     hipStream_t stream = nullptr;
     long long n_params = 0, macs = 0;
     int lds_bytes = 0;
+    // the GCAE decoder (version-3 images)
+    bool has_dec = false;
+    SfDecParams dp{};
+    SfDecParams* d_dec = nullptr;
+    int lds_dec = 0;
+    long long macs_dec = 0;
+    float *d_pose = nullptr, *d_perr = nullptr;
+    size_t cap_dec = 0;                 // windows d_pose / d_perr hold
     ~mi355_shopformer() {
         if (d_weights) (void)hipFree(d_weights);
         if (d_params) (void)hipFree(d_params);
-        for (float* q : {d_win, d_score, d_tok, d_rec, d_tsc, d_tok_scratch}) if (q) (void)hipFree(q);
+        if (d_dec) (void)hipFree(d_dec);
+        for (float* q : {d_win, d_score, d_tok, d_rec, d_tsc, d_tok_scratch, d_pose, d_perr}) if (q) (void)hipFree(q);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -39,6 +50,8 @@ struct Entry { uint32_t kind, d[3]; uint64_t off, count; };
 const char* kCfg[] = {"V", "T", "H", "L", "heads", "layers", "ff", "D", "ntok", "nnz", "s0", "s1", "s2", "s3", "T1", "T2", "T3", "T4"};
 constexpr int kNCfg = 18;
 constexpr int kNCfg2 = 24;             // version 2: + variant, Din, in_proj, out_proj, norm_kind, act_kind
+constexpr int kNCfg3 = 30;             // version 3: + the decoder's four factors, the frames its layers emit, the interpolation flag
+const char* kNoDecoder = "this Shopformer weight image was built without the decoder (build it with decoder=True)";
 
 int pad_stride(int k) { int c = (k + 3) / 4 * 4; if (((c / 4) & 1) == 0) c += 4; return c; }   // 4 * odd
 
@@ -49,12 +62,13 @@ int create_impl_sf(const uint8_t* blob, size_t nbytes, int device, mi355_shopfor
     if (nbytes < 24 || std::memcmp(blob, "MI355SF1", 8) != 0) return fail(MI355_EFORMAT, "not a Shopformer weight image (bad magic)");
     uint32_t ver, ncfg;
     std::memcpy(&ver, blob + 8, 4); std::memcpy(&ncfg, blob + 12, 4);
-    if (!((ver == 1 && ncfg == kNCfg) || (ver == 2 && ncfg == kNCfg2))) return fail(MI355_EFORMAT, "unsupported Shopformer weight image version");
+    if (!((ver == 1 && ncfg == kNCfg) || (ver == 2 && ncfg == kNCfg2) || (ver == 3 && ncfg == kNCfg3))) return fail(MI355_EFORMAT, "unsupported Shopformer weight image version");
     size_t pos = 16;
-    int cfg[kNCfg2] = {0};
+    int cfg[kNCfg3] = {0};
     if (nbytes < pos + 4 * ncfg + 4) return fail(MI355_EFORMAT, "truncated Shopformer weight image");
     std::memcpy(cfg, blob + pos, 4 * ncfg); pos += 4 * ncfg;
-    const bool v2 = ver == 2;
+    const bool v2 = ver == 2 || (ver == 3 && cfg[18] == 2);
+    const bool dec = ver == 3;
     uint32_t nent; std::memcpy(&nent, blob + pos, 4); pos += 4;
     const size_t rec = 32 + 4 + 12 + 16;
     if (nent > 4096 || nbytes < pos + nent * rec) return fail(MI355_EFORMAT, "truncated Shopformer weight image");
@@ -82,6 +96,8 @@ int create_impl_sf(const uint8_t* blob, size_t nbytes, int device, mi355_shopfor
     if (!in_set(p.T, {12, 24})) return bad("seq_len", p.T);
     if (!in_set(p.H, {32, 64})) return bad("hidden_channels", p.H);
     if (!in_set(p.L, {4, 8})) return bad("latent_channels", p.L);
+    if (dec && cfg[18] != 1 && cfg[18] != 2) return bad("variant", cfg[18]);
+    if (dec && !v2 && (cfg[19] != p.D || cfg[20] || cfg[21] || cfg[22] != 0 || cfg[23] != 0)) return bad("variant-1 field in a version-3 image", cfg[19]);
     p.variant = v2 ? cfg[18] : 1; p.Din = v2 ? cfg[19] : p.D; p.in_proj = v2 ? cfg[20] : 0; p.out_proj = v2 ? cfg[21] : 0;
     if (v2) {
         if (p.variant != 2) return bad("variant", p.variant);
@@ -141,6 +157,41 @@ int create_impl_sf(const uint8_t* blob, size_t nbytes, int device, mi355_shopfor
         p.GT = GT; p.offTgt = o[0]; p.offX = o[1]; p.offNb = o[2]; p.offU = o[3]; p.offSc = o[4];
     }
 
+    if (dec) {
+        // the decoder's envelope: factors 1 or 2, a 1x1 last layer, the frame count they imply, at most the window's length
+        SfDecParams& d = h->dp;
+        d.V = p.V; d.T = p.T; d.H = p.H; d.L = p.L; d.ntok = p.ntok; d.Din = p.L * p.V;
+        int frames = p.ntok;
+        for (int i = 0; i < 4; ++i) {
+            d.f[i] = cfg[24 + i];
+            if (!in_set(d.f[i], {1, 2}) || (i == 3 && d.f[i] != 1)) return bad("decoder upsample factor", d.f[i]);
+            frames *= d.f[i];
+        }
+        d.Td = cfg[28]; d.interp = cfg[29];
+        if (d.Td != frames || d.Td > p.T) return bad("decoder frame count", d.Td);
+        if (d.interp != (d.Td != p.T ? 1 : 0)) return bad("decoder interpolation flag", d.interp);
+        if ((p.V * p.H) % 32) return bad("decoder initial_proj width", p.V * p.H);
+        d.scale = (float)d.Td / (float)p.T;
+        d.csT = pad_stride(d.Din); d.csH = pad_stride(p.H);
+        // row group: G windows = G * ntok rows of initial_proj.  4 windows (8 or 12 rows of the 16-row tile) measured fastest: two
+        // workgroups fit a CU's LDS, which gains more than the full tile of 5 or 8 windows
+        auto plan_dec = [&](int G) {
+            d.offTok = 0; d.offX = G * p.ntok * d.csT; d.offOut = d.offX + G * p.ntok * p.V * d.csH;
+            return (d.offOut + (G * 2 * d.Td * p.V + 3) / 4 * 4) * 4;
+        };
+        int G = 4;
+        if (const char* e = std::getenv("MI355_SFD_ROW_GROUP")) {      // kernel experiments (row-group A/B of DESIGN.md 3.11); the product never sets it
+            const int g = std::atoi(e);
+            if (g >= 1 && g <= 32) G = g;
+        }
+        while (G > 1 && plan_dec(G) > SF_LDS_BYTES) --G;
+        if (plan_dec(G) > SF_LDS_BYTES) return fail(MI355_EFORMAT, "Shopformer weight image: one window's decoder rows do not fit the 160 KiB of LDS");
+        d.G = G; h->lds_dec = plan_dec(G); h->has_dec = true;
+        long long rows = p.ntok, m = (long long)p.ntok * d.Din * p.H * p.V;
+        for (int i = 0; i < 4; ++i) { rows *= d.f[i]; m += rows * p.V * p.H * (i == 3 ? 2 : p.H); }
+        h->macs_dec = m;
+    }
+
     // adjacency columns must stay inside a pose (they index LDS rows)
     const float* data = (const float*)(blob + pos);
     bool missing = false; std::string miss;
@@ -197,6 +248,14 @@ int create_impl_sf(const uint8_t* blob, size_t nbytes, int device, mi355_shopfor
     } else {
         p.proj = lin("proj", p.D, p.D);
     }
+    if (dec) {
+        SfDecParams& d = h->dp;
+        d.ipw = packed("dec.ip.w", p.V * p.H, 1, d.Din); d.ipb = plain("dec.ip.b", p.V * p.H);
+        for (int i = 0; i < 4; ++i) {
+            const std::string n = "dec.l" + std::to_string(i);
+            d.w[i] = packed(n + ".w", i == 3 ? 2 : p.H, d.f[i], p.H); d.b[i] = plain(n + ".b", i == 3 ? 2 : p.H);
+        }
+    }
     };
     bind();
     if (missing) return fail(MI355_EFORMAT, "Shopformer weight image: tensor '" + miss + "' is missing or has the wrong shape");
@@ -206,6 +265,7 @@ int create_impl_sf(const uint8_t* blob, size_t nbytes, int device, mi355_shopfor
     h->device = device;
     HIPCHK(hipSetDevice(device));
     KCHK(prepare_shopformer_device());
+    if (dec) KCHK(prepare_shopformer_decoder_device());
     HIPCHK(hipMalloc(&h->d_weights, std::max<size_t>(nfloats, 4) * 4));
     HIPCHK(hipMemcpy(h->d_weights, data, nfloats * 4, hipMemcpyHostToDevice));
     HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -223,6 +283,10 @@ int create_impl_sf(const uint8_t* blob, size_t nbytes, int device, mi355_shopfor
     h->macs = macs;
     HIPCHK(hipMalloc(&h->d_params, sizeof(SfParams)));
     HIPCHK(hipMemcpy(h->d_params, &p, sizeof(SfParams), hipMemcpyHostToDevice));
+    if (dec) {
+        HIPCHK(hipMalloc(&h->d_dec, sizeof(SfDecParams)));
+        HIPCHK(hipMemcpy(h->d_dec, &h->dp, sizeof(SfDecParams), hipMemcpyHostToDevice));
+    }
     *out = h.release();
     return MI355_OK;
 }
@@ -240,6 +304,28 @@ int ensure_cap(mi355_shopformer* h, size_t n) {
     h->cap = n;
     return MI355_OK;
 }
+
+int ensure_cap_dec(mi355_shopformer* h, size_t n) {
+    if (n <= h->cap_dec) return MI355_OK;
+    for (float** q : {&h->d_pose, &h->d_perr}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    h->cap_dec = 0;
+    const SfParams& p = h->p;
+    HIPCHK(hipMalloc(&h->d_pose, n * 2 * p.T * p.V * 4));
+    HIPCHK(hipMalloc(&h->d_perr, n * p.T * p.V * 4));
+    h->cap_dec = n;
+    return MI355_OK;
+}
+
+// device / async calls without a tokens output: the handle's scratch, grown here
+int ensure_scratch(mi355_shopformer* h, size_t n) {
+    if (n <= h->scratch_cap) return MI355_OK;
+    if (h->d_tok_scratch) { (void)hipFree(h->d_tok_scratch); h->d_tok_scratch = nullptr; h->scratch_cap = 0; }
+    HIPCHK(hipMalloc(&h->d_tok_scratch, n * h->p.ntok * h->p.Din * 4));
+    h->scratch_cap = n;
+    return MI355_OK;
+}
+
+constexpr int kOutputsOld = (int)offsetof(mi355_shopformer_outputs_t, poses);      // the struct before the decoder's two pointers
 
 }  // namespace
 
@@ -262,10 +348,17 @@ int mi355_shopformer_info(const mi355_shopformer* h, mi355_shopformer_info_t* in
     return MI355_OK;
 }
 
-static int outputs_ok(const mi355_shopformer* h, const mi355_shopformer_outputs_t* o) {
-    if (!o || o->struct_size != (int)sizeof(mi355_shopformer_outputs_t)) return fail(MI355_EINVAL, "mi355_shopformer_outputs_t: null or struct_size is not sizeof");
-    if (!o->scores && !o->token_scores && !o->tokens && !o->recon) return fail(MI355_EINVAL, "mi355_shopformer_outputs_t: every output pointer is null");
+// checks the caller's struct and copies it into the current layout: a caller compiled against the older, shorter struct has no
+// decoder outputs
+static int outputs_ok(const mi355_shopformer* h, const mi355_shopformer_outputs_t* in, mi355_shopformer_outputs_t* o) {
+    if (!in || (in->struct_size != (int)sizeof(mi355_shopformer_outputs_t) && in->struct_size != kOutputsOld))
+        return fail(MI355_EINVAL, "mi355_shopformer_outputs_t: null or struct_size is not sizeof");
+    std::memset(o, 0, sizeof(*o));
+    std::memcpy(o, in, (size_t)in->struct_size);
+    if (!o->scores && !o->token_scores && !o->tokens && !o->recon && !o->poses && !o->pose_error) return fail(MI355_EINVAL, "mi355_shopformer_outputs_t: every output pointer is null");
     if (o->token_scores && h->p.variant != 2) return fail(MI355_EINVAL, "token_scores exist only for the shopformer_2 variant (version-2 images)");
+    if ((o->poses || o->pose_error) && !h->has_dec) return fail(MI355_EINVAL, kNoDecoder);
+    if (o->pose_error && !o->poses) return fail(MI355_EINVAL, "pose_error is written beside poses: set the poses output too");
     return MI355_OK;
 }
 
@@ -273,11 +366,7 @@ static int outputs_ok(const mi355_shopformer* h, const mi355_shopformer_outputs_
 static int run2_device(mi355_shopformer* h, const float* win, int n, float* scores, float* tsc, float* tok, float* rec, hipStream_t st) {
     const SfParams& p = h->p;
     if (!tok) {
-        if ((size_t)n > h->scratch_cap) {
-            if (h->d_tok_scratch) { (void)hipFree(h->d_tok_scratch); h->d_tok_scratch = nullptr; h->scratch_cap = 0; }
-            HIPCHK(hipMalloc(&h->d_tok_scratch, (size_t)n * p.ntok * p.Din * 4));
-            h->scratch_cap = (size_t)n;
-        }
+        const int rc = ensure_scratch(h, (size_t)n); if (rc) return rc;
         tok = h->d_tok_scratch;
     }
     KCHK(launch_shopformer2(h->d_params, p.G, p.GT, h->lds_bytes, h->lds_tf, win, n, tok, scores, tsc, rec, st, &h->launches));
@@ -287,32 +376,51 @@ static int run2_device(mi355_shopformer* h, const float* win, int n, float* scor
 int mi355_shopformer_score_ex_device_async(mi355_shopformer* h, const float* windows_dev, int n, const mi355_shopformer_outputs_t* out,
                                            void* stream) {
     if (!h || n < 0 || (n > 0 && !windows_dev)) return fail(MI355_EINVAL, "null argument or negative count");
-    int rc = outputs_ok(h, out); if (rc) return rc;
+    mi355_shopformer_outputs_t o;
+    int rc = outputs_ok(h, out, &o); if (rc) return rc;
     if (n == 0) return MI355_OK;
-    if (h->p.variant != 2) {
-        if (!out->scores) return fail(MI355_EINVAL, "the shopformer/ variant needs the scores output");
-        return mi355_shopformer_score_device_async(h, windows_dev, n, out->scores, out->tokens, out->recon, stream);
+    if (h->p.variant != 2 && !o.scores) return fail(MI355_EINVAL, "the shopformer/ variant needs the scores output");
+    if (o.poses) {                      // the score path into a tokens buffer, then the decoder's one launch on it
+        HIPCHK(hipSetDevice(h->device));
+        float* tok = o.tokens;
+        if (!tok) { rc = ensure_scratch(h, (size_t)n); if (rc) return rc; tok = h->d_tok_scratch; }
+        if (h->p.variant == 2) { rc = run2_device(h, windows_dev, n, o.scores, o.token_scores, tok, o.recon, (hipStream_t)stream); if (rc) return rc; }
+        else KCHK(launch_shopformer(h->d_params, h->p.G, windows_dev, n, o.scores, tok, o.recon, (hipStream_t)stream, &h->launches));
+        KCHK(launch_shopformer_decoder(h->d_dec, h->dp.G, h->lds_dec, tok, n, o.poses, o.pose_error, windows_dev, (hipStream_t)stream, &h->launches));
+        return MI355_OK;
     }
+    if (h->p.variant != 2) return mi355_shopformer_score_device_async(h, windows_dev, n, o.scores, o.tokens, o.recon, stream);
     HIPCHK(hipSetDevice(h->device));
-    return run2_device(h, windows_dev, n, out->scores, out->token_scores, out->tokens, out->recon, (hipStream_t)stream);
+    return run2_device(h, windows_dev, n, o.scores, o.token_scores, o.tokens, o.recon, (hipStream_t)stream);
 }
 
 int mi355_shopformer_score_ex(mi355_shopformer* h, const float* windows, int n, const mi355_shopformer_outputs_t* out) {
     if (!h || n < 0 || (n > 0 && !windows)) return fail(MI355_EINVAL, "null argument or negative count");
-    int rc = outputs_ok(h, out); if (rc) return rc;
+    mi355_shopformer_outputs_t full;
+    int rc = outputs_ok(h, out, &full); if (rc) return rc;
+    out = &full;
     if (n == 0) return MI355_OK;
-    if (h->p.variant != 2) {
-        if (!out->scores) return fail(MI355_EINVAL, "the shopformer/ variant needs the scores output");
-        return mi355_shopformer_score(h, windows, n, out->scores, out->tokens, out->recon);
-    }
+    if (h->p.variant != 2 && !out->scores) return fail(MI355_EINVAL, "the shopformer/ variant needs the scores output");
+    if (h->p.variant != 2 && !out->poses) return mi355_shopformer_score(h, windows, n, out->scores, out->tokens, out->recon);
     HIPCHK(hipSetDevice(h->device));
     rc = ensure_cap(h, (size_t)n); if (rc) return rc;
+    if (out->poses) { rc = ensure_cap_dec(h, (size_t)n); if (rc) return rc; }
     const SfParams& p = h->p;
     const size_t per = (size_t)p.ntok * p.Din * 4;
     HIPCHK(hipMemcpyAsync(h->d_win, windows, (size_t)n * 2 * p.T * p.V * 4, hipMemcpyHostToDevice, h->stream));
-    rc = run2_device(h, h->d_win, n, out->scores ? h->d_score : nullptr, out->token_scores ? h->d_tsc : nullptr, h->d_tok,
-                     out->recon ? h->d_rec : nullptr, h->stream);
-    if (rc) return rc;
+    if (p.variant == 2) {
+        rc = run2_device(h, h->d_win, n, out->scores ? h->d_score : nullptr, out->token_scores ? h->d_tsc : nullptr, h->d_tok,
+                         out->recon ? h->d_rec : nullptr, h->stream);
+        if (rc) return rc;
+    } else {
+        KCHK(launch_shopformer(h->d_params, p.G, h->d_win, n, h->d_score, h->d_tok, out->recon ? h->d_rec : nullptr, h->stream, &h->launches));
+    }
+    if (out->poses) {
+        KCHK(launch_shopformer_decoder(h->d_dec, h->dp.G, h->lds_dec, h->d_tok, n, h->d_pose, out->pose_error ? h->d_perr : nullptr, h->d_win,
+                                       h->stream, &h->launches));
+        HIPCHK(hipMemcpyAsync(out->poses, h->d_pose, (size_t)n * 2 * p.T * p.V * 4, hipMemcpyDeviceToHost, h->stream));
+        if (out->pose_error) HIPCHK(hipMemcpyAsync(out->pose_error, h->d_perr, (size_t)n * p.T * p.V * 4, hipMemcpyDeviceToHost, h->stream));
+    }
     if (out->scores) HIPCHK(hipMemcpyAsync(out->scores, h->d_score, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     if (out->token_scores) HIPCHK(hipMemcpyAsync(out->token_scores, h->d_tsc, (size_t)n * p.ntok * 4, hipMemcpyDeviceToHost, h->stream));
     if (out->tokens) HIPCHK(hipMemcpyAsync(out->tokens, h->d_tok, n * per, hipMemcpyDeviceToHost, h->stream));
@@ -349,6 +457,40 @@ int mi355_shopformer_score(mi355_shopformer* h, const float* windows, int n, flo
     if (tokens) HIPCHK(hipMemcpyAsync(tokens, h->d_tok, n * per, hipMemcpyDeviceToHost, h->stream));
     if (recon) HIPCHK(hipMemcpyAsync(recon, h->d_rec, n * per, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    return MI355_OK;
+}
+
+int mi355_shopformer_decode_device_async(mi355_shopformer* h, const float* tokens_dev, int n, float* poses_dev, void* stream) {
+    if (!h || n < 0 || (n > 0 && (!tokens_dev || !poses_dev))) return fail(MI355_EINVAL, "null argument or negative count");
+    if (!h->has_dec) return fail(MI355_EINVAL, kNoDecoder);
+    if (n == 0) return MI355_OK;
+    HIPCHK(hipSetDevice(h->device));
+    KCHK(launch_shopformer_decoder(h->d_dec, h->dp.G, h->lds_dec, tokens_dev, n, poses_dev, nullptr, nullptr, (hipStream_t)stream, &h->launches));
+    return MI355_OK;
+}
+
+int mi355_shopformer_decode(mi355_shopformer* h, const float* tokens, int n, float* poses) {
+    if (!h || n < 0 || (n > 0 && (!tokens || !poses))) return fail(MI355_EINVAL, "null argument or negative count");
+    if (!h->has_dec) return fail(MI355_EINVAL, kNoDecoder);
+    if (n == 0) return MI355_OK;
+    HIPCHK(hipSetDevice(h->device));
+    int rc = ensure_cap(h, (size_t)n); if (rc) return rc;
+    rc = ensure_cap_dec(h, (size_t)n); if (rc) return rc;
+    const SfParams& p = h->p;
+    HIPCHK(hipMemcpyAsync(h->d_tok, tokens, (size_t)n * p.ntok * p.Din * 4, hipMemcpyHostToDevice, h->stream));
+    KCHK(launch_shopformer_decoder(h->d_dec, h->dp.G, h->lds_dec, h->d_tok, n, h->d_pose, nullptr, nullptr, h->stream, &h->launches));
+    HIPCHK(hipMemcpyAsync(poses, h->d_pose, (size_t)n * 2 * p.T * p.V * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MI355_OK;
+}
+
+int mi355_shopformer_decoder_info(const mi355_shopformer* h, mi355_shopformer_decoder_info_t* info) {
+    if (!h || !info) return fail(MI355_EINVAL, "null argument");
+    if (!h->has_dec) return fail(MI355_EINVAL, kNoDecoder);
+    std::memset(info, 0, sizeof(*info));
+    for (int i = 0; i < 4; ++i) info->factors[i] = h->dp.f[i];
+    info->frames = h->dp.Td; info->interpolate = h->dp.interp; info->group = h->dp.G; info->lds_bytes = h->lds_dec;
+    info->macs_per_window = h->macs_dec;
     return MI355_OK;
 }
 

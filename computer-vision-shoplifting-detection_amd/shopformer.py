@@ -3,11 +3,16 @@ fused HIP launch (csrc/shopformer_kernels.hip).
 
 Only what ``normality_score`` depends on is evaluated: ``bn_input`` -> 4 ST-GCN blocks -> tokens ``[N, 3, latent*V]`` -> positional
 encoding -> post-norm transformer encoder / decoder (no causal mask) -> ``output_proj`` -> mean squared error against
-``tokens + PE``.  The GCAE decoder is not part of the score and is not loaded.
+``tokens + PE``.  The GCAE decoder is not part of the score; it is loaded only when asked for (``decoder=True``, below).
 
 A second variant, the reference's ``shopformer_2/`` network (pre-norm ``nn.Transformer`` layers, erf GELU, two real tokens, optional
 input / output projection, per-token scores), is loaded by the same functions: a nested config dict with a ``model``
 key, or ``variant=2``, selects it.  It runs as two launches: the tokenizer, then the transformer over row groups of 16 windows.
+
+With ``decoder=True`` the loader also folds ``gcae.decoder.*`` (``initial_proj``, four (transposed) convolutions with their
+BatchNorms, linear interpolation along time when the layers emit fewer frames than ``seq_len``) into a version-3 image, and the
+model gains the reference's fourth output: ``forward(x, poses=True)`` adds ``gcae_reconstructed`` (``reconstructed_poses`` under
+``shopformer_2``'s name) and ``pose_error``, ``decode(tokens)`` runs the decoder alone; one more HIP launch.
 
 This module holds (a) the loader: reference-named state dict -> folded tensors -> a small self-describing weight image whose
 matrices are already in the kernel's MFMA fragment order, (b) ``Shopformer``, the ctypes front of ``mi355_shopformer_*``, and (c) the
@@ -47,6 +52,56 @@ SUPPORTED_2 = {"num_keypoints": (17, 18), "seq_len": (12, 24), "gcae.hidden_chan
                "num_tokens": (2,), "in_channels": (2,), "gcae.num_layers": (4,), "transformer.num_layers": (1, 2, 3, 4)}
 MAX_FF_2, MAX_D_MODEL_2 = 512, 144
 KIND_PLAIN, KIND_PACKED = 0, 1
+# version-3 images: either variant plus its GCAE decoder; all of a version-2 header's ints (variant 1: variant = 1, Din = D, no
+# projections, post-norm, ReLU) and six more: the decoder's four upsample factors, the frames its layers emit, the interpolation flag
+IMAGE_VERSION_3 = 3
+CFG_FIELDS_V3 = CFG_FIELDS_V2 + ("u0", "u1", "u2", "u3", "Tdec", "interp")
+N_DEC_LAYERS = 4
+
+
+def decoder_factors(num_tokens: int, seq_len: int, num_layers: int = N_DEC_LAYERS) -> List[int]:
+    """the decoder's upsample rule: from the CONFIG's ``num_tokens`` (not the token count the encoder really emits), double per layer
+    while the doubled length still fits ``seq_len``.  2 -> 12: [2, 2, 1, 1]; 2 -> 24: [2, 2, 2, 1]"""
+    f, cur = [1] * num_layers, num_tokens
+    for i in range(num_layers):
+        if cur >= seq_len:
+            break
+        if cur * 2 <= seq_len:
+            f[i], cur = 2, cur * 2
+    return f
+
+
+def _fold_decoder(sd, need, t: Dict[str, np.ndarray], geo: dict, num_tokens: int) -> None:
+    """``gcae.decoder.*`` into ``t`` and the six decoder ints into ``geo``.  ``dec.ip``: initial_proj with its output features
+    reordered from (channel, joint) to (joint, channel), so that a (window, token) row of its output is V rows of H channels;
+    ``dec.l{i}.w``: [out, parity, in], the BatchNorm behind the layer folded in (float64); the last layer has 2 outputs and no norm."""
+    V, T, H, L, ntok = geo["V"], geo["T"], geo["H"], geo["L"], geo["ntok"]
+    f = decoder_factors(num_tokens, T)
+    frames = ntok * int(np.prod(f))
+    if f[-1] != 1 or frames > T:
+        raise ValueError(f"Shopformer decoder: upsample factors {f} on {ntok} tokens give {frames} frames for seq_len = {T}; a last layer "
+                         f"that upsamples and more frames than seq_len are not supported")
+    dec = "gcae.decoder."
+    w = need(dec + "initial_proj.weight", (H * V, L * V)).reshape(H, V, L * V).transpose(1, 0, 2)
+    t["dec.ip.w"] = w.reshape(V * H, 1, L * V)
+    t["dec.ip.b"] = need(dec + "initial_proj.bias", (H * V,)).reshape(H, V).T.reshape(-1)
+    for i in range(N_DEC_LAYERS):
+        co, p = (H if i < N_DEC_LAYERS - 1 else 2), f"{dec}layers.{4 * i}."
+        if f[i] > 1:
+            w = need(p + "weight", (H, co, f[i], 1))[..., 0].transpose(1, 2, 0)              # ConvTranspose2d [in, out, k, 1] -> [out, k, in]
+        else:
+            w = need(p + "weight", (co, H, 1, 1))[:, :, 0, 0].reshape(co, 1, H)
+        b = need(p + "bias", (co,))
+        if i < N_DEC_LAYERS - 1:
+            need(f"{dec}layers.{4 * i + 1}.weight", (co,))
+            for k in ("bias", "running_mean", "running_var"):
+                need(f"{dec}layers.{4 * i + 1}.{k}", (co,))
+            g, sh = _bn(sd, f"{dec}layers.{4 * i + 1}")
+            w, b = w * g[:, None, None], b * g + sh
+        t[f"dec.l{i}.w"], t[f"dec.l{i}.b"] = w, b
+    geo.update({"u0": f[0], "u1": f[1], "u2": f[2], "u3": f[3], "Tdec": frames, "interp": int(frames != T)})
+    if "variant" not in geo:
+        geo.update({"variant": 1, "Din": geo["D"], "in_proj": 0, "out_proj": 0, "norm_kind": NORM_POST, "act_kind": ACT_RELU})
 
 
 def resolve_config(config: Optional[dict]) -> dict:
@@ -196,14 +251,16 @@ def _fold_tokenizer(sd, need, t: Dict[str, np.ndarray], V: int, H: int, L: int, 
     return nnz
 
 
-def fold_state_dict(sd: Dict[str, np.ndarray], config: Optional[dict] = None, dtype=np.float32, variant: Optional[int] = None) -> Tuple[dict, Dict[str, np.ndarray]]:
+def fold_state_dict(sd: Dict[str, np.ndarray], config: Optional[dict] = None, dtype=np.float32, variant: Optional[int] = None,
+                    decoder: bool = False) -> Tuple[dict, Dict[str, np.ndarray]]:
     """reference state dict -> (geometry, logical folded tensors, float32; ``dtype=np.float64`` keeps the unrounded fold, for tests).  Every BatchNorm disappears into the scale/shift of the
     input or into the weights and bias of the conv in front of it (folded in float64, rounded once).  Matrices are [out, taps, in].
-    ``variant``: 1 = ``shopformer/``, 2 = ``shopformer_2/``, None = 2 when the config is the nested dict with a ``model`` key."""
+    ``variant``: 1 = ``shopformer/``, 2 = ``shopformer_2/``, None = 2 when the config is the nested dict with a ``model`` key.
+    ``decoder``: also fold ``gcae.decoder.*`` (the geometry then has the version-3 fields)."""
     if variant not in (None, 1, 2):
         raise ValueError(f"Shopformer variant must be 1 or 2, got {variant}")
     if variant == 2 or (variant is None and is_variant_2(config)):
-        return fold_state_dict_2(sd, config, dtype)
+        return fold_state_dict_2(sd, config, dtype, decoder)
     cfg = resolve_config(config)
     sd = _np_state(sd)
     V, T, H, L = cfg["num_keypoints"], cfg["seq_len"], cfg["hidden_channels"], cfg["latent_channels"]
@@ -254,10 +311,12 @@ def fold_state_dict(sd: Dict[str, np.ndarray], config: Optional[dict] = None, dt
     geo = {"V": V, "T": T, "H": H, "L": L, "heads": cfg["transformer_heads"], "layers": cfg["transformer_layers"], "ff": FF_DIM, "D": D,
            "ntok": ntok, "nnz": nnz, "s0": strides[0], "s1": strides[1], "s2": strides[2], "s3": strides[3],
            "T1": tn[1], "T2": tn[2], "T3": tn[3], "T4": tn[4]}
+    if decoder:
+        _fold_decoder(sd, need, t, geo, cfg["num_tokens"])
     return geo, {k: np.ascontiguousarray(v, dtype) for k, v in t.items()}
 
 
-def fold_state_dict_2(sd, config: dict, dtype=np.float32) -> Tuple[dict, Dict[str, np.ndarray]]:
+def fold_state_dict_2(sd, config: dict, dtype=np.float32, decoder: bool = False) -> Tuple[dict, Dict[str, np.ndarray]]:
     """the ``shopformer_2`` state dict (``gcae.*``, ``transformer.encoder.layers.N.*``, ``transformer.encoder.norm.*``, the decoder
     alike, ``transformer.input_projection.*`` / ``output_projection.*`` when input_dim != d_model) -> (geometry, folded tensors).
     Layer names in the image: e{N} / d{N} as in variant 1, ``en`` / ``dn`` the two final norms, ``inp`` / ``outp`` the projections."""
@@ -318,6 +377,8 @@ def fold_state_dict_2(sd, config: dict, dtype=np.float32) -> Tuple[dict, Dict[st
            "ntok": ntok, "nnz": nnz, "s0": strides[0], "s1": strides[1], "s2": strides[2], "s3": strides[3],
            "T1": tn[1], "T2": tn[2], "T3": tn[3], "T4": tn[4],
            "variant": 2, "Din": Din, "in_proj": int(proj), "out_proj": int(proj), "norm_kind": NORM_PRE, "act_kind": ACT_GELU_ERF}
+    if decoder:
+        _fold_decoder(sd, need, t, geo, cfg["num_tokens"])
     return geo, {k: np.ascontiguousarray(v, dtype) for k, v in t.items()}
 
 
@@ -360,6 +421,8 @@ def build_image(geo: dict, tensors: Dict[str, np.ndarray]) -> bytes:
         data.append(flat)
         off += len(flat)
     ver, fields = (IMAGE_VERSION_2, CFG_FIELDS_V2) if geo.get("variant", 1) == 2 else (IMAGE_VERSION, CFG_FIELDS)
+    if "Tdec" in geo:
+        ver, fields = IMAGE_VERSION_3, CFG_FIELDS_V3
     head = MAGIC + struct.pack("<II", ver, len(fields)) + struct.pack(f"<{len(fields)}i", *(geo[f] for f in fields))
     head += struct.pack("<I", len(entries))
     for name, kind, dims, o, n in entries:
@@ -373,7 +436,7 @@ def parse_image(blob: bytes) -> Tuple[dict, Dict[str, np.ndarray]]:
     if blob[:8] != MAGIC:
         raise ValueError("not a Shopformer weight image (bad magic)")
     ver, ncfg = struct.unpack_from("<II", blob, 8)
-    fields = {IMAGE_VERSION: CFG_FIELDS, IMAGE_VERSION_2: CFG_FIELDS_V2}.get(ver)
+    fields = {IMAGE_VERSION: CFG_FIELDS, IMAGE_VERSION_2: CFG_FIELDS_V2, IMAGE_VERSION_3: CFG_FIELDS_V3}.get(ver)
     if fields is None or ncfg != len(fields):
         raise ValueError(f"unsupported Shopformer weight image version {ver}")
     pos = 16
@@ -400,8 +463,9 @@ def parse_image(blob: bytes) -> Tuple[dict, Dict[str, np.ndarray]]:
     return geo, out
 
 
-def image_from_state_dict(sd, config: Optional[dict] = None, variant: Optional[int] = None) -> bytes:
-    return build_image(*fold_state_dict(sd, config, variant=variant))
+def image_from_state_dict(sd, config: Optional[dict] = None, variant: Optional[int] = None, decoder: bool = False) -> bytes:
+    """``decoder=False``: the version-1 / version-2 image of the score path; ``decoder=True``: a version-3 image with the GCAE decoder too"""
+    return build_image(*fold_state_dict(sd, config, variant=variant, decoder=decoder))
 
 
 def load_config_file(path) -> Optional[dict]:
@@ -428,7 +492,7 @@ def state_dict_from_checkpoint(ck: dict) -> dict:
     return ck
 
 
-def image_from_checkpoint(path: str, config=None, variant: Optional[int] = None) -> bytes:
+def image_from_checkpoint(path: str, config=None, variant: Optional[int] = None, decoder: bool = False) -> bytes:
     import torch
     ck = torch.load(path, map_location="cpu", weights_only=True)
     if config is None and isinstance(ck, dict) and is_variant_2(ck.get("config")):
@@ -437,7 +501,7 @@ def image_from_checkpoint(path: str, config=None, variant: Optional[int] = None)
         config = os.path.join(os.path.dirname(os.path.abspath(path)), "config.json")
     if isinstance(config, (str, os.PathLike)):
         config = load_config_file(config)
-    return image_from_state_dict(state_dict_from_checkpoint(ck), config, variant=variant)
+    return image_from_state_dict(state_dict_from_checkpoint(ck), config, variant=variant, decoder=decoder)
 
 
 # ---------------------------------------------------------------------------------------------- the model
@@ -451,11 +515,20 @@ class ShopformerInfo(C.Structure):
 class ShopformerOutputs(C.Structure):
     """mi355_shopformer_outputs_t: optional output pointers of the *_ex entry points (host or device, as the call takes them)"""
     _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int), ("scores", C.c_void_p), ("token_scores", C.c_void_p),
-                ("tokens", C.c_void_p), ("recon", C.c_void_p)]
+                ("tokens", C.c_void_p), ("recon", C.c_void_p), ("poses", C.c_void_p), ("pose_error", C.c_void_p)]
 
 
-def _outputs(scores=None, token_scores=None, tokens=None, recon=None) -> ShopformerOutputs:
-    return ShopformerOutputs(C.sizeof(ShopformerOutputs), 0, scores or None, token_scores or None, tokens or None, recon or None)
+class ShopformerDecoderInfo(C.Structure):
+    _fields_ = [("factors", C.c_int * 4), ("frames", C.c_int), ("interpolate", C.c_int), ("group", C.c_int), ("lds_bytes", C.c_int),
+                ("macs_per_window", C.c_longlong)]
+
+
+NO_DECODER = "this Shopformer model was loaded without the decoder (load it with decoder=True)"
+
+
+def _outputs(scores=None, token_scores=None, tokens=None, recon=None, poses=None, pose_error=None) -> ShopformerOutputs:
+    return ShopformerOutputs(C.sizeof(ShopformerOutputs), 0, scores or None, token_scores or None, tokens or None, recon or None,
+                             poses or None, pose_error or None)
 
 
 class Shopformer:
@@ -474,6 +547,10 @@ class Shopformer:
         self.variant = int(self.geometry.get("variant", 1))
         self.token_dim = int(self.geometry.get("Din", self.d_model))        # width of tokens / reconstructed_tokens
         self.neck = self.variant == 2 and self.num_keypoints == 18           # the shopformer_2 loader synthesises joint 17
+        self.decoder_info = None
+        if self.has_decoder:
+            self.decoder_info = ShopformerDecoderInfo()
+            _lib.check(_lib.lib().mi355_shopformer_decoder_info(self._h, C.byref(self.decoder_info)))
 
     def _info(self) -> ShopformerInfo:
         info = ShopformerInfo()
@@ -485,17 +562,23 @@ class Shopformer:
         """kernel launches this model has enqueued so far (the engine's own counter, incremented beside the launch)"""
         return int(self._info().launches)
 
-    @classmethod
-    def from_state_dict(cls, sd, config: Optional[dict] = None, device: int = 0, variant: Optional[int] = None) -> "Shopformer":
-        return cls(image_from_state_dict(sd, config, variant=variant), device=device)
+    @property
+    def has_decoder(self) -> bool:
+        """the image holds the GCAE decoder (it was built with ``decoder=True``): ``forward(poses=True)`` and ``decode`` work"""
+        return "Tdec" in self.geometry
 
     @classmethod
-    def from_checkpoint(cls, path: str, config=None, device: int = 0, variant: Optional[int] = None) -> "Shopformer":
+    def from_state_dict(cls, sd, config: Optional[dict] = None, device: int = 0, variant: Optional[int] = None,
+                        decoder: bool = False) -> "Shopformer":
+        return cls(image_from_state_dict(sd, config, variant=variant, decoder=decoder), device=device)
+
+    @classmethod
+    def from_checkpoint(cls, path: str, config=None, device: int = 0, variant: Optional[int] = None, decoder: bool = False) -> "Shopformer":
         """``torch.save({'model_state_dict': ...})`` as the reference's train.py writes it; ``config``: a dict, a path, or None for the
         ``config.json`` beside the checkpoint (absent: the reference's defaults), as its inference.py resolves it.  A ``shopformer_2``
         checkpoint carries its nested config under ``config`` (used when none is given); ``config`` may also be a YAML path; the split
         ``gcae_state_dict`` / ``transformer_state_dict`` form is accepted as its evaluate.py accepts it."""
-        return cls(image_from_checkpoint(path, config, variant), device=device)
+        return cls(image_from_checkpoint(path, config, variant, decoder), device=device)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -512,11 +595,15 @@ class Shopformer:
             raise ValueError(f"windows must be [N, 2, {self.seq_len}, {self.num_keypoints}], got {tuple(w.shape)}")
         return w
 
-    def forward(self, windows, outputs: bool = True) -> Dict[str, np.ndarray]:
+    def forward(self, windows, outputs: bool = True, poses: bool = False) -> Dict[str, np.ndarray]:
         """-> ``normality_score`` [N]; with ``outputs`` also ``tokens`` and ``reconstructed_tokens`` [N, n_tokens, token_dim] and, for
-        the shopformer_2 variant, ``token_scores`` [N, n_tokens]"""
+        the shopformer_2 variant, ``token_scores`` [N, n_tokens]; with ``poses`` (a model loaded with ``decoder=True``) also
+        ``gcae_reconstructed`` [N, 2, T, V] = the decoder on ``tokens`` (the same array as ``reconstructed_poses``, shopformer_2's name)
+        and ``pose_error`` [N, T, V], the mean over the 2 channels of (reconstruction - window)^2"""
         w = self._check(windows)
         n = len(w)
+        if poses:
+            return self._forward_poses(w, outputs)
         score = np.empty(n, np.float32)
         tok = np.empty((n, self.n_tokens, self.token_dim), np.float32) if outputs else None
         rec = np.empty((n, self.n_tokens, self.token_dim), np.float32) if outputs else None
@@ -534,6 +621,47 @@ class Shopformer:
         if ts is not None:
             out["token_scores"] = ts
         return out
+
+    def _forward_poses(self, w: np.ndarray, outputs: bool) -> Dict[str, np.ndarray]:
+        if not self.has_decoder:
+            raise ValueError(NO_DECODER)
+        n, ptr = len(w), lambda a: a.ctypes.data if a is not None else None
+        score = np.empty(n, np.float32)
+        tok = np.empty((n, self.n_tokens, self.token_dim), np.float32) if outputs else None
+        rec = np.empty((n, self.n_tokens, self.token_dim), np.float32) if outputs else None
+        ts = np.empty((n, self.n_tokens), np.float32) if outputs and self.variant == 2 else None
+        pose = np.empty((n, 2, self.seq_len, self.num_keypoints), np.float32)
+        err = np.empty((n, self.seq_len, self.num_keypoints), np.float32)
+        if n:
+            o = _outputs(ptr(score), ptr(ts), ptr(tok), ptr(rec), ptr(pose), ptr(err))
+            _lib.check(_lib.lib().mi355_shopformer_score_ex(self._h, w.ctypes.data, n, C.byref(o)))
+        out = {"normality_score": score}
+        if outputs:
+            out["tokens"], out["reconstructed_tokens"] = tok, rec
+        if ts is not None:
+            out["token_scores"] = ts
+        out["gcae_reconstructed"] = out["reconstructed_poses"] = pose
+        out["pose_error"] = err
+        return out
+
+    def decode(self, tokens) -> np.ndarray:
+        """tokens ``[N, n_tokens, token_dim]`` -> the decoder's poses ``[N, 2, T, V]``; ``decode(forward(x)["reconstructed_tokens"])`` is
+        the pose the transformer expected.  One launch; a pose's bits do not depend on N or on its position."""
+        if not self.has_decoder:
+            raise ValueError(NO_DECODER)
+        t = np.ascontiguousarray(tokens, np.float32)
+        if t.ndim != 3 or t.shape[1:] != (self.n_tokens, self.token_dim):
+            raise ValueError(f"tokens must be [N, {self.n_tokens}, {self.token_dim}], got {tuple(t.shape)}")
+        pose = np.empty((len(t), 2, self.seq_len, self.num_keypoints), np.float32)
+        if len(t):
+            _lib.check(_lib.lib().mi355_shopformer_decode(self._h, t.ctypes.data, len(t), pose.ctypes.data))
+        return pose
+
+    def decode_device_async(self, tokens_dev: int, n: int, poses_dev: int, stream: int = 0) -> None:
+        """``decode`` on device pointers, enqueued on the caller's stream; returns without waiting"""
+        if not self.has_decoder:
+            raise ValueError(NO_DECODER)
+        _lib.check(_lib.lib().mi355_shopformer_decode_device_async(self._h, tokens_dev, int(n), poses_dev, stream or None))
 
     def score(self, windows, reduction: str = "mean") -> np.ndarray:
         """``reduction='mean'`` -> [N]; ``'none'`` -> [N, n_tokens] (the shopformer_2 variant's per-token scores)"""
@@ -554,13 +682,16 @@ class Shopformer:
         return (self.score(windows) > threshold).astype(np.int64)
 
     def score_device_async(self, windows_dev: int, n: int, scores_dev: int, stream: int = 0, tokens_dev: int = 0, recon_dev: int = 0,
-                           token_scores_dev: int = 0) -> None:
+                           token_scores_dev: int = 0, poses_dev: int = 0, pose_error_dev: int = 0) -> None:
         """device pointers in, device pointers out, enqueued on the caller's stream (0 = the null stream); returns without waiting.
-        ``token_scores_dev`` ([n, n_tokens]) is an output of the shopformer_2 variant only."""
-        if token_scores_dev or self.variant == 2:
-            if self.variant != 2:
-                raise ValueError("token_scores exist only for the shopformer_2 variant")
-            o = _outputs(scores_dev, token_scores_dev, tokens_dev, recon_dev)
+        ``token_scores_dev`` ([n, n_tokens]) is an output of the shopformer_2 variant only; ``poses_dev`` ([n, 2, T, V]) and
+        ``pose_error_dev`` ([n, T, V], beside ``poses_dev``) need a model loaded with ``decoder=True``."""
+        if (poses_dev or pose_error_dev) and not self.has_decoder:
+            raise ValueError(NO_DECODER)
+        if token_scores_dev and self.variant != 2:
+            raise ValueError("token_scores exist only for the shopformer_2 variant")
+        if token_scores_dev or self.variant == 2 or poses_dev or pose_error_dev:
+            o = _outputs(scores_dev, token_scores_dev, tokens_dev, recon_dev, poses_dev, pose_error_dev)
             _lib.check(_lib.lib().mi355_shopformer_score_ex_device_async(self._h, windows_dev, int(n), C.byref(o), stream or None))
             return
         _lib.check(_lib.lib().mi355_shopformer_score_device_async(self._h, windows_dev, int(n), scores_dev, tokens_dev or None,

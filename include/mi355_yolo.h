@@ -457,10 +457,32 @@ typedef struct {
     float* token_scores;    /* [n][n_tokens] */
     float* tokens;          /* [n][n_tokens][token width] */
     float* recon;           /* [n][n_tokens][token width] */
+    /* the struct grew here (see below); struct_size may be the size up to this point, the two pointers below are then absent */
+    float* poses;           /* [n][2][seq_len][num_keypoints]: the GCAE decoder's reconstruction of the window */
+    float* pose_error;      /* [n][seq_len][num_keypoints]: mean over the 2 channels of (poses - windows)^2; needs poses */
 } mi355_shopformer_outputs_t;
 int  mi355_shopformer_score_ex(mi355_shopformer* h, const float* windows, int n, const mi355_shopformer_outputs_t* out);
 int  mi355_shopformer_score_ex_device_async(mi355_shopformer* h, const float* windows_dev, int n, const mi355_shopformer_outputs_t* out,
                                             void* stream);
+/* Version-3 images (cvsd_amd/shopformer.py, decoder=True) hold either network plus its GCAE decoder: tokens ->
+ * initial_proj -> four (transposed) convolutions -> linear interpolation along time when the layers emit fewer frames than seq_len.
+ * `poses` / `pose_error` of the outputs struct ask the _ex calls for it: ONE more launch after the score path's, reading the tokens
+ * that path wrote; version-1-variant images are accepted by the _ex calls with scores set.  A caller that passes the struct's
+ * earlier size (up to and including `recon`) gets the earlier behaviour.  mi355_shopformer_decode runs the decoder alone on
+ * caller-supplied tokens [n][n_tokens][token width] -> poses [n][2][seq_len][num_keypoints] (one launch; no pose_error: there is no
+ * window).  A pose's bits do not depend on n or on its position in the batch.  On a handle whose image was built without the
+ * decoder each of these fails with MI355_EINVAL before any launch. */
+int  mi355_shopformer_decode(mi355_shopformer* h, const float* tokens, int n, float* poses);
+int  mi355_shopformer_decode_device_async(mi355_shopformer* h, const float* tokens_dev, int n, float* poses_dev, void* stream);
+typedef struct {
+    int factors[4];         /* upsample factor of each decoder layer: 2 = (2,1)/(2,1) transposed convolution, 1 = 1x1 convolution */
+    int frames;             /* frames the layers emit (n_tokens * product of the factors) */
+    int interpolate;        /* 1: frames != seq_len, linear interpolation along time (align_corners=False) follows */
+    int group;              /* windows per workgroup: group * n_tokens rows of initial_proj */
+    int lds_bytes;
+    long long macs_per_window;
+} mi355_shopformer_decoder_info_t;
+int  mi355_shopformer_decoder_info(const mi355_shopformer* h, mi355_shopformer_decoder_info_t* info);
 
 #ifdef __cplusplus
 }
