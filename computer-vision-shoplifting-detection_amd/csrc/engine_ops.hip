@@ -126,6 +126,90 @@ int mi355_op_dwconv2d(int device_id, const float* x, int n, int h, int w, int x_
     return MI355_OK;
 }
 
+int mi355_op_decode(int device_id, const float* const* bufs, const int* geom, int n_levels, int n, int nc, int nkpt, int kdim,
+                    int mode, int gate, float* pred, float* best, int* fallback_count) {
+    if (!bufs || !geom || !pred || !best || n <= 0 || nc <= 0 || nkpt < 0) return fail(MI355_EINVAL, "bad argument");
+    if (n_levels < 1 || n_levels > 4) return fail(MI355_EINVAL, "decode takes 1 to 4 levels");
+    if (mode < 0 || mode > 2) return fail(MI355_EINVAL, "mode must be 0 (full), 1 (nms) or 2 (split)");
+    if (nkpt ? (kdim != 2 && kdim != 3) : kdim != 0) return fail(MI355_EINVAL, "kdim must be 2 or 3 with keypoints and 0 without");
+    const int nk = nkpt * kdim, no = 4 + nc + nk;
+    DecodeArgs d{};
+    long anchors = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        const int* g = geom + 7 * l;           // cs, box_off, cls_off, kpt_off, h, w, stride
+        if (!bufs[l] || g[0] <= 0 || g[4] <= 0 || g[5] <= 0 || g[6] <= 0) return fail(MI355_EINVAL, "bad level");
+        if (g[1] < 0 || g[1] + 64 > g[0] || g[2] < 0 || g[2] + nc > g[0] || (nk && (g[3] < 0 || g[3] + nk > g[0])))
+            return fail(MI355_EINVAL, "a level's box / class / keypoint slice lies outside its cs channels");
+        d.lv[l].cs = g[0]; d.lv[l].box_off = g[1]; d.lv[l].cls_off = g[2]; d.lv[l].kpt_off = g[3];
+        d.lv[l].H = g[4]; d.lv[l].W = g[5]; d.lv[l].stride = g[6]; d.lv[l].anchor0 = (int)anchors;
+        anchors += (long)g[4] * g[5];
+    }
+    if (anchors * n * (long)no > (1l << 28)) return fail(MI355_EINVAL, "too many anchors");
+    HIPCHK(hipSetDevice(device_id));
+    DevMem dm; float *d_pred, *d_best; int* d_words;
+    for (int l = 0; l < n_levels; ++l) {
+        float* d_buf;
+        const size_t bytes = (size_t)n * d.lv[l].H * d.lv[l].W * d.lv[l].cs * 4;
+        HIPCHK(dm.alloc(&d_buf, bytes)); HIPCHK(hipMemcpy(d_buf, bufs[l], bytes, hipMemcpyHostToDevice));
+        d.lv[l].buf = d_buf;
+    }
+    const size_t pn = (size_t)n * anchors * no, bn = (size_t)n * anchors * 2;
+    HIPCHK(dm.alloc(&d_pred, pn * 4)); HIPCHK(hipMemcpy(d_pred, pred, pn * 4, hipMemcpyHostToDevice));
+    HIPCHK(dm.alloc(&d_best, bn * 4)); HIPCHK(hipMemcpy(d_best, best, bn * 4, hipMemcpyHostToDevice));
+    const int words[2] = {gate, 0};            // the gate word, the box stage's counter
+    HIPCHK(dm.alloc(&d_words, sizeof(words))); HIPCHK(hipMemcpy(d_words, words, sizeof(words), hipMemcpyHostToDevice));
+    d.n_levels = n_levels; d.B = n; d.A = (int)anchors; d.nc = nc; d.nkpt = nkpt; d.kdim = kdim;
+    d.pred = d_pred; d.best = (float2*)d_best;
+    if (mode == 2) {
+        KCHK(launch_decode(d, false, nullptr, 1));
+        d.gate = d_words; d.fallback_count = d_words + 1;
+        KCHK(launch_decode(d, false, nullptr, 2));
+    } else {
+        KCHK(launch_decode(d, mode == 0, nullptr));
+    }
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(pred, d_pred, pn * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(best, d_best, bn * 4, hipMemcpyDeviceToHost));
+    if (fallback_count) HIPCHK(hipMemcpy(fallback_count, d_words + 1, sizeof(int), hipMemcpyDeviceToHost));
+    return MI355_OK;
+}
+
+int mi355_op_sppf_pools(int device_id, const void* x, int n, int h, int w, int x_cs, int x_off, int c, void* y, int y_cs, int y_off,
+                        int half) {
+    if (!x || !y || n <= 0 || h <= 0 || w <= 0 || c <= 0) return fail(MI355_EINVAL, "bad argument");
+    const int es = half ? 2 : 4, al = 16 / es;
+    auto view_ok = [&](int cs, int off, int cv) { return cs > 0 && off >= 0 && !(cs % al) && !(off % al) && off + cv <= cs; };
+    if ((c % al) || !view_ok(x_cs, x_off, c) || !view_ok(y_cs, y_off, 3 * c))
+        return fail(MI355_EINVAL, "views: c, strides and offsets must be multiples of 16 bytes and the views (c in, 3c out) inside the tensors");
+    HIPCHK(hipSetDevice(device_id));
+    const size_t np = (size_t)n * h * w;
+    DevMem dm; char *d_x, *d_y;
+    HIPCHK(dm.alloc(&d_x, np * x_cs * es)); HIPCHK(hipMemcpy(d_x, x, np * x_cs * es, hipMemcpyHostToDevice));
+    HIPCHK(dm.alloc(&d_y, np * y_cs * es)); HIPCHK(hipMemcpy(d_y, y, np * y_cs * es, hipMemcpyHostToDevice));
+    if (half) KCHK(launch_sppf_pools_f16(d_x + (size_t)x_off * es, x_cs, d_y + (size_t)y_off * es, y_cs, n, h, w, c, nullptr));
+    else KCHK(launch_sppf_pools((const float*)d_x + x_off, x_cs, (float*)d_y + y_off, y_cs, n, h, w, c, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(y, d_y, np * y_cs * es, hipMemcpyDeviceToHost));
+    return MI355_OK;
+}
+
+int mi355_op_upsample2x(int device_id, const uint32_t* x, int n, int h, int w, int x_cs, int x_off, int c, uint32_t* y, int y_cs,
+                        int y_off) {
+    if (!x || !y || n <= 0 || h <= 0 || w <= 0 || c <= 0) return fail(MI355_EINVAL, "bad argument");
+    auto view_ok = [&](int cs, int off) { return cs > 0 && off >= 0 && !(cs & 3) && !(off & 3) && off + c <= cs; };
+    if (!view_ok(x_cs, x_off) || !view_ok(y_cs, y_off))
+        return fail(MI355_EINVAL, "views: strides / offsets must be multiples of 4 and the view inside the tensor");
+    HIPCHK(hipSetDevice(device_id));
+    const size_t np = (size_t)n * h * w;
+    DevMem dm; float *d_x, *d_y;
+    HIPCHK(dm.alloc(&d_x, np * x_cs * 4)); HIPCHK(hipMemcpy(d_x, x, np * x_cs * 4, hipMemcpyHostToDevice));
+    HIPCHK(dm.alloc(&d_y, 4 * np * y_cs * 4)); HIPCHK(hipMemcpy(d_y, y, 4 * np * y_cs * 4, hipMemcpyHostToDevice));
+    KCHK(launch_upsample2x(d_x + x_off, x_cs, d_y + y_off, y_cs, n, h, w, c, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(y, d_y, 4 * np * y_cs * 4, hipMemcpyDeviceToHost));
+    return MI355_OK;
+}
+
 int mi355_op_psa_attention(int device_id, const float* qkv, int n, int hw, int heads, int key_dim, int head_dim, float* y) {
     if (!qkv || !y || n <= 0 || hw <= 0 || heads <= 0) return fail(MI355_EINVAL, "bad argument");
     if (key_dim != 32 || head_dim != 64) return fail(MI355_EINVAL, "key_dim must be 32 and head_dim 64");

@@ -84,6 +84,113 @@ def dwconv2d(x_nhwc: np.ndarray, w_c1kk: np.ndarray, bias: np.ndarray, silu: boo
     return out
 
 
+# What decode / sppf_pools / upsample2x put into outputs before the launch: a quiet NaN with a payload no kernel produces, so a
+# word the kernel did not write is told apart from any value it could have written (compare the bits, NaN != NaN).
+SENTINEL_BITS = np.uint32(0x7FC5A5A5)
+SENTINEL = SENTINEL_BITS.view(np.float32)
+DECODE_MODES = {"full": 0, "nms": 1, "split": 2}
+
+
+def _sentinel(shape) -> np.ndarray:
+    return np.full(shape, SENTINEL_BITS, dtype=np.uint32).view(np.float32)
+
+
+def decode(levels, nc: int, nkpt: int = 0, kdim: int = 0, mode: str = "full", gate: Optional[int] = None, device: int = 0):
+    """The head decode kernel alone (DFL + dist2bbox, class scores -> best score / first argmax, keypoints), fp32.
+    ``levels``: up to 4 tuples ``(buf [n,h,w,cs] fp32, box_off, cls_off, kpt_off, stride)``: 64 box logits, nc class logits and
+    nkpt*kdim keypoint values of each pixel sit at those channel offsets of ``buf``.
+    ``mode``: "full" = the raw-head form (every class score stored); "nms" = the form predict() runs (box, keypoints, best);
+    "split" = the sparse box branch's pair: score stage, then the box stage behind a device gate word set to ``gate``.
+    -> (pred [n, A, 4+nc+nkpt*kdim], best [n, A, 2]) and, for "split", the box stage's fallback counter.  Both arrays are filled
+    with SENTINEL before the launch."""
+    if mode not in DECODE_MODES:
+        raise ValueError(f"mode must be one of {sorted(DECODE_MODES)}")
+    if (mode == "split") != (gate is not None):
+        raise ValueError("gate is the split mode's argument (and it needs one)")
+    levels = list(levels)
+    if not 1 <= len(levels) <= 4:
+        raise ValueError("decode takes 1 to 4 levels")
+    if nc <= 0 or nkpt < 0 or (kdim not in (2, 3) if nkpt else kdim != 0):
+        raise ValueError("nc must be positive; kdim 2 or 3 with keypoints, 0 without")
+    nk = nkpt * kdim
+    no = 4 + nc + nk
+    bufs, geom, anchors, n = [], [], 0, None
+    for buf, box_off, cls_off, kpt_off, stride in levels:
+        b = _f32(buf)
+        if b.ndim != 4 or (n is not None and b.shape[0] != n):
+            raise ValueError("every level is [n, h, w, cs] with the same n")
+        n, h, w, cs = b.shape
+        if min(n, h, w) <= 0 or stride <= 0:
+            raise ValueError("empty level or non-positive stride")
+        if box_off < 0 or box_off + 64 > cs or cls_off < 0 or cls_off + nc > cs or (nk and (kpt_off < 0 or kpt_off + nk > cs)):
+            raise ValueError("a level's box / class / keypoint slice lies outside its cs channels")
+        bufs.append(b)
+        geom += [cs, box_off, cls_off, kpt_off, h, w, stride]
+        anchors += h * w
+    pred = _sentinel((n, anchors, no))
+    best = _sentinel((n, anchors, 2))
+    ptrs = (C.c_void_p * len(bufs))(*[b.ctypes.data for b in bufs])
+    g = (C.c_int * len(geom))(*[int(v) for v in geom])
+    count = C.c_int(-1)
+    _lib.check(_lib.lib().mi355_op_decode(device, ptrs, g, len(bufs), n, nc, nkpt, kdim, DECODE_MODES[mode], int(gate or 0),
+                                          pred.ctypes.data, best.ctypes.data, C.byref(count)))
+    return (pred, best, count.value) if mode == "split" else (pred, best)
+
+
+def _check_view(name: str, cs: int, off: int, c: int, al: int):
+    if off < 0 or cs % al or off % al or off + c > cs:
+        raise ValueError(f"{name}: stride {cs} / offset {off} must be multiples of {al} and channels {off} .. {off + c} inside the tensor")
+
+
+def sppf_pools(x_nhwc: np.ndarray, c: int, x_off: int = 0, y: Optional[np.ndarray] = None, y_off: int = 0, half: bool = False,
+               device: int = 0) -> np.ndarray:
+    """SPPF's three chained MaxPool2d(5, 1, 2) on channel views: pools channels x_off .. x_off+c of x [N,H,W,Cx] and writes
+    x1|x2|x3 into channels y_off .. y_off+3c of a copy of ``y`` [N,H,W,Cy] (default: SENTINEL-filled [N,H,W,3c]); the other
+    channels of y come back unchanged.  ``half``: x and y are rounded to fp16 on the host and the fp16 kernels run (c, strides and
+    offsets are then multiples of 8 instead of 4: 16-byte vectors); values are returned as fp32 either way."""
+    x = _f32(x_nhwc)
+    if x.ndim != 4:
+        raise ValueError("x must be [N, H, W, Cx]")
+    n, h, wd, cx = x.shape
+    al = 8 if half else 4
+    if c <= 0 or c % al:
+        raise ValueError(f"c must be a positive multiple of {al}")
+    out = _sentinel((n, h, wd, 3 * c)) if y is None else np.array(y, dtype=np.float32, order="C", copy=True)
+    if out.shape[:3] != (n, h, wd):
+        raise ValueError("y must be [N, H, W, Cy] with x's N, H, W")
+    _check_view("x", cx, x_off, c, al)
+    _check_view("y", out.shape[3], y_off, 3 * c, al)
+    if half:
+        x, out = x.astype(np.float16), out.astype(np.float16)
+    _lib.check(_lib.lib().mi355_op_sppf_pools(device, x.ctypes.data, n, h, wd, cx, x_off, c, out.ctypes.data, out.shape[3], y_off,
+                                              int(half)))
+    return out.astype(np.float32) if half else out
+
+
+def upsample2x(x_nhwc: np.ndarray, c: int, x_off: int = 0, y: Optional[np.ndarray] = None, y_off: int = 0, device: int = 0) -> np.ndarray:
+    """Nearest 2x upsample of 32-bit words on channel views (the engine also moves fp16 pairs with it, so any bit pattern must
+    survive): x [N,H,W,Cx] uint32 (or fp32, taken as its bits) channels x_off .. x_off+c -> channels y_off .. y_off+c of a copy of
+    ``y`` [N,2H,2W,Cy] (default: SENTINEL_BITS-filled [N,2H,2W,c]); returned as uint32, the other channels of y unchanged."""
+    def words(a):
+        a = np.asarray(a)
+        if a.dtype not in (np.dtype(np.uint32), np.dtype(np.float32)):
+            raise ValueError("32-bit words: uint32 or float32 arrays")
+        return np.ascontiguousarray(a).view(np.uint32)
+    x = words(x_nhwc)
+    if x.ndim != 4:
+        raise ValueError("x must be [N, H, W, Cx]")
+    n, h, wd, cx = x.shape
+    if c <= 0:
+        raise ValueError("c must be positive")
+    out = np.full((n, 2 * h, 2 * wd, c), SENTINEL_BITS, np.uint32) if y is None else words(y).copy()
+    if out.shape[:3] != (n, 2 * h, 2 * wd):
+        raise ValueError("y must be [N, 2H, 2W, Cy]")
+    _check_view("x", cx, x_off, c, 4)
+    _check_view("y", out.shape[3], y_off, c, 4)
+    _lib.check(_lib.lib().mi355_op_upsample2x(device, x.ctypes.data, n, h, wd, cx, x_off, c, out.ctypes.data, out.shape[3], y_off))
+    return out
+
+
 def psa_attention(qkv: np.ndarray, heads: int, key_dim: int = 32, head_dim: int = 64, device: int = 0) -> np.ndarray:
     """PSA attention (YOLO11 Attention between qkv and pe): qkv [N, HW, heads*(2*key_dim+head_dim)] laid out
     [q of every head | k of every head | v of every head] -> [N, HW, heads*head_dim]."""

@@ -396,6 +396,26 @@ int  mi355_op_dwconv2d(int device_id, const float* x, int n, int h, int w, int x
  * out [q of every head | k of every head | v of every head]; y[n][hw][heads*head_dim] = per frame and head
  * softmax_j(q_i . k_j * key_dim^-0.5) v_j.  key_dim 32, head_dim 64 (every YOLO11 scale). */
 int  mi355_op_psa_attention(int device_id, const float* qkv, int n, int hw, int heads, int key_dim, int head_dim, float* y);
+/* The head decode kernel alone (DFL + dist2bbox, class sigmoid -> best score / first argmax, keypoint decode), fp32, on raw head
+ * maps of the caller: bufs[l] = [n][h][w][cs] and geom[l] = {cs, box_off, cls_off, kpt_off, h, w, stride} for each of n_levels
+ * (1 .. 4) levels; 64 box logits at box_off, nc class logits at cls_off, nkpt*kdim keypoint values at kpt_off (kdim 2 or 3, or
+ * nkpt = kdim = 0).  mode 0: the raw-head form (every class score stored); 1: the form NMS runs behind (box, keypoints and best
+ * only); 2: the split form of the sparse box branch -- the score stage, then the box stage behind a device gate word set to
+ * `gate`; *fallback_count (or NULL) receives the box stage's counter.  pred[n][A][4+nc+nkpt*kdim] (anchor-major) and best[n][A][2]
+ * are read in and handed back, so whatever the launch does not write keeps the caller's bits.  The launcher's alignment rules
+ * (cs and box_off multiples of 4) come back as MI355_EHIP with its message. */
+int  mi355_op_decode(int device_id, const float* const* bufs, const int* geom, int n_levels, int n, int nc, int nkpt, int kdim,
+                     int mode, int gate, float* pred, float* best, int* fallback_count);
+/* SPPF's three chained MaxPool2d(5, 1, 2) on channel views: x[n][h][w][x_cs] holds the input view at channels x_off .. x_off+c-1;
+ * y[n][h][w][y_cs] is read in, x1|x2|x3 written to channels y_off .. y_off+3c-1 and every other channel handed back unchanged.
+ * half = 0: fp32 elements, c, strides and offsets multiples of 4; half = 1: fp16 bit patterns, multiples of 8. */
+int  mi355_op_sppf_pools(int device_id, const void* x, int n, int h, int w, int x_cs, int x_off, int c, void* y, int y_cs, int y_off,
+                         int half);
+/* Nearest 2x upsample of 32-bit words on channel views (also the engine's copy of fp16 pairs: the words are never interpreted):
+ * x[n][h][w][x_cs] view x_off .. x_off+c-1 -> y[n][2h][2w][y_cs] view y_off .. y_off+c-1; y is read in and its other channels
+ * handed back unchanged.  Strides and offsets are multiples of 4, c is any positive count. */
+int  mi355_op_upsample2x(int device_id, const uint32_t* x, int n, int h, int w, int x_cs, int x_off, int c, uint32_t* y, int y_cs,
+                         int y_off);
 /* The u8 stem: letterboxed BGR frames -> (x/255, RGB) -> conv k x k stride s (pad k/2, or 2 for k=6) + bias + SiLU. */
 int  mi355_op_stem(int device_id, const uint8_t* bgr, int n, int h, int w, const float* w_oihw, const float* bias,
                    int cout, int k, int stride, float* y);
