@@ -85,6 +85,8 @@ SIGNATURES = {
     "mi355_op_psa_attention": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mi355_op_decode": (C.c_int, [C.c_int, _P(C.c_void_p), _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p, _i32p]),
+    "mi355_op_sparse_box": (C.c_int, [C.c_int, _P(C.c_void_p), _i32p, C.c_int, C.c_int, C.c_void_p, C.c_float, _i32p, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_void_p, _i32p]),
     "mi355_op_sppf_pools": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                       C.c_int, C.c_int]),
     "mi355_op_upsample2x": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,

@@ -174,6 +174,99 @@ int mi355_op_decode(int device_id, const float* const* bufs, const int* geom, in
     return MI355_OK;
 }
 
+// The sparse tail of a pass without its dense launches (engine_run.hip:launch_net): state zeroed, launch_sparse_lists,
+// launch_sparse_box.  ptrs: 10 per level, geom: 11 per level (include/mi355_yolo.h).
+int mi355_op_sparse_box(int device_id, void* const* ptrs, const int* geom, int n_levels, int n, const float* best, float conf,
+                        const int* classes, int n_classes, int nc, int no, int act, float* pred, int* state) {
+    if (!ptrs || !geom || !best || !pred || !state || n <= 0 || nc <= 0) return fail(MI355_EINVAL, "bad argument");
+    if (n_levels < 1 || n_levels > 3) return fail(MI355_EINVAL, "sparse_box takes 1 to 3 levels");
+    if (no < 4 + nc) return fail(MI355_EINVAL, "no must be at least 4 + nc");
+    if (act < 0 || act > 2) return fail(MI355_EINVAL, "act must be 0 (none), 1 (SiLU) or 2 (fast SiLU)");
+    SparseArgs sa{};
+    struct Lv { int src_cs, src_off, cin, cout_a, mid_cs, mid_off; float* d_mid; size_t mid_floats; };
+    Lv lv[3];
+    long anchors = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        const int* g = geom + 11 * l;          // h, w, src_cs, src_off, cin, cout_a, stride, mid_cs, mid_off, cap_dil, cap_cand
+        void* const* p = ptrs + 10 * l;        // src, wA, bA, wB, bB, wC, bC, mid, dil, cand
+        for (int i = 0; i < 10; ++i) if (!p[i]) return fail(MI355_EINVAL, "bad level: null pointer");
+        const int h = g[0], w = g[1], stride = g[6];
+        lv[l] = Lv{g[2], g[3], g[4], g[5], g[7], g[8], nullptr, 0};
+        if (h <= 0 || w <= 0 || stride <= 0) return fail(MI355_EINVAL, "bad level");
+        if (lv[l].cin <= 0 || (lv[l].cin & 15)) return fail(MI355_EINVAL, "cin must be a positive multiple of 16");
+        if (lv[l].cout_a < 64) return fail(MI355_EINVAL, "cv2.i.0 needs at least 64 couts");
+        auto view_ok = [](int cs, int off, int c) { return cs > 0 && off >= 0 && !(cs & 3) && !(off & 3) && off + c <= cs; };
+        if (!view_ok(lv[l].src_cs, lv[l].src_off, lv[l].cin) || !view_ok(lv[l].mid_cs, lv[l].mid_off, 64))
+            return fail(MI355_EINVAL, "views: strides / offsets must be multiples of 4 and the views (cin of src, 64 of mid) inside the tensors");
+        const long pos = (long)n * h * w;
+        if (pos > (1l << 24)) return fail(MI355_EINVAL, "too many positions");
+        if (g[9] < 1 || g[10] < 1 || g[9] > pos || g[10] > pos) return fail(MI355_EINVAL, "list capacities must lie in 1 .. n*h*w");
+        SparseLevel& L = sa.lv[l];
+        L.src_cs = lv[l].src_cs; L.cib = lv[l].cin / 16; L.mid_cs = lv[l].mid_cs;
+        L.H = h; L.W = w; L.stride = stride; L.anchor0 = (int)anchors; L.cap_dil = g[9]; L.cap_cand = g[10];
+        anchors += (long)h * w;
+    }
+    if (anchors * n * (long)no > (1l << 28)) return fail(MI355_EINVAL, "too many anchors");
+    std::vector<unsigned> mask;
+    if (n_classes > 0 && classes) {
+        mask.assign((nc + 31) / 32, 0u);
+        for (int i = 0; i < n_classes; ++i) if (classes[i] >= 0 && classes[i] < nc) mask[classes[i] >> 5] |= 1u << (classes[i] & 31);
+        // the lists kernel indexes the mask with best[]'s class: it must name a class
+        for (long i = 0; i < anchors * n; ++i)
+            if (!(best[2 * i + 1] >= 0.f && best[2 * i + 1] < (float)nc)) return fail(MI355_EINVAL, "best[] holds a class outside 0 .. nc-1");
+    }
+    HIPCHK(hipSetDevice(device_id));
+    DevMem dm; float *d_pred, *d_best; int* d_state; unsigned* d_mask = nullptr;
+    auto upload_conv = [&](const float* wt, const float* b, int co, int ci, int k, const float** dw, const float** db) -> int {
+        std::vector<float> pk(packed_weight_floats(co, ci, k)), bp(round_up(co, 16), 0.f);
+        pack_conv_weights(wt, co, ci, k, pk.data());
+        std::memcpy(bp.data(), b, (size_t)co * 4);
+        float *w_, *b_;
+        HIPCHK(dm.alloc(&w_, pk.size() * 4)); HIPCHK(hipMemcpy(w_, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(dm.alloc(&b_, bp.size() * 4)); HIPCHK(hipMemcpy(b_, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
+        *dw = w_; *db = b_;
+        return MI355_OK;
+    };
+    for (int l = 0; l < n_levels; ++l) {
+        void* const* p = ptrs + 10 * l;
+        SparseLevel& L = sa.lv[l];
+        const size_t np = (size_t)n * L.H * L.W;
+        float* d_src;
+        HIPCHK(dm.alloc(&d_src, np * L.src_cs * 4)); HIPCHK(hipMemcpy(d_src, p[0], np * L.src_cs * 4, hipMemcpyHostToDevice));
+        lv[l].mid_floats = np * L.mid_cs;
+        HIPCHK(dm.alloc(&lv[l].d_mid, lv[l].mid_floats * 4)); HIPCHK(hipMemcpy(lv[l].d_mid, p[7], lv[l].mid_floats * 4, hipMemcpyHostToDevice));
+        L.src = d_src + lv[l].src_off; L.mid = lv[l].d_mid + lv[l].mid_off;
+        // the whole (possibly merged cv2.i.0 | cv3.i.0) weight is packed; the kernel reads its first four cout tiles
+        int rc = upload_conv((const float*)p[1], (const float*)p[2], lv[l].cout_a, lv[l].cin, 3, &L.wA, &L.biasA); if (rc) return rc;
+        rc = upload_conv((const float*)p[3], (const float*)p[4], 64, 64, 3, &L.wB, &L.biasB); if (rc) return rc;
+        rc = upload_conv((const float*)p[5], (const float*)p[6], 64, 64, 1, &L.wC, &L.biasC); if (rc) return rc;
+        HIPCHK(dm.alloc(&L.dil, (size_t)L.cap_dil * 4)); HIPCHK(hipMemset(L.dil, 0xFF, (size_t)L.cap_dil * 4));
+        HIPCHK(dm.alloc(&L.cand, (size_t)L.cap_cand * 4)); HIPCHK(hipMemset(L.cand, 0xFF, (size_t)L.cap_cand * 4));
+    }
+    const size_t pn = (size_t)n * anchors * no, bn = (size_t)n * anchors * 2;
+    HIPCHK(dm.alloc(&d_pred, pn * 4)); HIPCHK(hipMemcpy(d_pred, pred, pn * 4, hipMemcpyHostToDevice));
+    HIPCHK(dm.alloc(&d_best, bn * 4)); HIPCHK(hipMemcpy(d_best, best, bn * 4, hipMemcpyHostToDevice));
+    HIPCHK(dm.alloc(&d_state, 16 * sizeof(int))); HIPCHK(hipMemset(d_state, 0xFF, 16 * sizeof(int)));     // whatever an earlier pass left
+    if (!mask.empty()) { HIPCHK(dm.alloc(&d_mask, mask.size() * 4)); HIPCHK(hipMemcpy(d_mask, mask.data(), mask.size() * 4, hipMemcpyHostToDevice)); }
+    sa.n_levels = n_levels; sa.B = n; sa.A = (int)anchors; sa.no = no; sa.act = act; sa.pred = d_pred; sa.best = (const float2*)d_best;
+    sa.conf = conf; sa.class_mask = d_mask; sa.state = d_state;
+    HIPCHK(hipMemsetAsync(d_state, 0, 12 * sizeof(int), nullptr));
+    KCHK(launch_sparse_lists(sa, nullptr));
+    KCHK(launch_sparse_box(sa, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(state, d_state, 12 * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pred, d_pred, pn * 4, hipMemcpyDeviceToHost));
+    for (int l = 0; l < n_levels; ++l) {
+        void* const* p = ptrs + 10 * l;
+        const SparseLevel& L = sa.lv[l];
+        HIPCHK(hipMemcpy(p[7], lv[l].d_mid, lv[l].mid_floats * 4, hipMemcpyDeviceToHost));
+        const int nd = std::max(0, std::min(state[l], L.cap_dil)), ncd = std::max(0, std::min(state[4 + l], L.cap_cand));
+        if (nd) HIPCHK(hipMemcpy(p[8], L.dil, (size_t)nd * 4, hipMemcpyDeviceToHost));
+        if (ncd) HIPCHK(hipMemcpy(p[9], L.cand, (size_t)ncd * 4, hipMemcpyDeviceToHost));
+    }
+    return MI355_OK;
+}
+
 int mi355_op_sppf_pools(int device_id, const void* x, int n, int h, int w, int x_cs, int x_off, int c, void* y, int y_cs, int y_off,
                         int half) {
     if (!x || !y || n <= 0 || h <= 0 || w <= 0 || c <= 0) return fail(MI355_EINVAL, "bad argument");

@@ -137,6 +137,87 @@ def decode(levels, nc: int, nkpt: int = 0, kdim: int = 0, mode: str = "full", ga
     return (pred, best, count.value) if mode == "split" else (pred, best)
 
 
+class SparseBoxResult:
+    """What :func:`sparse_box` hands back: ``pred`` [n, A, no]; per level ``mid`` [n, h, w, mid_cs], ``dil`` / ``cand`` (the first
+    min(count, cap) list entries, int32, in the kernel's order), ``n_dil`` / ``n_cand`` (the counts the device holds, also beyond
+    the caps); ``overflow`` (the device's overflow word)."""
+
+    def __init__(self, pred, mid, dil, cand, n_dil, n_cand, overflow):
+        self.pred, self.mid, self.dil, self.cand = pred, mid, dil, cand
+        self.n_dil, self.n_cand, self.overflow = n_dil, n_cand, overflow
+
+
+def sparse_box(levels, best: np.ndarray, conf: float, nc: int, no: Optional[int] = None, classes: Optional[Sequence[int]] = None,
+               act: int = 1, device: int = 0) -> SparseBoxResult:
+    """The sparse box branch alone (the lists kernel and the two gathered convs of csrc/conv_f32_sparse.hip), enqueued as a pass
+    enqueues its sparse tail minus the dense launches.  ``levels``: 1 to 3 dicts with
+    ``src`` [n,h,w,cs] fp32 (the neck map at channels ``src_off`` .. ``src_off + cin``, cin a multiple of 16; default: all of src),
+    ``wA, bA`` (cv2.i.0, OIHW [>= 64, cin, 3, 3]: the first 64 couts are used, a merged cv3.i.0 may follow), ``wB, bB``
+    ([64, 64, 3, 3]), ``wC, bC`` ([64, 64, 1, 1]), ``stride``, ``mid_cs`` / ``mid_off`` (default 64 / 0) and ``cap_dil`` /
+    ``cap_cand`` (default: every position).  ``best`` [n, A, 2] (score, class) is the caller's; ``conf`` and ``classes`` filter as
+    NMS does.  ``pred`` [n, A, no] (``no`` defaults to 4 + nc) and every ``mid`` are filled with SENTINEL before the launch."""
+    levels = list(levels)
+    if not 1 <= len(levels) <= 3:
+        raise ValueError("sparse_box takes 1 to 3 levels")
+    no = 4 + nc if no is None else no
+    if nc <= 0 or no < 4 + nc:
+        raise ValueError("nc must be positive and no at least 4 + nc")
+    if act not in (0, 1, 2):
+        raise ValueError("act must be 0 (none), 1 (SiLU) or 2 (fast SiLU)")
+    keep, ptrs, geom, mids, dils, cands, anchors, n = [], [], [], [], [], [], 0, None
+    for lv in levels:
+        src = _f32(lv["src"])
+        if src.ndim != 4 or (n is not None and src.shape[0] != n):
+            raise ValueError("every level's src is [n, h, w, cs] with the same n")
+        n, h, w, cs = src.shape
+        stride, src_off, cin = int(lv["stride"]), int(lv.get("src_off", 0)), int(lv.get("cin", cs))
+        mid_cs, mid_off = int(lv.get("mid_cs", 64)), int(lv.get("mid_off", 0))
+        if min(n, h, w) <= 0 or stride <= 0:
+            raise ValueError("empty level or non-positive stride")
+        if cin <= 0 or cin % 16:
+            raise ValueError("cin must be a positive multiple of 16")
+        _check_view("src", cs, src_off, cin, 4)
+        _check_view("mid", mid_cs, mid_off, 64, 4)
+        wA, bA, wB, bB, wC, bC = (_f32(lv[k]) for k in ("wA", "bA", "wB", "bB", "wC", "bC"))
+        cout_a = wA.shape[0]
+        if wA.shape != (cout_a, cin, 3, 3) or cout_a < 64 or bA.shape != (cout_a,):
+            raise ValueError("wA must be [>= 64, cin, 3, 3] with a bias per cout")
+        if wB.shape != (64, 64, 3, 3) or bB.shape != (64,) or wC.shape != (64, 64, 1, 1) or bC.shape != (64,):
+            raise ValueError("wB must be [64, 64, 3, 3], wC [64, 64, 1, 1], each with 64 biases")
+        pos = n * h * w
+        cap_dil = pos if lv.get("cap_dil") is None else int(lv["cap_dil"])
+        cap_cand = pos if lv.get("cap_cand") is None else int(lv["cap_cand"])
+        if not (1 <= cap_dil <= pos and 1 <= cap_cand <= pos):
+            raise ValueError("list capacities must lie in 1 .. n*h*w")
+        mid, dil, cand = _sentinel((n, h, w, mid_cs)), np.full(cap_dil, -1, np.int32), np.full(cap_cand, -1, np.int32)
+        arrs = [src, wA, bA, wB, bB, wC, bC, mid, dil, cand]
+        keep.append(arrs)
+        ptrs += [a.ctypes.data for a in arrs]
+        geom += [h, w, cs, src_off, cin, cout_a, stride, mid_cs, mid_off, cap_dil, cap_cand]
+        mids.append(mid); dils.append(dil); cands.append(cand)
+        anchors += h * w
+    bst = _f32(best)
+    if bst.shape != (n, anchors, 2):
+        raise ValueError("best must be [n, A, 2] with A the levels' positions per frame")
+    cls_arr, ncls = None, 0
+    if classes is not None:
+        cls_arr = (C.c_int * len(classes))(*[int(c) for c in classes])
+        ncls = len(classes)
+        if ncls and not ((bst[..., 1] >= 0) & (bst[..., 1] < nc)).all():
+            raise ValueError("with a class list every class of best[] must lie in 0 .. nc-1")
+    pred = _sentinel((n, anchors, no))
+    state = (C.c_int * 12)()
+    p = (C.c_void_p * len(ptrs))(*ptrs)
+    g = (C.c_int * len(geom))(*[int(v) for v in geom])
+    _lib.check(_lib.lib().mi355_op_sparse_box(device, p, g, len(levels), n, bst.ctypes.data, float(conf), cls_arr, ncls, nc, no, int(act),
+                                              pred.ctypes.data, state))
+    nl = len(levels)
+    n_dil, n_cand = [state[l] for l in range(nl)], [state[4 + l] for l in range(nl)]
+    dils = [d[:max(0, min(c, len(d)))].copy() for d, c in zip(dils, n_dil)]
+    cands = [d[:max(0, min(c, len(d)))].copy() for d, c in zip(cands, n_cand)]
+    return SparseBoxResult(pred, mids, dils, cands, n_dil, n_cand, state[8])
+
+
 def _check_view(name: str, cs: int, off: int, c: int, al: int):
     if off < 0 or cs % al or off % al or off + c > cs:
         raise ValueError(f"{name}: stride {cs} / offset {off} must be multiples of {al} and channels {off} .. {off + c} inside the tensor")

@@ -406,6 +406,21 @@ int  mi355_op_psa_attention(int device_id, const float* qkv, int n, int hw, int 
  * (cs and box_off multiples of 4) come back as MI355_EHIP with its message. */
 int  mi355_op_decode(int device_id, const float* const* bufs, const int* geom, int n_levels, int n, int nc, int nkpt, int kdim,
                      int mode, int gate, float* pred, float* best, int* fallback_count);
+/* The sparse box branch alone (csrc/conv_f32_sparse.hip), enqueued as a pass enqueues its sparse tail minus the dense launches:
+ * the 12 state ints zeroed, the lists kernel, then cv2.i.0 at the dilated and cv2.i.1 -> cv2.i.2 -> DFL -> box at the candidate
+ * positions.  n_levels 1 .. 3; per level l
+ *   geom[11 l ..] = {h, w, src_cs, src_off, cin, cout_a, stride, mid_cs, mid_off, cap_dil, cap_cand}
+ *   ptrs[10 l ..] = {src, wA, bA, wB, bB, wC, bC, mid, dil, cand}
+ * src[n][h][w][src_cs] holds the neck map at channels src_off .. src_off+cin-1 (cin a multiple of 16); wA[cout_a][cin][3][3]
+ * (cout_a >= 64: the first 64 couts are cv2.i.0, a merged cv3.i.0 may follow), wB[64][64][3][3], wC[64][64][1][1] are OIHW with
+ * their biases; mid[n][h][w][mid_cs] is read in, channels mid_off .. mid_off+63 of the dilated pixels written, and handed back;
+ * dil / cand receive the first min(count, cap) list entries (b*h*w + y*w + x, in no fixed order).  Strides and offsets are
+ * multiples of 4, capacities lie in 1 .. n*h*w.  best[n][A][2] (score, class) is the caller's; conf and classes[n_classes] (or
+ * NULL = every class) filter as NMS does.  pred[n][A][no] is read in and handed back with columns 0 .. 3 of the candidate anchors
+ * written; act as in the conv epilogues (1 = SiLU).  state[12] receives the device words: [0, 3) dilated counts, [4, 7)
+ * candidate counts, [8] = 1 when a list overflowed (nothing else is then written). */
+int  mi355_op_sparse_box(int device_id, void* const* ptrs, const int* geom, int n_levels, int n, const float* best, float conf,
+                         const int* classes, int n_classes, int nc, int no, int act, float* pred, int* state);
 /* SPPF's three chained MaxPool2d(5, 1, 2) on channel views: x[n][h][w][x_cs] holds the input view at channels x_off .. x_off+c-1;
  * y[n][h][w][y_cs] is read in, x1|x2|x3 written to channels y_off .. y_off+3c-1 and every other channel handed back unchanged.
  * half = 0: fp32 elements, c, strides and offsets multiples of 4; half = 1: fp16 bit patterns, multiples of 8. */

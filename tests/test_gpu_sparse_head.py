@@ -20,15 +20,15 @@ def _rows_equal(a, b, tag):
         assert np.array_equal(ra[i, :ca[i]].view(np.uint32), rb[i, :cb[i]].view(np.uint32)), f"{tag}: rows of frame {i} differ"
 
 
-def _pair(name, monkeypatch, chunk, cap=None):
+def _pair(name, monkeypatch, chunk, cap=None, nc=None):
     from cvsd_amd import YOLO, _lib
     from tools import synth
-    _, sd = synth.synthetic_checkpoint(name, seed=0)
+    _, sd = synth.synthetic_checkpoint(name, seed=0, nc=nc)
     monkeypatch.setenv("MI355_SPARSE_BOX", "1")
     if cap is not None:
         monkeypatch.setenv("MI355_SPARSE_CAP", str(cap))
-    sparse = YOLO.from_state_dict(name, sd, batch_chunk=chunk)
-    dense = YOLO.from_state_dict(name, sd, batch_chunk=chunk, flags=_lib.OPT_NO_SPARSE_BOX)
+    sparse = YOLO.from_state_dict(name, sd, nc=nc, batch_chunk=chunk)
+    dense = YOLO.from_state_dict(name, sd, nc=nc, batch_chunk=chunk, flags=_lib.OPT_NO_SPARSE_BOX)
     return sparse, dense, sd
 
 
@@ -161,3 +161,41 @@ def test_call_to_call_feedback_without_the_override(monkeypatch):
     assert eng.sparse_stats()["passes"] == 3
     _rows_equal(eng._infer_rows(frames, 0.25, 0.7, None, 300, 640), want_hi, "and it stays sparse (share under the bound)")
     assert eng.sparse_stats()["passes"] == 4
+
+
+def _sparse_equals_dense_and_ran(sparse, dense, frames, conf, imgsz, tag):
+    """rows equal the dense engine's, and the sparse kernels (not the fall-back) produced them"""
+    before = sparse.sparse_stats()["passes"]
+    got = sparse._infer_rows(frames, conf, 0.7, None, 300, imgsz)
+    want = dense._infer_rows(frames, conf, 0.7, None, 300, imgsz)
+    _rows_equal(got, want, tag)
+    st = sparse.sparse_stats()
+    assert st["enabled"] and st["passes"] > before and st["dense_fallbacks"] == 0 and not st["last_overflow"], (tag, st)
+    return got, st
+
+
+@pytest.mark.parametrize("nc", [1, 2])
+def test_one_and_two_class_detectors_take_the_element_wise_box_store(nc, monkeypatch):
+    """no = 5 and 6: rows of `pred` are not 16-byte aligned, so the box leaves the sparse kernel word by word.  320 x 320 frames
+    (40 / 20 / 10 levels), 5 frames in chunks of 4: a tail chunk of one frame"""
+    from tools import synth
+    sparse, dense, _ = _pair("yolov8n", monkeypatch, chunk=4, cap=1.0, nc=nc)
+    assert sparse.nc == nc
+    frames = synth.synthetic_frames(5, 320, 320, seed=1000)
+    for conf in (0.25, 0.001):
+        got, st = _sparse_equals_dense_and_ran(sparse, dense, frames, conf, 320, f"nc={nc} conf={conf}")
+        if conf == 0.001:
+            assert sum(st["candidates"]) > 0 and int(got[1].sum()) > 0, st
+    assert sparse.sparse_stats()["passes"] >= 4
+
+
+def test_rectangular_levels(monkeypatch):
+    """a uniform batch of 480 x 640 frames: the rect letterbox gives 60 x 80, 30 x 40 and 15 x 20 levels, so the kernels' y / x
+    arithmetic sees H != W"""
+    from tools import synth
+    sparse, dense, _ = _pair("yolov8n", monkeypatch, chunk=4, cap=1.0)
+    frames = synth.synthetic_frames(5, 480, 640, seed=1000)
+    for conf in (0.25, 0.001):
+        got, st = _sparse_equals_dense_and_ran(sparse, dense, frames, conf, 640, f"480x640 conf={conf}")
+        if conf == 0.001:
+            assert st["candidates"][0] > 0 and int(got[1].sum()) > 0, st
