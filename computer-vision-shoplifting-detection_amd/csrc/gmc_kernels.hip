@@ -432,376 +432,116 @@ __global__ __launch_bounds__(256) void corner_mask_kernel(const float* eig, int 
     ok[idx] = corner_mask_px(eig, h, w, __uint_as_float(*max_bits), quality, idx);
 }
 
-// per-device scratch, grow-only; calls are serialised (the tracker is sequential per video)
-struct GmcCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    uint8_t* d_planes = nullptr; size_t planes_cap = 0;        // [prev pyramid | cur pyramid]
-    float* d_pts = nullptr; float* d_next = nullptr; uint8_t* d_status = nullptr; int pts_cap = 0;
-    uint8_t* h_pin = nullptr; size_t pin_cap = 0;              // pinned staging: frames + points in, points + status out
-    uint8_t* d_front = nullptr; size_t front_cap = 0;          // frame preparation: [bgr | gray | eig | ok | tables | max]
-    uint8_t* h_front = nullptr; size_t hfront_cap = 0;
-};
-std::mutex g_mu;
-GmcCtx g_ctx[16];
-
+// ---- host side -------------------------------------------------------------------------------------------------------------------------
+// Four entry points run the same step -- the one-shot calls on g_ctx, step_begin / step_finish, track_batch, and the multi-camera tick
+// further down -- and each piece of it is stated once here: buffers, pyramid geometry, the launches, a camera's state, the host tail.
 #define GCHK(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return -2; } } while (0)
 
-// buildOpticalFlowPyramid's level geometry, stated once for every entry point: level l + 1 is ((h + 1) / 2) x ((w + 1) / 2) and exists while
-// it is larger than the window in both directions (at most max_level levels above the plane, kMaxLevels in all).  off[l]: byte offset of
-// level l in a pyramid whose planes start 256 bytes aligned; *bytes: the pyramid's size.  Returns the number of levels.
-int pyr_geometry(int h0, int w0, int max_level, int win, int* hs, int* ws, size_t* off, size_t* bytes) {
-    int levels = 1;
-    hs[0] = h0; ws[0] = w0;
-    for (int l = 0; l < max_level && levels < kMaxLevels; ++l) {
-        const int nh = (hs[levels - 1] + 1) / 2, nw = (ws[levels - 1] + 1) / 2;
-        if (nh <= win || nw <= win) break;
-        hs[levels] = nh; ws[levels] = nw; ++levels;
-    }
-    size_t total = 0;
-    for (int l = 0; l < levels; ++l) { off[l] = total; total += ((size_t)hs[l] * ws[l] + 255) & ~(size_t)255; }
-    *bytes = total;
-    return levels;
-}
+constexpr size_t al(size_t v) { return (v + 255) & ~(size_t)255; }          // every part of a staging / scratch buffer starts 256 bytes aligned
 
-}  // namespace
-
-// Same contract as mi355_gmc_pyr_lk (gmc_host.cpp) with the work done on GPU `device`: 0 = ok, -1 = bad argument, -2 = HIP error.
-extern "C" int mi355_gmc_pyr_lk_device(int device, const uint8_t* prev, const uint8_t* cur, int height, int width, const float* pts, int n,
-                                       int win, int max_level, int max_iters, double eps, double min_eig, float* next_pts, uint8_t* status) {
-    if (!prev || !cur || height <= 0 || width <= 0 || n < 0 || (n > 0 && (!pts || !next_pts || !status)) || win < 3 || !(win & 1) || win > 21 ||
-        device < 0 || device >= 16 || max_level < 0)
-        return -1;
-    if (n == 0) return 0;
-    std::lock_guard<std::mutex> lock(g_mu);
-    GCHK(hipSetDevice(device));
-    GmcCtx& c = g_ctx[device];
-    if (!c.stream) { GCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking)); c.device = device; }
-    // level geometry (buildOpticalFlowPyramid stops at levels not larger than the window)
-    int hs[kMaxLevels], ws[kMaxLevels];
-    size_t off[kMaxLevels], pyr_bytes = 0;
-    const int levels = pyr_geometry(height, width, max_level, win, hs, ws, off, &pyr_bytes);
-    if (c.planes_cap < 2 * pyr_bytes) {
-        if (c.d_planes) (void)hipFree(c.d_planes);
-        c.d_planes = nullptr; c.planes_cap = 0;
-        GCHK(hipMalloc(&c.d_planes, 2 * pyr_bytes)); c.planes_cap = 2 * pyr_bytes;
-    }
-    if (c.pts_cap < n) {
-        if (c.d_pts) (void)hipFree(c.d_pts); if (c.d_next) (void)hipFree(c.d_next); if (c.d_status) (void)hipFree(c.d_status);
-        c.d_pts = c.d_next = nullptr; c.d_status = nullptr; c.pts_cap = 0;
-        const int cap = std::max(1024, n);
-        GCHK(hipMalloc(&c.d_pts, (size_t)cap * 8)); GCHK(hipMalloc(&c.d_next, (size_t)cap * 8)); GCHK(hipMalloc(&c.d_status, (size_t)cap));
-        c.pts_cap = cap;
-    }
-    const size_t frame = (size_t)height * width;
-    const size_t pin_need = 2 * frame + (size_t)n * 8 + (size_t)n * 8 + (size_t)n + 64;
-    if (c.pin_cap < pin_need) {
-        if (c.h_pin) (void)hipHostFree(c.h_pin);
-        c.h_pin = nullptr; c.pin_cap = 0;
-        GCHK(hipHostMalloc(&c.h_pin, pin_need)); c.pin_cap = pin_need;
-    }
-    uint8_t* h_prev = c.h_pin; uint8_t* h_cur = h_prev + frame;
-    float* h_pts = (float*)(c.h_pin + ((2 * frame + 15) & ~(size_t)15));               // 16-byte aligned behind the frames
-    float* h_next = h_pts + 2 * (size_t)n;
-    uint8_t* h_status = (uint8_t*)(h_next + 2 * (size_t)n);
-    std::memcpy(h_prev, prev, frame); std::memcpy(h_cur, cur, frame); std::memcpy(h_pts, pts, (size_t)n * 8);
-    uint8_t* dp = c.d_planes; uint8_t* dc = c.d_planes + pyr_bytes;
-    GCHK(hipMemcpyAsync(dp, h_prev, frame, hipMemcpyHostToDevice, c.stream));
-    GCHK(hipMemcpyAsync(dc, h_cur, frame, hipMemcpyHostToDevice, c.stream));
-    GCHK(hipMemcpyAsync(c.d_pts, h_pts, (size_t)n * 8, hipMemcpyHostToDevice, c.stream));
-    LkArgs a{};
-    for (int l = 0; l < levels; ++l) { a.prev[l] = dp + off[l]; a.cur[l] = dc + off[l]; a.h[l] = hs[l]; a.w[l] = ws[l]; }
-    for (int l = 1; l < levels; ++l) {
-        const int np = hs[l] * ws[l];
-        hipLaunchKernelGGL(pyr_down_kernel, dim3((np + 255) / 256), dim3(256), 0, c.stream, dp + off[l - 1], hs[l - 1], ws[l - 1], dp + off[l], hs[l], ws[l]);
-        hipLaunchKernelGGL(pyr_down_kernel, dim3((np + 255) / 256), dim3(256), 0, c.stream, dc + off[l - 1], hs[l - 1], ws[l - 1], dc + off[l], hs[l], ws[l]);
-    }
-    a.top = levels - 1; a.n = n; a.win = win; a.max_iters = max_iters; a.width = width; a.height = height;
-    a.eps2 = eps * eps; a.min_eig = min_eig;
-    a.pts = c.d_pts; a.next = c.d_next; a.status = c.d_status;
-    hipLaunchKernelGGL(lk_kernel, dim3((n + kLkWaves - 1) / kLkWaves), dim3(64 * kLkWaves), 0, c.stream, a);
-    GCHK(hipGetLastError());
-    GCHK(hipMemcpyAsync(h_next, c.d_next, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
-    GCHK(hipMemcpyAsync(h_status, c.d_status, (size_t)n, hipMemcpyDeviceToHost, c.stream));
-    GCHK(hipStreamSynchronize(c.stream));
-    std::memcpy(next_pts, h_next, (size_t)n * 8); std::memcpy(status, h_status, (size_t)n);
-    return 0;
-}
-
-// Frame preparation of GMC.apply on GPU `device`: BGR frame [height][width][3] -> gray plane of (height / downscale) x (width /
-// downscale) (cv2.cvtColor + cv2.resize INTER_LINEAR, bit for bit the fixed-point arithmetic gmc.py states), the float32
-// min-eigenvalue map of cornerMinEigenVal and the 0/1 mask of the corners goodFeaturesToTrack keeps before it orders them
-// (quality threshold, 3x3 non-maximum suppression, border excluded).  xtab / ytab: per output column / row (source index, tap 0,
-// tap 1) as gmc._linear_coeffs gives them; ignored when downscale == 1.  Outputs are host buffers of oh * ow elements.
-extern "C" int mi355_gmc_prepare_device(int device, const uint8_t* bgr, int height, int width, int oh, int ow, const int* xtab, const int* ytab,
-                                        double quality, uint8_t* gray_out, float* eig_out, uint8_t* ok_out) {
-    if (!bgr || height <= 0 || width <= 0 || oh <= 0 || ow <= 0 || !gray_out || !eig_out || !ok_out || device < 0 || device >= 16) return -1;
-    const int resize = !(oh == height && ow == width);
-    if (resize && (!xtab || !ytab)) return -1;
-    std::lock_guard<std::mutex> lock(g_mu);
-    GCHK(hipSetDevice(device));
-    GmcCtx& c = g_ctx[device];
-    if (!c.stream) { GCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking)); c.device = device; }
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t nb = (size_t)height * width * 3, np = (size_t)oh * ow;
-    const size_t o_gray = al(nb), o_eig = o_gray + al(np), o_ok = o_eig + al(np * 4), o_xt = o_ok + al(np), o_yt = o_xt + al((size_t)ow * 12),
-                 o_max = o_yt + al((size_t)oh * 12), total = o_max + 256;
-    if (c.front_cap < total) {
-        if (c.d_front) (void)hipFree(c.d_front);
-        c.d_front = nullptr; c.front_cap = 0;
-        GCHK(hipMalloc(&c.d_front, total)); c.front_cap = total;
-    }
-    const size_t h_in = al(nb) + al((size_t)ow * 12) + al((size_t)oh * 12), h_total = h_in + al(np) + al(np * 4) + al(np);
-    if (c.hfront_cap < h_total) {
-        if (c.h_front) (void)hipHostFree(c.h_front);
-        c.h_front = nullptr; c.hfront_cap = 0;
-        GCHK(hipHostMalloc(&c.h_front, h_total)); c.hfront_cap = h_total;
-    }
-    uint8_t* hp = c.h_front;
-    uint8_t* h_bgr = hp; uint8_t* h_xt = hp + al(nb); uint8_t* h_yt = h_xt + al((size_t)ow * 12);
-    uint8_t* h_gray = hp + h_in; uint8_t* h_eig = h_gray + al(np); uint8_t* h_ok = h_eig + al(np * 4);
-    std::memcpy(h_bgr, bgr, nb);
-    GCHK(hipMemcpyAsync(c.d_front, h_bgr, nb, hipMemcpyHostToDevice, c.stream));
-    if (resize) {
-        std::memcpy(h_xt, xtab, (size_t)ow * 12); std::memcpy(h_yt, ytab, (size_t)oh * 12);
-        GCHK(hipMemcpyAsync(c.d_front + o_xt, h_xt, (size_t)ow * 12, hipMemcpyHostToDevice, c.stream));
-        GCHK(hipMemcpyAsync(c.d_front + o_yt, h_yt, (size_t)oh * 12, hipMemcpyHostToDevice, c.stream));
-    }
-    GCHK(hipMemsetAsync(c.d_front + o_max, 0, 4, c.stream));
-    const unsigned blocks = (unsigned)((np + 255) / 256);
-    hipLaunchKernelGGL(gray_resize_kernel, dim3(blocks), dim3(256), 0, c.stream, c.d_front, height, width, (const int*)(c.d_front + o_xt),
-                       (const int*)(c.d_front + o_yt), c.d_front + o_gray, oh, ow, resize);
-    hipLaunchKernelGGL(min_eig_kernel, dim3(blocks), dim3(256), 0, c.stream, c.d_front + o_gray, oh, ow, (float*)(c.d_front + o_eig),
-                       (unsigned*)(c.d_front + o_max));
-    hipLaunchKernelGGL(corner_mask_kernel, dim3(blocks), dim3(256), 0, c.stream, (const float*)(c.d_front + o_eig), oh, ow,
-                       (const unsigned*)(c.d_front + o_max), quality, c.d_front + o_ok);
-    GCHK(hipGetLastError());
-    GCHK(hipMemcpyAsync(h_gray, c.d_front + o_gray, np, hipMemcpyDeviceToHost, c.stream));
-    GCHK(hipMemcpyAsync(h_eig, c.d_front + o_eig, np * 4, hipMemcpyDeviceToHost, c.stream));
-    GCHK(hipMemcpyAsync(h_ok, c.d_front + o_ok, np, hipMemcpyDeviceToHost, c.stream));
-    GCHK(hipStreamSynchronize(c.stream));
-    std::memcpy(gray_out, h_gray, np); std::memcpy(eig_out, h_eig, np * 4); std::memcpy(ok_out, h_ok, np);
-    return 0;
-}
-
-// ---- one motion-compensation step as two calls: enqueue, then collect ------------------------------------------------------------
-// model.track() enqueues the step for a frame BEFORE the detector runs on it and collects it when the tracker asks for the warp: the
-// frame preparation and the optical flow (0.7 ms for a thousand corners) then run beside the detector pass on a stream of their own
-// instead of after it.  The object keeps the previous frame's pyramid on the device (two slots, swapped per step).
-struct mi355_gmc {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    uint8_t* d_front = nullptr; size_t front_cap = 0;          // [bgr | eig | ok | x table | y table | max]
-    uint8_t* d_pyr[2] = {nullptr, nullptr}; size_t pyr_cap = 0;
-    int slot = 0; bool have_prev = false; int ph = 0, pw = 0;  // the slot and plane size of the last prepared frame
-    int tab_key[4] = {0, 0, 0, 0};                             // (height, width, oh, ow) the resize tables on the device belong to
-    float* d_pts = nullptr; float* d_next = nullptr; uint8_t* d_status = nullptr; int pts_cap = 0;
-    uint8_t* h_pin = nullptr; size_t pin_cap = 0;
-    hipEvent_t ev_up = nullptr; int up_h = 0, up_w = 0;        // recorded behind the pending step's frame upload (mi355_gmc_pending_frame)
-    // the pending step
-    bool pending = false; int oh = 0, ow = 0, n_lk = 0;
-    size_t o_hgray = 0, o_heig = 0, o_hok = 0, o_hnext = 0, o_hstatus = 0;
-    // ---- GMC.apply_sparseoptflow's state machine (mi355_gmc_track_*): the previous frame's plane and ordered corners live here, so a
-    // step is two calls from the tracker's language binding (enqueue, collect -> 2 x 3 matrix) and nothing per frame is done in it
-    bool host = false;                                         // mi355_gmc_create(-1): every stage in host C++ (csrc/gmc_host.cpp)
-    int downscale = 2;
-    std::vector<int> xt, yt; int tkey[4] = {0, 0, 0, 0};       // INTER_LINEAR tables of (height, width, oh, ow)
-    std::vector<uint8_t> prev_gray, cur_gray, ok; std::vector<float> eig;
-    std::vector<float> prev_pts, lk_pts, next_pts; std::vector<uint8_t> status;
-    int prev_h = 0, prev_w = 0; bool have_prev_pts = false;
-    bool track_pending = false; int t_oh = 0, t_ow = 0, t_n = 0;
-    std::vector<uint8_t> host_frame; int hf_h = 0, hf_w = 0;   // host object: the frame of the pending step
-    // collect worker (device objects): the host half of a step -- wait for the stream, order the new corners, RANSAC -- runs on a thread of
-    // its own from the moment track_begin has enqueued the step, i.e. beside the detector pass the caller runs next; track_finish joins it
-    std::thread worker; std::mutex mu; std::condition_variable cv;
-    bool job_ready = false, job_done = false, worker_stop = false; int job_rc = 0; double job_H[6] = {1, 0, 0, 0, 1, 0};
-    // mi355_gmc_batch_frames: the frames of the batch a (concurrent) mi355_gmc_track_batch call has uploaded
-    hipEvent_t ev_batch_up = nullptr; unsigned long long batch_up_seq = 0; int batch_n = 0, batch_h = 0, batch_w = 0; size_t batch_fstride = 0;
-    bool batch_failed = false;
-    bool job_active = false;                                   // written by the calling thread only: this step's collect belongs to the worker
-    // mi355_gmc_track_batch: device buffers of one batch (grow-only) and their pinned mirror
-    uint8_t* d_batch = nullptr; size_t batch_cap = 0;
-    uint8_t* h_batch = nullptr; size_t hbatch_cap = 0;
+// Grow-only buffer in device or pinned host memory.  The owner says what it needs and, where it keeps slack, what to allocate instead;
+// what a reallocation invalidates is the owner's business too: buf_grow tells it.
+struct Buf {
+    bool pinned = false;
+    uint8_t* p = nullptr; size_t cap = 0;
 };
+void buf_free(Buf& b) {
+    if (b.p) (void)(b.pinned ? hipHostFree(b.p) : hipFree(b.p));
+    b.p = nullptr; b.cap = 0;
+}
+// 0 = large enough as it is, 1 = reallocated at max(need, alloc) bytes (the contents are gone), -2 = HIP error (the buffer is empty)
+int buf_grow(Buf& b, size_t need, size_t alloc = 0) {
+    if (b.cap >= need) return 0;
+    buf_free(b);
+    alloc = std::max(alloc, need);
+    GCHK(b.pinned ? hipHostMalloc(&b.p, alloc) : hipMalloc(&b.p, alloc));
+    b.cap = alloc;
+    return 1;
+}
+// a device buffer and its pinned mirror, a quarter of slack on both
+int grow_pair(Buf& d, Buf& h, size_t need) {
+    const int rd = buf_grow(d, need, need + need / 4), rh = buf_grow(h, need, need + need / 4);
+    return (rd < 0 || rh < 0) ? -2 : (rd | rh);
+}
+// the device side of a Lucas-Kanade launch: points in [n][2], points out [n][2], status [n]; room for 1024 points at least
+struct PtsBufs {
+    Buf pts, next, status;
+};
+int grow_points(PtsBufs& b, int n) {
+    const size_t cap = (size_t)std::max(1024, n);
+    return (buf_grow(b.pts, (size_t)n * 8, cap * 8) < 0 || buf_grow(b.next, (size_t)n * 8, cap * 8) < 0 || buf_grow(b.status, (size_t)n, cap) < 0) ? -2 : 0;
+}
+void free_points(PtsBufs& b) { buf_free(b.pts); buf_free(b.next); buf_free(b.status); }
 
-extern "C" int mi355_gmc_create(int device, mi355_gmc** out) {
-    if (!out || device < -1) return -1;
-    *out = nullptr;
-    if (device == -1) {                                         // host object: no HIP call is ever made through it
-        mi355_gmc* g = new mi355_gmc();
-        g->device = -1; g->host = true;
-        *out = g;
-        return 0;
+// buildOpticalFlowPyramid's level geometry: level l + 1 is ((h + 1) / 2) x ((w + 1) / 2) and exists while it is larger than the window in
+// both directions (at most max_level levels above the plane, kMaxLevels in all).  off[l]: byte offset of level l in a pyramid whose planes
+// start 256 bytes aligned; bytes: the pyramid's size.
+struct PyrGeom {
+    int levels; int hs[kMaxLevels], ws[kMaxLevels];
+    size_t off[kMaxLevels], bytes;
+};
+PyrGeom pyr_geometry(int h0, int w0, int max_level, int win) {
+    PyrGeom q{};
+    q.levels = 1; q.hs[0] = h0; q.ws[0] = w0;
+    for (int l = 0; l < max_level && q.levels < kMaxLevels; ++l) {
+        const int nh = (q.hs[q.levels - 1] + 1) / 2, nw = (q.ws[q.levels - 1] + 1) / 2;
+        if (nh <= win || nw <= win) break;
+        q.hs[q.levels] = nh; q.ws[q.levels] = nw; ++q.levels;
     }
-    GCHK(hipSetDevice(device));
-    mi355_gmc* g = new mi355_gmc();
-    g->device = device;
-    // The step runs BESIDE the detector pass (model.track enqueues it first), on a stream of its own at the default priority.  Measured
-    // (tools/track_prio_ab.sh, round 4): giving this stream the LOWEST and the detector's the HIGHEST priority does not speed the detector
-    // up (637-644 us per frame either way) and delays the collect (119-139 -> 163-171 us): 805-838 -> 863-893 us per frame.
-    // MI355_GMC_PRIO=1 asks for the lowest priority (A/B only).
-    int least = 0, greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-    static const bool low_prio = getenv("MI355_GMC_PRIO") && atoi(getenv("MI355_GMC_PRIO")) == 1;
-    if (hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, low_prio ? least : 0) != hipSuccess) { (void)hipGetLastError(); delete g; return -2; }
-    *out = g;
-    return 0;
+    for (int l = 0; l < q.levels; ++l) { q.off[l] = q.bytes; q.bytes += al((size_t)q.hs[l] * q.ws[l]); }
+    return q;
 }
 
-extern "C" void mi355_gmc_destroy(mi355_gmc* g) {
-    if (g && g->worker.joinable()) {
-        { std::lock_guard<std::mutex> lk(g->mu); g->worker_stop = true; }
-        g->cv.notify_all();
-        g->worker.join();
-    }
-    if (!g) return;
-    if (g->host) { delete g; return; }
-    (void)hipSetDevice(g->device);
-    if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
-    if (g->ev_up) (void)hipEventDestroy(g->ev_up);
-    if (g->ev_batch_up) (void)hipEventDestroy(g->ev_batch_up);
-    if (g->d_front) (void)hipFree(g->d_front);
-    for (int i = 0; i < 2; ++i) if (g->d_pyr[i]) (void)hipFree(g->d_pyr[i]);
-    if (g->d_pts) (void)hipFree(g->d_pts); if (g->d_next) (void)hipFree(g->d_next); if (g->d_status) (void)hipFree(g->d_status);
-    if (g->h_pin) (void)hipHostFree(g->h_pin);
-    if (g->d_batch) (void)hipFree(g->d_batch);
-    if (g->h_batch) (void)hipHostFree(g->h_batch);
-    delete g;
+// level l - 1 -> level l of `count` pyramids that lie `stride` bytes apart
+void enqueue_pyr_down(hipStream_t s, int count, uint8_t* pyr, size_t stride, const PyrGeom& q, int l) {
+    const int np = q.hs[l] * q.ws[l];
+    hipLaunchKernelGGL(pyr_down_kernel, dim3((np + 255) / 256, count), dim3(256), 0, s, pyr + q.off[l - 1], q.hs[l - 1], q.ws[l - 1], pyr + q.off[l], q.hs[l], q.ws[l],
+                       stride);
 }
 
-// Enqueue one step: frame preparation of `bgr` (as mi355_gmc_prepare_device) and, when n_prev > 0, Lucas-Kanade tracking of the
-// n_prev points `prev_pts` from the PREVIOUS step's plane into this one (as mi355_gmc_pyr_lk_device; the previous step must have
-// prepared a plane of the same oh x ow).  Returns at once; nothing of `bgr` / `prev_pts` is read after the call returns.
-extern "C" int mi355_gmc_step_begin(mi355_gmc* g, const uint8_t* bgr, int height, int width, int oh, int ow, const int* xtab, const int* ytab,
-                                    double quality, const float* prev_pts, int n_prev, int win, int max_level, int max_iters, double eps,
-                                    double min_eig) {
-    if (g && g->host) return -1;
-    if (!g || !bgr || height <= 0 || width <= 0 || oh <= 0 || ow <= 0 || n_prev < 0 || (n_prev > 0 && !prev_pts) || win < 3 || !(win & 1) || win > 21 ||
-        max_level < 0)
-        return -1;
-    const int resize = !(oh == height && ow == width);
-    if (resize && (!xtab || !ytab)) return -1;
-    if (g->pending) return -1;                                  // collect the previous step first
-    if (n_prev > 0 && !(g->have_prev && g->ph == oh && g->pw == ow)) return -1;
-    GCHK(hipSetDevice(g->device));
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t nb = (size_t)height * width * 3, np = (size_t)oh * ow;
-    // pyramid geometry of the oh x ow plane
-    int hs[kMaxLevels], ws[kMaxLevels];
-    size_t off[kMaxLevels], pyr_bytes = 0;
-    const int levels = pyr_geometry(oh, ow, max_level, win, hs, ws, off, &pyr_bytes);
-    if (g->pyr_cap < pyr_bytes) {
-        for (int i = 0; i < 2; ++i) { if (g->d_pyr[i]) (void)hipFree(g->d_pyr[i]); g->d_pyr[i] = nullptr; }
-        g->pyr_cap = 0; g->have_prev = false;
-        if (n_prev > 0) return -1;
-        GCHK(hipMalloc(&g->d_pyr[0], pyr_bytes)); GCHK(hipMalloc(&g->d_pyr[1], pyr_bytes)); g->pyr_cap = pyr_bytes;
-    }
-    const size_t o_eig = al(nb), o_ok = o_eig + al(np * 4), o_xt = o_ok + al(np), o_yt = o_xt + al((size_t)ow * 12), o_max = o_yt + al((size_t)oh * 12),
-                 total = o_max + 256;
-    if (g->front_cap < total) {
-        if (g->d_front) (void)hipFree(g->d_front);
-        g->d_front = nullptr; g->front_cap = 0; g->tab_key[0] = 0;
-        GCHK(hipMalloc(&g->d_front, total)); g->front_cap = total;
-    }
-    if (g->pts_cap < n_prev) {
-        if (g->d_pts) (void)hipFree(g->d_pts); if (g->d_next) (void)hipFree(g->d_next); if (g->d_status) (void)hipFree(g->d_status);
-        g->d_pts = g->d_next = nullptr; g->d_status = nullptr; g->pts_cap = 0;
-        const int cap = std::max(1024, n_prev);
-        GCHK(hipMalloc(&g->d_pts, (size_t)cap * 8)); GCHK(hipMalloc(&g->d_next, (size_t)cap * 8)); GCHK(hipMalloc(&g->d_status, (size_t)cap));
-        g->pts_cap = cap;
-    }
-    // pinned staging: [bgr | x table | y table | prev points] in, [gray | eig | ok | next points | status] out
-    const size_t i_xt = al(nb), i_yt = i_xt + al((size_t)ow * 12), i_pts = i_yt + al((size_t)oh * 12), i_end = i_pts + al((size_t)n_prev * 8);
-    g->o_hgray = i_end; g->o_heig = g->o_hgray + al(np); g->o_hok = g->o_heig + al(np * 4); g->o_hnext = g->o_hok + al(np);
-    g->o_hstatus = g->o_hnext + al((size_t)n_prev * 8);
-    const size_t pin_need = g->o_hstatus + al((size_t)n_prev) + 256;
-    if (g->pin_cap < pin_need) {
-        if (g->h_pin) (void)hipHostFree(g->h_pin);
-        g->h_pin = nullptr; g->pin_cap = 0;
-        GCHK(hipHostMalloc(&g->h_pin, pin_need)); g->pin_cap = pin_need;
-    }
-    uint8_t* hp = g->h_pin;
-    std::memcpy(hp, bgr, nb);
-    GCHK(hipMemcpyAsync(g->d_front, hp, nb, hipMemcpyHostToDevice, g->stream));
-    if (!g->ev_up) GCHK(hipEventCreateWithFlags(&g->ev_up, hipEventDisableTiming));
-    GCHK(hipEventRecord(g->ev_up, g->stream)); g->up_h = height; g->up_w = width;
-    if (resize && !(g->tab_key[0] == height && g->tab_key[1] == width && g->tab_key[2] == oh && g->tab_key[3] == ow)) {
-        std::memcpy(hp + i_xt, xtab, (size_t)ow * 12); std::memcpy(hp + i_yt, ytab, (size_t)oh * 12);
-        GCHK(hipMemcpyAsync(g->d_front + o_xt, hp + i_xt, (size_t)ow * 12, hipMemcpyHostToDevice, g->stream));
-        GCHK(hipMemcpyAsync(g->d_front + o_yt, hp + i_yt, (size_t)oh * 12, hipMemcpyHostToDevice, g->stream));
-        g->tab_key[0] = height; g->tab_key[1] = width; g->tab_key[2] = oh; g->tab_key[3] = ow;
-    }
-    GCHK(hipMemsetAsync(g->d_front + o_max, 0, 4, g->stream));
-    const int nslot = g->slot ^ 1;
-    uint8_t* dc = g->d_pyr[nslot];
-    uint8_t* dp = g->d_pyr[g->slot];
-    const unsigned blocks = (unsigned)((np + 255) / 256);
-    hipLaunchKernelGGL(gray_resize_kernel, dim3(blocks), dim3(256), 0, g->stream, g->d_front, height, width, (const int*)(g->d_front + o_xt),
-                       (const int*)(g->d_front + o_yt), dc + off[0], oh, ow, resize);
-    hipLaunchKernelGGL(min_eig_kernel, dim3(blocks), dim3(256), 0, g->stream, dc + off[0], oh, ow, (float*)(g->d_front + o_eig),
-                       (unsigned*)(g->d_front + o_max));
-    hipLaunchKernelGGL(corner_mask_kernel, dim3(blocks), dim3(256), 0, g->stream, (const float*)(g->d_front + o_eig), oh, ow,
-                       (const unsigned*)(g->d_front + o_max), quality, g->d_front + o_ok);
-    for (int l = 1; l < levels; ++l) {
-        const int npx = hs[l] * ws[l];
-        hipLaunchKernelGGL(pyr_down_kernel, dim3((npx + 255) / 256), dim3(256), 0, g->stream, dc + off[l - 1], hs[l - 1], ws[l - 1], dc + off[l], hs[l], ws[l]);
-    }
-    if (n_prev > 0) {
-        std::memcpy(hp + i_pts, prev_pts, (size_t)n_prev * 8);
-        GCHK(hipMemcpyAsync(g->d_pts, hp + i_pts, (size_t)n_prev * 8, hipMemcpyHostToDevice, g->stream));
-        LkArgs a{};
-        for (int l = 0; l < levels; ++l) { a.prev[l] = dp + off[l]; a.cur[l] = dc + off[l]; a.h[l] = hs[l]; a.w[l] = ws[l]; }
-        a.top = levels - 1; a.n = n_prev; a.win = win; a.max_iters = max_iters; a.width = ow; a.height = oh;
-        a.eps2 = eps * eps; a.min_eig = min_eig;
-        a.pts = g->d_pts; a.next = g->d_next; a.status = g->d_status;
-        hipLaunchKernelGGL(lk_kernel, dim3((n_prev + kLkWaves - 1) / kLkWaves), dim3(64 * kLkWaves), 0, g->stream, a);
-        GCHK(hipMemcpyAsync(hp + g->o_hnext, g->d_next, (size_t)n_prev * 8, hipMemcpyDeviceToHost, g->stream));
-        GCHK(hipMemcpyAsync(hp + g->o_hstatus, g->d_status, (size_t)n_prev, hipMemcpyDeviceToHost, g->stream));
-    }
-    GCHK(hipGetLastError());
-    GCHK(hipMemcpyAsync(hp + g->o_hgray, dc + off[0], np, hipMemcpyDeviceToHost, g->stream));
-    GCHK(hipMemcpyAsync(hp + g->o_heig, g->d_front + o_eig, np * 4, hipMemcpyDeviceToHost, g->stream));
-    GCHK(hipMemcpyAsync(hp + g->o_hok, g->d_front + o_ok, np, hipMemcpyDeviceToHost, g->stream));
-    g->slot = nslot; g->have_prev = true; g->ph = oh; g->pw = ow;
-    g->pending = true; g->oh = oh; g->ow = ow; g->n_lk = n_prev;
-    return 0;
+// The frame preparation of `count` frames as one set of launches: the BGR frame at src + f * src_stride becomes level 0 of the pyramid at
+// pyr + f * pyr_stride (q: its geometry), its min-eigenvalue map and corner mask go to eig / ok + f * plane, its maximum to max_bits[f] (zeroed
+// by the caller); then the pyramid's upper levels.  xtab / ytab: the INTER_LINEAR tables on the device (not read unless `resize`).
+void enqueue_prepare(hipStream_t s, int count, const uint8_t* src, size_t src_stride, int H, int W, const int* xtab, const int* ytab, int resize, uint8_t* pyr,
+                     size_t pyr_stride, float* eig, uint8_t* ok, unsigned* max_bits, double quality, const PyrGeom& q) {
+    const int oh = q.hs[0], ow = q.ws[0];
+    const dim3 grid((unsigned)(((size_t)oh * ow + 255) / 256), count);
+    hipLaunchKernelGGL(gray_resize_kernel, grid, dim3(256), 0, s, src, H, W, xtab, ytab, pyr, oh, ow, resize, src_stride, pyr_stride);
+    hipLaunchKernelGGL(min_eig_kernel, grid, dim3(256), 0, s, pyr, oh, ow, eig, max_bits, pyr_stride);
+    hipLaunchKernelGGL(corner_mask_kernel, grid, dim3(256), 0, s, eig, oh, ow, max_bits, quality, ok);
+    for (int l = 1; l < q.levels; ++l) enqueue_pyr_down(s, count, pyr, pyr_stride, q, l);
 }
 
-// The frame of the pending step as it sits on the device (dense BGR [height][width][3], uploaded once by mi355_gmc_step_begin): waits -- on
-// the host, ~10 us -- until that upload has landed and hands out the pointer, so that the detector pass of the same frame
-// (mi355_yolo_infer_device) reads this copy instead of uploading its own.  Besides saving the second upload this is what lets the two
-// overlap at all: a second host -> device copy queues up behind the step's device -> host copies, which wait for its Lucas-Kanade launch
-// (measured: the detector's first kernel started when the whole step was over, tools/track_timeline.py).  Valid until the next step_begin.
-extern "C" int mi355_gmc_pending_frame(mi355_gmc* g, const uint8_t** dev_bgr, int* height, int* width) {
-    if (!g || g->host || !(g->pending || g->track_pending) || !g->ev_up || !dev_bgr || !height || !width) return -1;
-    GCHK(hipSetDevice(g->device));
-    GCHK(hipEventSynchronize(g->ev_up));
-    *dev_bgr = g->d_front; *height = g->up_h; *width = g->up_w;
-    return 0;
+// Lucas-Kanade from the pyramid at `prev` into the one at `cur` (both of geometry q): n points -- or, with n_arr, `pairs` frame pairs in ONE
+// launch: pair p tracks n_arr[p] <= n points from prev + p * pair_stride into cur + p * pair_stride, its points / results at p * n.
+struct LkParams {
+    int win, max_iters; double eps, min_eig;
+};
+void enqueue_lk(hipStream_t s, const PyrGeom& q, const uint8_t* prev, const uint8_t* cur, const LkParams& k, const float* pts, float* next, uint8_t* status, int n,
+                int pairs = 1, size_t pair_stride = 0, const int* n_arr = nullptr) {
+    LkArgs a{};
+    for (int l = 0; l < q.levels; ++l) { a.prev[l] = prev + q.off[l]; a.cur[l] = cur + q.off[l]; a.h[l] = q.hs[l]; a.w[l] = q.ws[l]; }
+    a.top = q.levels - 1; a.n = n_arr ? 0 : n; a.win = k.win; a.max_iters = k.max_iters; a.width = q.ws[0]; a.height = q.hs[0];
+    a.eps2 = k.eps * k.eps; a.min_eig = k.min_eig;
+    a.pts = pts; a.next = next; a.status = status;
+    a.pair_stride = pair_stride; a.max_pts = n_arr ? n : 0; a.n_arr = n_arr;
+    hipLaunchKernelGGL(lk_kernel, dim3((n + kLkWaves - 1) / kLkWaves, pairs), dim3(64 * kLkWaves), 0, s, a);
 }
 
-// Collect the enqueued step: gray / eig / ok of oh * ow elements, next_pts [n_prev][2] and status [n_prev] (untouched when the step
-// had n_prev == 0).
-extern "C" int mi355_gmc_step_finish(mi355_gmc* g, uint8_t* gray_out, float* eig_out, uint8_t* ok_out, float* next_pts, uint8_t* status) {
-    if (!g || g->host || !g->pending || !gray_out || !eig_out || !ok_out || (g->n_lk > 0 && (!next_pts || !status))) return -1;
-    GCHK(hipSetDevice(g->device));
-    g->pending = false;
-    if (hipStreamSynchronize(g->stream) != hipSuccess) { (void)hipGetLastError(); g->have_prev = false; return -2; }
-    const size_t np = (size_t)g->oh * g->ow;
-    std::memcpy(gray_out, g->h_pin + g->o_hgray, np); std::memcpy(eig_out, g->h_pin + g->o_heig, np * 4); std::memcpy(ok_out, g->h_pin + g->o_hok, np);
-    if (g->n_lk > 0) { std::memcpy(next_pts, g->h_pin + g->o_hnext, (size_t)g->n_lk * 8); std::memcpy(status, g->h_pin + g->o_hstatus, (size_t)g->n_lk); }
-    return 0;
+// "run body(i) for i in 0 .. n - 1 on nthreads threads" (inline when that is one); host_threads: how many a step of n items gets
+int host_threads(int n) { return std::max(1, std::min(std::min(8, n), (int)std::thread::hardware_concurrency())); }
+template <class F>
+void parallel_for(int n, int nthreads, F&& body) {
+    if (nthreads <= 1) { for (int i = 0; i < n; ++i) body(i); return; }
+    std::vector<std::thread> th;
+    for (int t = 0; t < nthreads; ++t) th.emplace_back([&, t] { for (int i = t; i < n; i += nthreads) body(i); });
+    for (auto& t : th) t.join();
 }
 
-// ---- the whole step of GMC.apply_sparseoptflow on the object (ultralytics/trackers/utils/gmc.py, reached from /root/reference/model.py:38) ----
-// track_begin = enqueue: frame preparation of `bgr` and Lucas-Kanade tracking of the previous frame's corners into it (GPU object: on the
-// object's stream, returns at once; host object: the frame is copied and the work happens in track_finish).  track_finish = collect:
-// orders the new frame's corners (kept for the next step), estimates the partial affine transform prev -> cur from the tracked pairs
-// (RANSAC, seed 0) when more than 4 survive, scales its translation back to frame pixels.  H_out: 6 doubles, row-major 2 x 3; the
-// identity on the first frame of a plane size, when the previous frame had no corners, or when too few points were tracked.
-namespace {
-constexpr int kMaxCorners = 1000, kLkWin = 21, kLkLevels = 3, kLkIters = 30;
-constexpr double kQuality = 0.01, kLkEps = 0.01, kLkMinEig = 1e-4, kRansacThr = 3.0, kRansacConf = 0.99;
+// ---- GMC.apply_sparseoptflow (ultralytics/trackers/utils/gmc.py): its parameters, one camera's state, the host half of a step ---------
+constexpr int kMaxCorners = 1000, kLkLevels = 3;
+constexpr LkParams kLk = {21, 30, 0.01, 1e-4};
+constexpr double kQuality = 0.01, kRansacThr = 3.0, kRansacConf = 0.99;
 constexpr int kRansacIters = 2000;
 
 // INTER_LINEAR sample table of a dn-long axis resampled from sn: (source index, tap 0, tap 1), 11-bit taps, float32 coordinates as cv2
@@ -820,56 +560,373 @@ void linear_table(int dn, int sn, std::vector<int>& tab) {
     }
 }
 
-// The host half of a step behind the kernels (one statement, for the single object and the multi-camera one): the partial affine transform
-// prev -> cur from the tracked pairs (RANSAC, seed 0) when more than 4 survive, its translation scaled back to frame pixels -- else the
-// identity; then this frame's corners, strongest first, into prev_pts for the next step.
-void step_tail(const float* lk_pts, const float* next_pts, const uint8_t* status, int n, int downscale, const float* eig, const uint8_t* ok, int oh, int ow,
-               std::vector<float>& prev_pts, double* H) {
+// the (height, width, oh, ow) a pair of resize tables belongs to
+bool key_is(const int* k, int H, int W, int oh, int ow) { return k[0] == H && k[1] == W && k[2] == oh && k[3] == ow; }
+void key_set(int* k, int H, int W, int oh, int ow) { k[0] = H; k[1] = W; k[2] = oh; k[3] = ow; }
+
+// One camera's state between steps: the previous frame's plane and ordered corners on the host, and -- device objects -- which pyramid slot
+// holds that frame and which tables the device has.  mi355_gmc has one, mi355_gmc_multi one per camera.
+struct CamState {
+    std::vector<int> xt, yt; int tkey[4] = {0, 0, 0, 0};       // INTER_LINEAR tables of (height, width, oh, ow)
+    std::vector<float> prev_pts, lk_pts; std::vector<uint8_t> prev_gray;
+    int prev_h = 0, prev_w = 0; bool have_prev_pts = false;
+    int slot = 0; bool have_prev = false; int ph = 0, pw = 0;  // the slot and plane size of the last prepared frame
+    int tab_key[4] = {0, 0, 0, 0};                             // (height, width, oh, ow) the resize tables on the device belong to
+};
+// make the host tables current for (H, W, oh, ow)
+void cam_tables(CamState& c, int H, int W, int oh, int ow) {
+    if (key_is(c.tkey, H, W, oh, ow)) return;
+    linear_table(ow, W, c.xt); linear_table(oh, H, c.yt);
+    key_set(c.tkey, H, W, oh, ow);
+}
+// does the previous frame precede a frame of plane size oh x ow?  (corners known, same size; on_device: and its pyramid is there)
+bool cam_follows(const CamState& c, int oh, int ow, bool on_device) {
+    return c.have_prev_pts && c.prev_h == oh && c.prev_w == ow && (!on_device || (c.have_prev && c.ph == oh && c.pw == ow));
+}
+// What this frame tracks: the previous frame's corners, only into a plane of the same size (GMC.apply resets otherwise) -> lk_pts; returns
+// their number.  When there are none the device pyramid is no predecessor either.
+int cam_decide(CamState& c, int oh, int ow, bool on_device) {
+    const bool lk = cam_follows(c, oh, ow, on_device) && !c.prev_pts.empty();
+    c.lk_pts.clear();
+    if (lk) c.lk_pts = c.prev_pts; else c.have_prev = false;
+    return (int)(c.lk_pts.size() / 2);
+}
+// this frame (its plane in prev_gray, its corners in prev_pts by now) becomes the previous one
+void cam_advance(CamState& c, int oh, int ow) { c.prev_h = oh; c.prev_w = ow; c.have_prev_pts = true; }
+// a step's results never arrived: nothing precedes the next frame
+void cam_lost(CamState& c) { c.have_prev = false; c.have_prev_pts = false; }
+// GMC.reset_params
+void cam_forget(CamState& c) {
+    cam_lost(c);
+    c.prev_pts.clear(); c.prev_gray.clear(); c.prev_h = c.prev_w = 0;
+}
+// the previous frame as the object holds it (tests): plane size, number of corners; gray_out [oh * ow] and pts_out [pts_cap][2] when given
+void cam_report(const CamState& c, int* oh, int* ow, int* n_pts, uint8_t* gray_out, float* pts_out, int pts_cap) {
+    const int n = c.have_prev_pts ? (int)(c.prev_pts.size() / 2) : 0;
+    if (oh) *oh = c.have_prev_pts ? c.prev_h : 0;
+    if (ow) *ow = c.have_prev_pts ? c.prev_w : 0;
+    if (n_pts) *n_pts = n;
+    if (gray_out && c.have_prev_pts) std::memcpy(gray_out, c.prev_gray.data(), c.prev_gray.size());
+    if (pts_out && pts_cap > 0 && n > 0) std::memcpy(pts_out, c.prev_pts.data(), (size_t)std::min(n, pts_cap) * 8);
+}
+
+// The host half of a step behind the kernels, in two parts (the batched entry point needs them apart: pair f tracks frame f - 1's corners).
+// tail_warp: the partial affine transform prev -> cur from the tracked pairs (RANSAC, seed 0) when more than 4 survive, its translation scaled
+// back to frame pixels -- else the identity.  tail_corners: a frame's corners, strongest first, as the next step tracks them.
+void tail_warp(const float* lk_pts, const float* next_pts, const uint8_t* status, int n, int downscale, double* H) {
     H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0;
-    if (n > 0) {
-        std::vector<double> src, dst;
-        for (int i = 0; i < n; ++i)
-            if (status[i]) {
-                src.push_back(lk_pts[2 * i]); src.push_back(lk_pts[2 * i + 1]);
-                dst.push_back(next_pts[2 * i]); dst.push_back(next_pts[2 * i + 1]);
-            }
-        const int m = (int)(src.size() / 2);
-        if (m > 4) {
-            double E[6];
-            if (mi355_gmc_affine_partial(src.data(), dst.data(), m, kRansacThr, kRansacConf, kRansacIters, 0ull, E, nullptr) == 1) {
-                std::memcpy(H, E, sizeof(E));
-                H[2] *= downscale; H[5] *= downscale;
-            }
+    std::vector<double> src, dst;
+    for (int i = 0; i < n; ++i)
+        if (status[i]) {
+            src.push_back(lk_pts[2 * i]); src.push_back(lk_pts[2 * i + 1]);
+            dst.push_back(next_pts[2 * i]); dst.push_back(next_pts[2 * i + 1]);
         }
+    const int m = (int)(src.size() / 2);
+    double E[6];
+    if (m > 4 && mi355_gmc_affine_partial(src.data(), dst.data(), m, kRansacThr, kRansacConf, kRansacIters, 0ull, E, nullptr) == 1) {
+        std::memcpy(H, E, sizeof(E));
+        H[2] *= downscale; H[5] *= downscale;
     }
-    // this frame becomes the previous one: its corners, strongest first
-    prev_pts.resize((size_t)kMaxCorners * 2);
-    const int nc = mi355_gmc_order_corners(eig, ok, oh, ow, kMaxCorners, prev_pts.data());
-    prev_pts.resize((size_t)std::max(nc, 0) * 2);
+}
+void tail_corners(const float* eig, const uint8_t* ok, int oh, int ow, std::vector<float>& pts) {
+    pts.resize((size_t)kMaxCorners * 2);
+    const int nc = mi355_gmc_order_corners(eig, ok, oh, ow, kMaxCorners, pts.data());
+    pts.resize((size_t)std::max(nc, 0) * 2);
+}
+
+// one-shot calls: per-device scratch, grow-only; calls are serialised (the tracker is sequential per video)
+struct GmcCtx {
+    hipStream_t stream = nullptr;
+    Buf planes;                                                // [prev pyramid | cur pyramid]
+    PtsBufs lk;
+    Buf h_pin{true};                                           // pinned staging: frames + points in, points + status out
+    Buf front, h_front{true};                                  // frame preparation: [bgr | gray | eig | ok | tables | max]
+};
+std::mutex g_mu;
+GmcCtx g_ctx[16];
+int one_shot_ctx(int device, GmcCtx** out) {
+    GCHK(hipSetDevice(device));
+    GmcCtx& c = g_ctx[device];
+    if (!c.stream) GCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    *out = &c;
+    return 0;
+}
+
+}  // namespace
+
+// Same contract as mi355_gmc_pyr_lk (gmc_host.cpp) with the work done on GPU `device`: 0 = ok, -1 = bad argument, -2 = HIP error.
+extern "C" int mi355_gmc_pyr_lk_device(int device, const uint8_t* prev, const uint8_t* cur, int height, int width, const float* pts, int n,
+                                       int win, int max_level, int max_iters, double eps, double min_eig, float* next_pts, uint8_t* status) {
+    if (!prev || !cur || height <= 0 || width <= 0 || n < 0 || (n > 0 && (!pts || !next_pts || !status)) || win < 3 || !(win & 1) || win > 21 ||
+        device < 0 || device >= 16 || max_level < 0)
+        return -1;
+    if (n == 0) return 0;
+    std::lock_guard<std::mutex> lock(g_mu);
+    GmcCtx* ctx = nullptr;
+    if (one_shot_ctx(device, &ctx)) return -2;
+    GmcCtx& c = *ctx;
+    const PyrGeom q = pyr_geometry(height, width, max_level, win);
+    const size_t frame = (size_t)height * width;
+    const size_t pin_need = 2 * frame + (size_t)n * 8 + (size_t)n * 8 + (size_t)n + 64;
+    if (buf_grow(c.planes, 2 * q.bytes) < 0 || grow_points(c.lk, n) < 0 || buf_grow(c.h_pin, pin_need) < 0) return -2;
+    uint8_t* h_prev = c.h_pin.p; uint8_t* h_cur = h_prev + frame;
+    float* h_pts = (float*)(c.h_pin.p + ((2 * frame + 15) & ~(size_t)15));             // 16-byte aligned behind the frames
+    float* h_next = h_pts + 2 * (size_t)n;
+    uint8_t* h_status = (uint8_t*)(h_next + 2 * (size_t)n);
+    std::memcpy(h_prev, prev, frame); std::memcpy(h_cur, cur, frame); std::memcpy(h_pts, pts, (size_t)n * 8);
+    uint8_t* dp = c.planes.p; uint8_t* dc = c.planes.p + q.bytes;
+    float* d_pts = (float*)c.lk.pts.p; float* d_next = (float*)c.lk.next.p;
+    GCHK(hipMemcpyAsync(dp, h_prev, frame, hipMemcpyHostToDevice, c.stream));
+    GCHK(hipMemcpyAsync(dc, h_cur, frame, hipMemcpyHostToDevice, c.stream));
+    GCHK(hipMemcpyAsync(d_pts, h_pts, (size_t)n * 8, hipMemcpyHostToDevice, c.stream));
+    for (int l = 1; l < q.levels; ++l) { enqueue_pyr_down(c.stream, 1, dp, 0, q, l); enqueue_pyr_down(c.stream, 1, dc, 0, q, l); }
+    enqueue_lk(c.stream, q, dp, dc, LkParams{win, max_iters, eps, min_eig}, d_pts, d_next, c.lk.status.p, n);
+    GCHK(hipGetLastError());
+    GCHK(hipMemcpyAsync(h_next, d_next, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
+    GCHK(hipMemcpyAsync(h_status, c.lk.status.p, (size_t)n, hipMemcpyDeviceToHost, c.stream));
+    GCHK(hipStreamSynchronize(c.stream));
+    std::memcpy(next_pts, h_next, (size_t)n * 8); std::memcpy(status, h_status, (size_t)n);
+    return 0;
+}
+
+// Frame preparation of GMC.apply on GPU `device`: BGR frame [height][width][3] -> gray plane of (height / downscale) x (width /
+// downscale) (cv2.cvtColor + cv2.resize INTER_LINEAR, bit for bit the fixed-point arithmetic gmc.py states), the float32
+// min-eigenvalue map of cornerMinEigenVal and the 0/1 mask of the corners goodFeaturesToTrack keeps before it orders them
+// (quality threshold, 3x3 non-maximum suppression, border excluded).  xtab / ytab: per output column / row (source index, tap 0,
+// tap 1) as gmc._linear_coeffs gives them; ignored when downscale == 1.  Outputs are host buffers of oh * ow elements.
+extern "C" int mi355_gmc_prepare_device(int device, const uint8_t* bgr, int height, int width, int oh, int ow, const int* xtab, const int* ytab,
+                                        double quality, uint8_t* gray_out, float* eig_out, uint8_t* ok_out) {
+    if (!bgr || height <= 0 || width <= 0 || oh <= 0 || ow <= 0 || !gray_out || !eig_out || !ok_out || device < 0 || device >= 16) return -1;
+    const int resize = !(oh == height && ow == width);
+    if (resize && (!xtab || !ytab)) return -1;
+    std::lock_guard<std::mutex> lock(g_mu);
+    GmcCtx* ctx = nullptr;
+    if (one_shot_ctx(device, &ctx)) return -2;
+    GmcCtx& c = *ctx;
+    const size_t nb = (size_t)height * width * 3, np = (size_t)oh * ow;
+    const size_t o_gray = al(nb), o_eig = o_gray + al(np), o_ok = o_eig + al(np * 4), o_xt = o_ok + al(np), o_yt = o_xt + al((size_t)ow * 12),
+                 o_max = o_yt + al((size_t)oh * 12), total = o_max + 256;
+    const size_t h_in = al(nb) + al((size_t)ow * 12) + al((size_t)oh * 12), h_total = h_in + al(np) + al(np * 4) + al(np);
+    if (buf_grow(c.front, total) < 0 || buf_grow(c.h_front, h_total) < 0) return -2;
+    uint8_t* D = c.front.p; uint8_t* hp = c.h_front.p;
+    uint8_t* h_bgr = hp; uint8_t* h_xt = hp + al(nb); uint8_t* h_yt = h_xt + al((size_t)ow * 12);
+    uint8_t* h_gray = hp + h_in; uint8_t* h_eig = h_gray + al(np); uint8_t* h_ok = h_eig + al(np * 4);
+    std::memcpy(h_bgr, bgr, nb);
+    GCHK(hipMemcpyAsync(D, h_bgr, nb, hipMemcpyHostToDevice, c.stream));
+    if (resize) {
+        std::memcpy(h_xt, xtab, (size_t)ow * 12); std::memcpy(h_yt, ytab, (size_t)oh * 12);
+        GCHK(hipMemcpyAsync(D + o_xt, h_xt, (size_t)ow * 12, hipMemcpyHostToDevice, c.stream));
+        GCHK(hipMemcpyAsync(D + o_yt, h_yt, (size_t)oh * 12, hipMemcpyHostToDevice, c.stream));
+    }
+    GCHK(hipMemsetAsync(D + o_max, 0, 4, c.stream));
+    // the plane alone: a pyramid of one level
+    enqueue_prepare(c.stream, 1, D, 0, height, width, (const int*)(D + o_xt), (const int*)(D + o_yt), resize, D + o_gray, 0, (float*)(D + o_eig), D + o_ok,
+                    (unsigned*)(D + o_max), quality, pyr_geometry(oh, ow, 0, 3));
+    GCHK(hipGetLastError());
+    GCHK(hipMemcpyAsync(h_gray, D + o_gray, np, hipMemcpyDeviceToHost, c.stream));
+    GCHK(hipMemcpyAsync(h_eig, D + o_eig, np * 4, hipMemcpyDeviceToHost, c.stream));
+    GCHK(hipMemcpyAsync(h_ok, D + o_ok, np, hipMemcpyDeviceToHost, c.stream));
+    GCHK(hipStreamSynchronize(c.stream));
+    std::memcpy(gray_out, h_gray, np); std::memcpy(eig_out, h_eig, np * 4); std::memcpy(ok_out, h_ok, np);
+    return 0;
+}
+
+// ---- one motion-compensation step as two calls: enqueue, then collect ------------------------------------------------------------
+// model.track() enqueues the step for a frame BEFORE the detector runs on it and collects it when the tracker asks for the warp: the
+// frame preparation and the optical flow (0.7 ms for a thousand corners) then run beside the detector pass on a stream of their own
+// instead of after it.  The object keeps the previous frame's pyramid on the device (two slots, swapped per step).
+struct mi355_gmc {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    Buf d_front;                                               // [bgr | eig | ok | x table | y table | max]
+    Buf d_pyr[2];                                              // both of one size; cam.slot holds the last prepared frame's pyramid
+    PtsBufs d_lk;
+    Buf h_pin{true};
+    hipEvent_t ev_up = nullptr; int up_h = 0, up_w = 0;        // recorded behind the pending step's frame upload (mi355_gmc_pending_frame)
+    // the pending step
+    bool pending = false; int oh = 0, ow = 0, n_lk = 0;
+    size_t o_hgray = 0, o_heig = 0, o_hok = 0, o_hnext = 0, o_hstatus = 0;
+    // ---- GMC.apply_sparseoptflow's state machine (mi355_gmc_track_*): the previous frame's plane and ordered corners live here, so a
+    // step is two calls from the tracker's language binding (enqueue, collect -> 2 x 3 matrix) and nothing per frame is done in it
+    bool host = false;                                         // mi355_gmc_create(-1): every stage in host C++ (csrc/gmc_host.cpp)
+    int downscale = 2;
+    CamState cam;
+    std::vector<uint8_t> cur_gray, ok, status; std::vector<float> eig, next_pts;
+    bool track_pending = false; int t_oh = 0, t_ow = 0, t_n = 0;
+    std::vector<uint8_t> host_frame; int hf_h = 0, hf_w = 0;   // host object: the frame of the pending step
+    // collect worker (device objects): the host half of a step -- wait for the stream, order the new corners, RANSAC -- runs on a thread of
+    // its own from the moment track_begin has enqueued the step, i.e. beside the detector pass the caller runs next; track_finish joins it
+    std::thread worker; std::mutex mu; std::condition_variable cv;
+    bool job_ready = false, job_done = false, worker_stop = false; int job_rc = 0; double job_H[6] = {1, 0, 0, 0, 1, 0};
+    // mi355_gmc_batch_frames: the frames of the batch a (concurrent) mi355_gmc_track_batch call has uploaded
+    hipEvent_t ev_batch_up = nullptr; unsigned long long batch_up_seq = 0; int batch_n = 0, batch_h = 0, batch_w = 0; size_t batch_fstride = 0;
+    bool job_active = false;                                   // written by the calling thread only: this step's collect belongs to the worker
+    // mi355_gmc_track_batch: device buffers of one batch (grow-only) and their pinned mirror
+    Buf d_batch, h_batch{true};
+};
+
+namespace {
+// Both pyramid slots hold `bytes`: 0 = they did, 1 = reallocated, -2 = HIP error; after the last two no frame on the device precedes the next.
+int grow_pyramids(mi355_gmc* g, size_t bytes) {
+    const int r0 = buf_grow(g->d_pyr[0], bytes), r1 = buf_grow(g->d_pyr[1], bytes);
+    if (r0 || r1) g->cam.have_prev = false;
+    return (r0 < 0 || r1 < 0) ? -2 : (r0 | r1);
 }
 }  // namespace
 
+extern "C" int mi355_gmc_create(int device, mi355_gmc** out) {
+    if (!out || device < -1) return -1;
+    *out = nullptr;
+    if (device >= 0) GCHK(hipSetDevice(device));
+    mi355_gmc* g = new mi355_gmc();
+    g->device = device; g->host = device == -1;
+    *out = g;
+    if (g->host) return 0;                                      // host object: no HIP call is ever made through it
+    // The step runs BESIDE the detector pass (model.track enqueues it first), on a stream of its own at the default priority.  Measured
+    // (tools/track_prio_ab.sh, round 4): giving this stream the LOWEST and the detector's the HIGHEST priority does not speed the detector
+    // up (637-644 us per frame either way) and delays the collect (119-139 -> 163-171 us): 805-838 -> 863-893 us per frame.
+    // MI355_GMC_PRIO=1 asks for the lowest priority (A/B only).
+    int least = 0, greatest = 0;
+    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+    static const bool low_prio = getenv("MI355_GMC_PRIO") && atoi(getenv("MI355_GMC_PRIO")) == 1;
+    if (hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, low_prio ? least : 0) != hipSuccess) { (void)hipGetLastError(); delete g; *out = nullptr; return -2; }
+    return 0;
+}
+
+extern "C" void mi355_gmc_destroy(mi355_gmc* g) {
+    if (g && g->worker.joinable()) {
+        { std::lock_guard<std::mutex> lk(g->mu); g->worker_stop = true; }
+        g->cv.notify_all();
+        g->worker.join();
+    }
+    if (!g) return;
+    if (g->host) { delete g; return; }
+    (void)hipSetDevice(g->device);
+    if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
+    if (g->ev_up) (void)hipEventDestroy(g->ev_up);
+    if (g->ev_batch_up) (void)hipEventDestroy(g->ev_batch_up);
+    for (Buf* b : {&g->d_front, &g->d_pyr[0], &g->d_pyr[1], &g->h_pin, &g->d_batch, &g->h_batch}) buf_free(*b);
+    free_points(g->d_lk);
+    delete g;
+}
+
+// Enqueue one step: frame preparation of `bgr` (as mi355_gmc_prepare_device) and, when n_prev > 0, Lucas-Kanade tracking of the
+// n_prev points `prev_pts` from the PREVIOUS step's plane into this one (as mi355_gmc_pyr_lk_device; the previous step must have
+// prepared a plane of the same oh x ow).  Returns at once; nothing of `bgr` / `prev_pts` is read after the call returns.
+extern "C" int mi355_gmc_step_begin(mi355_gmc* g, const uint8_t* bgr, int height, int width, int oh, int ow, const int* xtab, const int* ytab,
+                                    double quality, const float* prev_pts, int n_prev, int win, int max_level, int max_iters, double eps,
+                                    double min_eig) {
+    if (g && g->host) return -1;
+    if (!g || !bgr || height <= 0 || width <= 0 || oh <= 0 || ow <= 0 || n_prev < 0 || (n_prev > 0 && !prev_pts) || win < 3 || !(win & 1) || win > 21 ||
+        max_level < 0)
+        return -1;
+    const int resize = !(oh == height && ow == width);
+    if (resize && (!xtab || !ytab)) return -1;
+    if (g->pending) return -1;                                  // collect the previous step first
+    CamState& c = g->cam;
+    if (n_prev > 0 && !(c.have_prev && c.ph == oh && c.pw == ow)) return -1;
+    GCHK(hipSetDevice(g->device));
+    const size_t nb = (size_t)height * width * 3, np = (size_t)oh * ow;
+    const PyrGeom q = pyr_geometry(oh, ow, max_level, win);    // of the oh x ow plane
+    {
+        const int r = grow_pyramids(g, q.bytes);
+        if (r < 0) return -2;
+        if (r && n_prev > 0) return -1;                         // the plane the points were to be tracked from went with the old pyramids
+    }
+    const size_t o_eig = al(nb), o_ok = o_eig + al(np * 4), o_xt = o_ok + al(np), o_yt = o_xt + al((size_t)ow * 12), o_max = o_yt + al((size_t)oh * 12),
+                 total = o_max + 256;
+    {
+        const int r = buf_grow(g->d_front, total);
+        if (r) c.tab_key[0] = 0;                                // the tables went with the old buffer
+        if (r < 0) return -2;
+    }
+    if (grow_points(g->d_lk, n_prev) < 0) return -2;
+    // pinned staging: [bgr | x table | y table | prev points] in, [gray | eig | ok | next points | status] out
+    const size_t i_xt = al(nb), i_yt = i_xt + al((size_t)ow * 12), i_pts = i_yt + al((size_t)oh * 12), i_end = i_pts + al((size_t)n_prev * 8);
+    g->o_hgray = i_end; g->o_heig = g->o_hgray + al(np); g->o_hok = g->o_heig + al(np * 4); g->o_hnext = g->o_hok + al(np);
+    g->o_hstatus = g->o_hnext + al((size_t)n_prev * 8);
+    if (buf_grow(g->h_pin, g->o_hstatus + al((size_t)n_prev) + 256) < 0) return -2;
+    uint8_t* hp = g->h_pin.p; uint8_t* D = g->d_front.p;
+    std::memcpy(hp, bgr, nb);
+    GCHK(hipMemcpyAsync(D, hp, nb, hipMemcpyHostToDevice, g->stream));
+    if (!g->ev_up) GCHK(hipEventCreateWithFlags(&g->ev_up, hipEventDisableTiming));
+    GCHK(hipEventRecord(g->ev_up, g->stream)); g->up_h = height; g->up_w = width;
+    if (resize && !key_is(c.tab_key, height, width, oh, ow)) {
+        std::memcpy(hp + i_xt, xtab, (size_t)ow * 12); std::memcpy(hp + i_yt, ytab, (size_t)oh * 12);
+        GCHK(hipMemcpyAsync(D + o_xt, hp + i_xt, (size_t)ow * 12, hipMemcpyHostToDevice, g->stream));
+        GCHK(hipMemcpyAsync(D + o_yt, hp + i_yt, (size_t)oh * 12, hipMemcpyHostToDevice, g->stream));
+        key_set(c.tab_key, height, width, oh, ow);
+    }
+    GCHK(hipMemsetAsync(D + o_max, 0, 4, g->stream));
+    const int nslot = c.slot ^ 1;
+    uint8_t* dc = g->d_pyr[nslot].p;
+    uint8_t* dp = g->d_pyr[c.slot].p;
+    enqueue_prepare(g->stream, 1, D, 0, height, width, (const int*)(D + o_xt), (const int*)(D + o_yt), resize, dc, 0, (float*)(D + o_eig), D + o_ok,
+                    (unsigned*)(D + o_max), quality, q);
+    if (n_prev > 0) {
+        float* d_pts = (float*)g->d_lk.pts.p; float* d_next = (float*)g->d_lk.next.p;
+        std::memcpy(hp + i_pts, prev_pts, (size_t)n_prev * 8);
+        GCHK(hipMemcpyAsync(d_pts, hp + i_pts, (size_t)n_prev * 8, hipMemcpyHostToDevice, g->stream));
+        enqueue_lk(g->stream, q, dp, dc, LkParams{win, max_iters, eps, min_eig}, d_pts, d_next, g->d_lk.status.p, n_prev);
+        GCHK(hipMemcpyAsync(hp + g->o_hnext, d_next, (size_t)n_prev * 8, hipMemcpyDeviceToHost, g->stream));
+        GCHK(hipMemcpyAsync(hp + g->o_hstatus, g->d_lk.status.p, (size_t)n_prev, hipMemcpyDeviceToHost, g->stream));
+    }
+    GCHK(hipGetLastError());
+    GCHK(hipMemcpyAsync(hp + g->o_hgray, dc, np, hipMemcpyDeviceToHost, g->stream));
+    GCHK(hipMemcpyAsync(hp + g->o_heig, D + o_eig, np * 4, hipMemcpyDeviceToHost, g->stream));
+    GCHK(hipMemcpyAsync(hp + g->o_hok, D + o_ok, np, hipMemcpyDeviceToHost, g->stream));
+    c.slot = nslot; c.have_prev = true; c.ph = oh; c.pw = ow;
+    g->pending = true; g->oh = oh; g->ow = ow; g->n_lk = n_prev;
+    return 0;
+}
+
+// The frame of the pending step as it sits on the device (dense BGR [height][width][3], uploaded once by mi355_gmc_step_begin): waits -- on
+// the host, ~10 us -- until that upload has landed and hands out the pointer, so that the detector pass of the same frame
+// (mi355_yolo_infer_device) reads this copy instead of uploading its own.  Besides saving the second upload this is what lets the two
+// overlap at all: a second host -> device copy queues up behind the step's device -> host copies, which wait for its Lucas-Kanade launch
+// (measured: the detector's first kernel started when the whole step was over, tools/track_timeline.py).  Valid until the next step_begin.
+extern "C" int mi355_gmc_pending_frame(mi355_gmc* g, const uint8_t** dev_bgr, int* height, int* width) {
+    if (!g || g->host || !(g->pending || g->track_pending) || !g->ev_up || !dev_bgr || !height || !width) return -1;
+    GCHK(hipSetDevice(g->device));
+    GCHK(hipEventSynchronize(g->ev_up));
+    *dev_bgr = g->d_front.p; *height = g->up_h; *width = g->up_w;
+    return 0;
+}
+
+// Collect the enqueued step: gray / eig / ok of oh * ow elements, next_pts [n_prev][2] and status [n_prev] (untouched when the step
+// had n_prev == 0).
+extern "C" int mi355_gmc_step_finish(mi355_gmc* g, uint8_t* gray_out, float* eig_out, uint8_t* ok_out, float* next_pts, uint8_t* status) {
+    if (!g || g->host || !g->pending || !gray_out || !eig_out || !ok_out || (g->n_lk > 0 && (!next_pts || !status))) return -1;
+    GCHK(hipSetDevice(g->device));
+    g->pending = false;
+    if (hipStreamSynchronize(g->stream) != hipSuccess) { (void)hipGetLastError(); g->cam.have_prev = false; return -2; }
+    const size_t np = (size_t)g->oh * g->ow;
+    const uint8_t* hp = g->h_pin.p;
+    std::memcpy(gray_out, hp + g->o_hgray, np); std::memcpy(eig_out, hp + g->o_heig, np * 4); std::memcpy(ok_out, hp + g->o_hok, np);
+    if (g->n_lk > 0) { std::memcpy(next_pts, hp + g->o_hnext, (size_t)g->n_lk * 8); std::memcpy(status, hp + g->o_hstatus, (size_t)g->n_lk); }
+    return 0;
+}
+
+// ---- the whole step of GMC.apply_sparseoptflow on the object (ultralytics/trackers/utils/gmc.py, reached from /root/reference/model.py:38) ----
+// track_begin = enqueue: frame preparation of `bgr` and Lucas-Kanade tracking of the previous frame's corners into it (GPU object: on the
+// object's stream, returns at once; host object: the frame is copied and the work happens in track_finish).  track_finish = collect:
+// orders the new frame's corners (kept for the next step), estimates the partial affine transform prev -> cur from the tracked pairs
+// (RANSAC, seed 0) when more than 4 survive, scales its translation back to frame pixels.  H_out: 6 doubles, row-major 2 x 3; the
+// identity on the first frame of a plane size, when the previous frame had no corners, or when too few points were tracked.
 static void collect_worker(mi355_gmc* g);
 extern "C" int mi355_gmc_track_begin(mi355_gmc* g, const uint8_t* bgr, int height, int width, int downscale) {
     if (!g || !bgr || height <= 0 || width <= 0 || downscale < 1 || g->track_pending) return -1;
     const int oh = downscale > 1 ? height / downscale : height, ow = downscale > 1 ? width / downscale : width;
     if (oh <= 0 || ow <= 0) return -1;
     g->downscale = downscale;
-    if (downscale > 1 && !(g->tkey[0] == height && g->tkey[1] == width && g->tkey[2] == oh && g->tkey[3] == ow)) {
-        linear_table(ow, width, g->xt); linear_table(oh, height, g->yt);
-        g->tkey[0] = height; g->tkey[1] = width; g->tkey[2] = oh; g->tkey[3] = ow;
-    }
-    // the previous frame's corners are tracked only into a plane of the same size (GMC.apply resets otherwise)
-    const bool lk = g->have_prev_pts && g->prev_h == oh && g->prev_w == ow && !g->prev_pts.empty();
-    g->lk_pts.clear();
-    if (lk) g->lk_pts = g->prev_pts;
-    const int n = (int)(g->lk_pts.size() / 2);
+    CamState& c = g->cam;
+    if (downscale > 1) cam_tables(c, height, width, oh, ow);
+    const int n = cam_decide(c, oh, ow, false);                 // whether the device pyramid fits is step_begin's check
     if (g->host) {
         g->host_frame.assign(bgr, bgr + (size_t)height * width * 3); g->hf_h = height; g->hf_w = width;
     } else {
-        if (!lk) g->have_prev = false;                          // the device pyramid of another plane size is not a predecessor
-        const int rc = mi355_gmc_step_begin(g, bgr, height, width, oh, ow, downscale > 1 ? g->xt.data() : nullptr, downscale > 1 ? g->yt.data() : nullptr,
-                                            kQuality, n ? g->lk_pts.data() : nullptr, n, kLkWin, kLkLevels, kLkIters, kLkEps, kLkMinEig);
+        const int rc = mi355_gmc_step_begin(g, bgr, height, width, oh, ow, downscale > 1 ? c.xt.data() : nullptr, downscale > 1 ? c.yt.data() : nullptr,
+                                            kQuality, n ? c.lk_pts.data() : nullptr, n, kLk.win, kLkLevels, kLk.max_iters, kLk.eps, kLk.min_eig);
         if (rc) return rc;
     }
     g->track_pending = true; g->t_oh = oh; g->t_ow = ow; g->t_n = n;
@@ -913,28 +970,28 @@ extern "C" int mi355_gmc_track_finish(mi355_gmc* g, double* H_out) {
 }
 
 static int track_collect(mi355_gmc* g, double* H_out) {
+    CamState& c = g->cam;
     const int oh = g->t_oh, ow = g->t_ow, n = g->t_n;
     const size_t np = (size_t)oh * ow;
     g->cur_gray.resize(np); g->eig.resize(np); g->ok.resize(np);
     g->next_pts.assign((size_t)n * 2, 0.f); g->status.assign((size_t)n, 0);
     if (g->host) {
-        int rc = mi355_gmc_prepare_host(g->host_frame.data(), g->hf_h, g->hf_w, oh, ow, g->downscale > 1 ? g->xt.data() : nullptr,
-                                        g->downscale > 1 ? g->yt.data() : nullptr, kQuality, g->cur_gray.data(), g->eig.data(), g->ok.data());
+        int rc = mi355_gmc_prepare_host(g->host_frame.data(), g->hf_h, g->hf_w, oh, ow, g->downscale > 1 ? c.xt.data() : nullptr,
+                                        g->downscale > 1 ? c.yt.data() : nullptr, kQuality, g->cur_gray.data(), g->eig.data(), g->ok.data());
         if (rc) return rc;
         if (n > 0) {
-            rc = mi355_gmc_pyr_lk(g->prev_gray.data(), g->cur_gray.data(), oh, ow, g->lk_pts.data(), n, kLkWin, kLkLevels, kLkIters, kLkEps, kLkMinEig,
+            rc = mi355_gmc_pyr_lk(c.prev_gray.data(), g->cur_gray.data(), oh, ow, c.lk_pts.data(), n, kLk.win, kLkLevels, kLk.max_iters, kLk.eps, kLk.min_eig,
                                   g->next_pts.data(), g->status.data());
             if (rc) return rc;
         }
     } else {
         const int rc = mi355_gmc_step_finish(g, g->cur_gray.data(), g->eig.data(), g->ok.data(), n ? g->next_pts.data() : nullptr, n ? g->status.data() : nullptr);
-        if (rc) { g->have_prev_pts = false; return rc; }
+        if (rc) { c.have_prev_pts = false; return rc; }
     }
-    double H[6];
-    step_tail(g->lk_pts.data(), g->next_pts.data(), g->status.data(), n, g->downscale, g->eig.data(), g->ok.data(), oh, ow, g->prev_pts, H);
-    g->prev_gray.swap(g->cur_gray);
-    g->prev_h = oh; g->prev_w = ow; g->have_prev_pts = true;
-    std::memcpy(H_out, H, sizeof(H));
+    tail_warp(c.lk_pts.data(), g->next_pts.data(), g->status.data(), n, g->downscale, H_out);
+    tail_corners(g->eig.data(), g->ok.data(), oh, ow, c.prev_pts);
+    c.prev_gray.swap(g->cur_gray);
+    cam_advance(c, oh, ow);
     return 0;
 }
 
@@ -959,98 +1016,57 @@ extern "C" int mi355_gmc_track_batch(mi355_gmc* g, const uint8_t* const* frames,
     if (oh <= 0 || ow <= 0) return -1;
     GCHK(hipSetDevice(g->device));
     g->downscale = downscale;
+    CamState& c = g->cam;
     const int resize = downscale > 1;
-    if (resize && !(g->tkey[0] == height && g->tkey[1] == width && g->tkey[2] == oh && g->tkey[3] == ow)) {
-        linear_table(ow, width, g->xt); linear_table(oh, height, g->yt);
-        g->tkey[0] = height; g->tkey[1] = width; g->tkey[2] = oh; g->tkey[3] = ow;
-    }
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    if (resize) cam_tables(c, height, width, oh, ow);
     const size_t nb = (size_t)height * width * 3, np = (size_t)oh * ow;
-    int hs[kMaxLevels], ws[kMaxLevels];
-    size_t off[kMaxLevels], pyr_bytes = 0;
-    const int levels = pyr_geometry(oh, ow, kLkLevels, kLkWin, hs, ws, off, &pyr_bytes);
+    const PyrGeom q = pyr_geometry(oh, ow, kLkLevels, kLk.win);
     // does the object's previous frame precede frames[0]?  (same plane size, corners known, its pyramid on the device)
-    const bool cont = g->have_prev_pts && g->prev_h == oh && g->prev_w == ow && g->have_prev && g->ph == oh && g->pw == ow && g->pyr_cap >= pyr_bytes;
-    // device: [frames n x nb | pyramids (n + 1) x pyr_bytes | eig n x np x 4 | ok n x np | x table | y table | max n x 4 | pts n x kMaxCorners x 8 |
+    const bool cont = cam_follows(c, oh, ow, true) && g->d_pyr[1].cap >= q.bytes;
+    // device: [frames n x nb | pyramids (n + 1) x q.bytes | eig n x np x 4 | ok n x np | x table | y table | max n x 4 | pts n x kMaxCorners x 8 |
     //          next (same) | status n x kMaxCorners | counts n x 4]
     const size_t fstride = (nb % 16 == 0) ? nb : al(nb);       // dense frames when 16-byte aligned: the detector may read them in place (mi355_gmc_batch_frames)
-    const size_t o_pyr = al((size_t)n * fstride), o_eig = o_pyr + (size_t)(n + 1) * pyr_bytes, o_ok = o_eig + al((size_t)n * np * 4), o_xt = o_ok + al((size_t)n * np),
+    const size_t o_pyr = al((size_t)n * fstride), o_eig = o_pyr + (size_t)(n + 1) * q.bytes, o_ok = o_eig + al((size_t)n * np * 4), o_xt = o_ok + al((size_t)n * np),
                  o_yt = o_xt + al((size_t)ow * 12), o_max = o_yt + al((size_t)oh * 12), o_pts = o_max + al((size_t)n * 4),
                  o_next = o_pts + al((size_t)n * kMaxCorners * 8), o_st = o_next + al((size_t)n * kMaxCorners * 8), o_cnt = o_st + al((size_t)n * kMaxCorners),
                  d_total = o_cnt + al((size_t)n * 4);
-    if (g->batch_cap < d_total) {
-        if (g->d_batch) (void)hipFree(g->d_batch);
-        g->d_batch = nullptr; g->batch_cap = 0;
-        GCHK(hipMalloc(&g->d_batch, d_total)); g->batch_cap = d_total;
-    }
     // pinned: [frames | tables | eig | ok | pts | next | status | counts | last gray]
     const size_t p_xt = al((size_t)n * fstride), p_yt = p_xt + al((size_t)ow * 12), p_eig = p_yt + al((size_t)oh * 12), p_ok = p_eig + al((size_t)n * np * 4),
                  p_pts = p_ok + al((size_t)n * np), p_next = p_pts + al((size_t)n * kMaxCorners * 8), p_st = p_next + al((size_t)n * kMaxCorners * 8),
                  p_cnt = p_st + al((size_t)n * kMaxCorners), p_gray = p_cnt + al((size_t)n * 4), h_total = p_gray + al(np);
-    if (g->hbatch_cap < h_total) {
-        if (g->h_batch) (void)hipHostFree(g->h_batch);
-        g->h_batch = nullptr; g->hbatch_cap = 0;
-        GCHK(hipHostMalloc(&g->h_batch, h_total)); g->hbatch_cap = h_total;
-    }
-    uint8_t* D = g->d_batch; uint8_t* P = g->h_batch;
-    {   // frames -> pinned staging on a few threads (64 frames of 320 x 240 are 14.7 MB: 2.5 ms on one core, a third of this call)
-        const int nt = std::max(1, std::min(std::min(8, n), (int)std::thread::hardware_concurrency()));
-        if (nt <= 1 || (size_t)n * nb < (1u << 20)) { for (int f = 0; f < n; ++f) std::memcpy(P + (size_t)f * fstride, frames[f], nb); }
-        else {
-            std::vector<std::thread> th;
-            for (int t = 0; t < nt; ++t) th.emplace_back([&, t] { for (int f = t; f < n; f += nt) std::memcpy(P + (size_t)f * fstride, frames[f], nb); });
-            for (auto& t : th) t.join();
-        }
-    }
+    if (buf_grow(g->d_batch, d_total) < 0 || buf_grow(g->h_batch, h_total) < 0) return -2;
+    uint8_t* D = g->d_batch.p; uint8_t* P = g->h_batch.p;
+    const int nthreads = host_threads(n);
+    // frames -> pinned staging on a few threads (64 frames of 320 x 240 are 14.7 MB: 2.5 ms on one core, a third of this call)
+    parallel_for(n, (size_t)n * nb < (1u << 20) ? 1 : nthreads, [&](int f) { std::memcpy(P + (size_t)f * fstride, frames[f], nb); });
     GCHK(hipMemcpyAsync(D, P, (size_t)n * fstride, hipMemcpyHostToDevice, g->stream));
     if (!g->ev_batch_up) GCHK(hipEventCreateWithFlags(&g->ev_batch_up, hipEventDisableTiming));
     GCHK(hipEventRecord(g->ev_batch_up, g->stream));
     { std::lock_guard<std::mutex> lk(g->mu); g->batch_n = n; g->batch_h = height; g->batch_w = width; g->batch_fstride = fstride; ++g->batch_up_seq; }
     g->cv.notify_all();
     if (resize) {
-        std::memcpy(P + p_xt, g->xt.data(), (size_t)ow * 12); std::memcpy(P + p_yt, g->yt.data(), (size_t)oh * 12);
+        std::memcpy(P + p_xt, c.xt.data(), (size_t)ow * 12); std::memcpy(P + p_yt, c.yt.data(), (size_t)oh * 12);
         GCHK(hipMemcpyAsync(D + o_xt, P + p_xt, (size_t)ow * 12, hipMemcpyHostToDevice, g->stream));
         GCHK(hipMemcpyAsync(D + o_yt, P + p_yt, (size_t)oh * 12, hipMemcpyHostToDevice, g->stream));
     }
     GCHK(hipMemsetAsync(D + o_max, 0, (size_t)n * 4, g->stream));
-    if (cont) GCHK(hipMemcpyAsync(D + o_pyr, g->d_pyr[g->slot], pyr_bytes, hipMemcpyDeviceToDevice, g->stream));   // slot 0 = the previous frame's pyramid
-    uint8_t* pyr1 = D + o_pyr + pyr_bytes;                     // frame f's pyramid at pyr1 + f * pyr_bytes
-    const unsigned blocks = (unsigned)((np + 255) / 256);
-    hipLaunchKernelGGL(gray_resize_kernel, dim3(blocks, n), dim3(256), 0, g->stream, D, height, width, (const int*)(D + o_xt), (const int*)(D + o_yt),
-                       pyr1 + off[0], oh, ow, resize, fstride, pyr_bytes);
-    hipLaunchKernelGGL(min_eig_kernel, dim3(blocks, n), dim3(256), 0, g->stream, pyr1 + off[0], oh, ow, (float*)(D + o_eig), (unsigned*)(D + o_max), pyr_bytes);
-    hipLaunchKernelGGL(corner_mask_kernel, dim3(blocks, n), dim3(256), 0, g->stream, (const float*)(D + o_eig), oh, ow, (const unsigned*)(D + o_max), kQuality,
-                       D + o_ok);
-    for (int l = 1; l < levels; ++l) {
-        const int npx = hs[l] * ws[l];
-        hipLaunchKernelGGL(pyr_down_kernel, dim3((npx + 255) / 256, n), dim3(256), 0, g->stream, pyr1 + off[l - 1], hs[l - 1], ws[l - 1], pyr1 + off[l], hs[l],
-                           ws[l], pyr_bytes);
-    }
+    if (cont) GCHK(hipMemcpyAsync(D + o_pyr, g->d_pyr[c.slot].p, q.bytes, hipMemcpyDeviceToDevice, g->stream));   // slot 0 = the previous frame's pyramid
+    uint8_t* pyr1 = D + o_pyr + q.bytes;                       // frame f's pyramid at pyr1 + f * q.bytes
+    enqueue_prepare(g->stream, n, D, fstride, height, width, (const int*)(D + o_xt), (const int*)(D + o_yt), resize, pyr1, q.bytes, (float*)(D + o_eig), D + o_ok,
+                    (unsigned*)(D + o_max), kQuality, q);
     GCHK(hipGetLastError());
     GCHK(hipMemcpyAsync(P + p_eig, D + o_eig, (size_t)n * np * 4, hipMemcpyDeviceToHost, g->stream));
     GCHK(hipMemcpyAsync(P + p_ok, D + o_ok, (size_t)n * np, hipMemcpyDeviceToHost, g->stream));
-    GCHK(hipMemcpyAsync(P + p_gray, pyr1 + (size_t)(n - 1) * pyr_bytes + off[0], np, hipMemcpyDeviceToHost, g->stream));
-    if (hipStreamSynchronize(g->stream) != hipSuccess) { (void)hipGetLastError(); g->have_prev = false; g->have_prev_pts = false; return -2; }
+    GCHK(hipMemcpyAsync(P + p_gray, pyr1 + (size_t)(n - 1) * q.bytes, np, hipMemcpyDeviceToHost, g->stream));
+    if (hipStreamSynchronize(g->stream) != hipSuccess) { (void)hipGetLastError(); cam_lost(c); return -2; }
     // corners of every frame, strongest first (host threads); pair f tracks the corners of frame f - 1 (f = 0: the object's previous frame)
     std::vector<std::vector<float>> corners(n);
-    std::vector<int> ncorn(n, 0);
-    const int nthreads = std::max(1, std::min(std::min(8, n), (int)std::thread::hardware_concurrency()));
-    auto parallel = [&](auto&& body) {
-        if (nthreads <= 1) { for (int f = 0; f < n; ++f) body(f); return; }
-        std::vector<std::thread> th;
-        for (int t = 0; t < nthreads; ++t) th.emplace_back([&, t] { for (int f = t; f < n; f += nthreads) body(f); });
-        for (auto& t : th) t.join();
-    };
-    parallel([&](int f) {
-        corners[f].resize((size_t)kMaxCorners * 2);
-        ncorn[f] = std::max(0, mi355_gmc_order_corners((const float*)(P + p_eig) + (size_t)f * np, P + p_ok + (size_t)f * np, oh, ow, kMaxCorners, corners[f].data()));
-        corners[f].resize((size_t)ncorn[f] * 2);
-    });
+    parallel_for(n, nthreads, [&](int f) { tail_corners((const float*)(P + p_eig) + (size_t)f * np, P + p_ok + (size_t)f * np, oh, ow, corners[f]); });
     int* cnt = (int*)(P + p_cnt);
     float* hp = (float*)(P + p_pts);
     int any = 0;
     for (int f = 0; f < n; ++f) {
-        const std::vector<float>* src = f == 0 ? (cont && !g->prev_pts.empty() ? &g->prev_pts : nullptr) : &corners[f - 1];
+        const std::vector<float>* src = f == 0 ? (cont && !c.prev_pts.empty() ? &c.prev_pts : nullptr) : &corners[f - 1];
         cnt[f] = src ? (int)(src->size() / 2) : 0;
         if (cnt[f]) std::memcpy(hp + (size_t)f * kMaxCorners * 2, src->data(), src->size() * sizeof(float));
         any |= cnt[f];
@@ -1058,49 +1074,24 @@ extern "C" int mi355_gmc_track_batch(mi355_gmc* g, const uint8_t* const* frames,
     if (any) {
         GCHK(hipMemcpyAsync(D + o_pts, P + p_pts, (size_t)n * kMaxCorners * 8, hipMemcpyHostToDevice, g->stream));
         GCHK(hipMemcpyAsync(D + o_cnt, P + p_cnt, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-        LkArgs a{};
-        for (int l = 0; l < levels; ++l) { a.prev[l] = D + o_pyr + off[l]; a.cur[l] = pyr1 + off[l]; a.h[l] = hs[l]; a.w[l] = ws[l]; }
-        a.top = levels - 1; a.n = 0; a.win = kLkWin; a.max_iters = kLkIters; a.width = ow; a.height = oh;
-        a.eps2 = kLkEps * kLkEps; a.min_eig = kLkMinEig;
-        a.pts = (const float*)(D + o_pts); a.next = (float*)(D + o_next); a.status = D + o_st;
-        a.pair_stride = pyr_bytes; a.max_pts = kMaxCorners; a.n_arr = (const int*)(D + o_cnt);
-        hipLaunchKernelGGL(lk_kernel, dim3((kMaxCorners + kLkWaves - 1) / kLkWaves, n), dim3(64 * kLkWaves), 0, g->stream, a);
+        enqueue_lk(g->stream, q, D + o_pyr, pyr1, kLk, (const float*)(D + o_pts), (float*)(D + o_next), D + o_st, kMaxCorners, n, q.bytes, (const int*)(D + o_cnt));
         GCHK(hipGetLastError());
         GCHK(hipMemcpyAsync(P + p_next, D + o_next, (size_t)n * kMaxCorners * 8, hipMemcpyDeviceToHost, g->stream));
         GCHK(hipMemcpyAsync(P + p_st, D + o_st, (size_t)n * kMaxCorners, hipMemcpyDeviceToHost, g->stream));
     }
     // the last frame's pyramid becomes the object's previous one (the per-frame entry points continue from it)
-    if (g->pyr_cap < pyr_bytes) {
-        for (int i = 0; i < 2; ++i) { if (g->d_pyr[i]) (void)hipFree(g->d_pyr[i]); g->d_pyr[i] = nullptr; }
-        g->pyr_cap = 0;
-        GCHK(hipMalloc(&g->d_pyr[0], pyr_bytes)); GCHK(hipMalloc(&g->d_pyr[1], pyr_bytes)); g->pyr_cap = pyr_bytes;
-    }
-    GCHK(hipMemcpyAsync(g->d_pyr[g->slot], pyr1 + (size_t)(n - 1) * pyr_bytes, pyr_bytes, hipMemcpyDeviceToDevice, g->stream));
-    if (hipStreamSynchronize(g->stream) != hipSuccess) { (void)hipGetLastError(); g->have_prev = false; g->have_prev_pts = false; return -2; }
-    g->have_prev = true; g->ph = oh; g->pw = ow;
+    if (grow_pyramids(g, q.bytes) < 0) return -2;
+    GCHK(hipMemcpyAsync(g->d_pyr[c.slot].p, pyr1 + (size_t)(n - 1) * q.bytes, q.bytes, hipMemcpyDeviceToDevice, g->stream));
+    if (hipStreamSynchronize(g->stream) != hipSuccess) { (void)hipGetLastError(); cam_lost(c); return -2; }
+    c.have_prev = true; c.ph = oh; c.pw = ow;
     const float* hn = (const float*)(P + p_next);
     const uint8_t* hst = P + p_st;
-    parallel([&](int f) {
-        double* H = H_out + 6 * f;
-        H[0] = 1; H[1] = 0; H[2] = 0; H[3] = 0; H[4] = 1; H[5] = 0;
-        const int m0 = cnt[f];
-        if (!m0) return;
-        std::vector<double> src, dst;
-        const float* p0 = hp + (size_t)f * kMaxCorners * 2; const float* p1 = hn + (size_t)f * kMaxCorners * 2; const uint8_t* st = hst + (size_t)f * kMaxCorners;
-        for (int i = 0; i < m0; ++i)
-            if (st[i]) { src.push_back(p0[2 * i]); src.push_back(p0[2 * i + 1]); dst.push_back(p1[2 * i]); dst.push_back(p1[2 * i + 1]); }
-        const int m = (int)(src.size() / 2);
-        if (m > 4) {
-            double E[6];
-            if (mi355_gmc_affine_partial(src.data(), dst.data(), m, kRansacThr, kRansacConf, kRansacIters, 0ull, E, nullptr) == 1) {
-                std::memcpy(H, E, sizeof(E));
-                H[2] *= downscale; H[5] *= downscale;
-            }
-        }
+    parallel_for(n, nthreads, [&](int f) {
+        tail_warp(hp + (size_t)f * kMaxCorners * 2, hn + (size_t)f * kMaxCorners * 2, hst + (size_t)f * kMaxCorners, cnt[f], downscale, H_out + 6 * f);
     });
-    g->prev_pts = corners[n - 1];
-    g->prev_gray.assign(P + p_gray, P + p_gray + np);
-    g->prev_h = oh; g->prev_w = ow; g->have_prev_pts = true;
+    c.prev_pts = corners[n - 1];
+    c.prev_gray.assign(P + p_gray, P + p_gray + np);
+    cam_advance(c, oh, ow);
     return 0;
 }
 
@@ -1120,7 +1111,7 @@ extern "C" int mi355_gmc_batch_frames(mi355_gmc* g, unsigned long long after_seq
     }
     GCHK(hipSetDevice(g->device));
     GCHK(hipEventSynchronize(g->ev_batch_up));
-    *dev = g->d_batch;
+    *dev = g->d_batch.p;
     return 0;
 }
 
@@ -1134,20 +1125,14 @@ extern "C" unsigned long long mi355_gmc_batch_seq(mi355_gmc* g) {
 extern "C" int mi355_gmc_track_reset(mi355_gmc* g) {
     if (!g) return -1;
     if (g->track_pending) { double H[6]; (void)mi355_gmc_track_finish(g, H); }
-    g->have_prev_pts = false; g->prev_pts.clear(); g->prev_gray.clear(); g->prev_h = g->prev_w = 0;
-    if (!g->host) g->have_prev = false;
+    cam_forget(g->cam);
     return 0;
 }
 
 // The previous frame as the object holds it (tests): plane size, number of corners; gray_out [oh * ow] and pts_out [pts_cap][2] when given.
 extern "C" int mi355_gmc_track_state(const mi355_gmc* g, int* oh, int* ow, int* n_pts, uint8_t* gray_out, float* pts_out, int pts_cap) {
     if (!g) return -1;
-    const int n = g->have_prev_pts ? (int)(g->prev_pts.size() / 2) : 0;
-    if (oh) *oh = g->have_prev_pts ? g->prev_h : 0;
-    if (ow) *ow = g->have_prev_pts ? g->prev_w : 0;
-    if (n_pts) *n_pts = n;
-    if (gray_out && g->have_prev_pts) std::memcpy(gray_out, g->prev_gray.data(), g->prev_gray.size());
-    if (pts_out && pts_cap > 0 && n > 0) std::memcpy(pts_out, g->prev_pts.data(), (size_t)std::min(n, pts_cap) * 8);
+    cam_report(g->cam, oh, ow, n_pts, gray_out, pts_out, pts_cap);
     return 0;
 }
 
@@ -1263,13 +1248,9 @@ __global__ __launch_bounds__(64 * kLkWaves) void lk_multi_kernel(MultiArgs m, in
 }
 
 struct MultiCam {
-    // GMC.apply_sparseoptflow's state of this camera (as mi355_gmc holds it for one)
-    std::vector<int> xt, yt; int tkey[4] = {0, 0, 0, 0};
-    std::vector<float> prev_pts, lk_pts; std::vector<uint8_t> prev_gray;
-    int prev_h = 0, prev_w = 0; bool have_prev_pts = false;
+    CamState s;                                              // GMC.apply_sparseoptflow's state of this camera (as mi355_gmc holds it for one)
     // its region of the arena: [pyramid slot 0 | pyramid slot 1 | x table | y table]
     size_t region = 0, region_cap = 0, pyr_bytes = 0;
-    int slot = 0; bool have_prev = false; int ph = 0, pw = 0; int tab_key[4] = {0, 0, 0, 0};
     // the pending tick
     bool active = false; int H = 0, W = 0, oh = 0, ow = 0, n = 0;
     size_t t_frame = 0, t_pts = 0, o_gray = 0, o_eig = 0, o_ok = 0, o_next = 0, o_status = 0;
@@ -1283,10 +1264,10 @@ struct mi355_gmc_multi {
     std::vector<mi355_gmc*> single;                           // host object: one host mi355_gmc per camera
     std::vector<MultiCam> cams;
     hipStream_t stream = nullptr; hipEvent_t ev_up = nullptr, ev_done = nullptr;
-    uint8_t* arena = nullptr; size_t arena_cap = 0, arena_used = 0;
-    uint8_t* d_tin = nullptr; uint8_t* h_tin = nullptr; size_t tin_cap = 0;       // the tick's frames + points (pinned mirror): ONE upload
-    uint8_t* d_tout = nullptr; uint8_t* h_tout = nullptr; size_t tout_cap = 0;    // maxima + per camera gray / eig / ok / next / status: ONE download
-    uint8_t* d_desc = nullptr; uint8_t* h_desc = nullptr; size_t desc_cap = 0, desc_bytes = 0;
+    Buf arena; size_t arena_used = 0;
+    Buf d_tin, h_tin{true};                                   // the tick's frames + points (pinned mirror): ONE upload
+    Buf d_tout, h_tout{true};                                 // maxima + per camera gray / eig / ok / next / status: ONE download
+    Buf d_desc, h_desc{true}; size_t desc_bytes = 0;
     std::vector<int> active;                                  // cameras of the pending tick, in camera order
     std::vector<std::thread> workers;
     bool job_active = false;                                  // written by the calling thread only: a tick has been begun and not collected
@@ -1322,42 +1303,28 @@ extern "C" void mi355_gmc_multi_destroy(mi355_gmc_multi* g) {
         if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
         if (g->ev_up) (void)hipEventDestroy(g->ev_up);
         if (g->ev_done) (void)hipEventDestroy(g->ev_done);
-        if (g->arena) (void)hipFree(g->arena);
-        if (g->d_tin) (void)hipFree(g->d_tin); if (g->h_tin) (void)hipHostFree(g->h_tin);
-        if (g->d_tout) (void)hipFree(g->d_tout); if (g->h_tout) (void)hipHostFree(g->h_tout);
-        if (g->d_desc) (void)hipFree(g->d_desc); if (g->h_desc) (void)hipHostFree(g->h_desc);
+        for (Buf* b : {&g->arena, &g->d_tin, &g->h_tin, &g->d_tout, &g->h_tout, &g->d_desc, &g->h_desc}) buf_free(*b);
     }
     delete g;
 }
 
 namespace {
-int multi_threads(int active) { return std::max(1, std::min(std::min(8, active), (int)std::thread::hardware_concurrency())); }
-
-// grow-only pair of a device buffer and its pinned mirror
-int grow_pair(uint8_t*& d, uint8_t*& h, size_t& cap, size_t need) {
-    if (cap >= need) return 0;
-    if (d) (void)hipFree(d); if (h) (void)hipHostFree(h);
-    d = h = nullptr; cap = 0;
-    need += need / 4;
-    GCHK(hipMalloc(&d, need)); GCHK(hipHostMalloc(&h, need)); cap = need;
-    return 0;
-}
-
-// the host half of camera ci's step, on a worker: wait for the tick's results, then step_tail
+// the host half of camera ci's step, on a worker: wait for the tick's results, then the warp and the corners
 void multi_collect(mi355_gmc_multi* g, int ci) {
     MultiCam& c = g->cams[ci];
     if (g->host) { c.rc = mi355_gmc_track_finish(g->single[ci], c.Hm); return; }
-    if (hipEventSynchronize(g->ev_done) != hipSuccess) { (void)hipGetLastError(); c.rc = -2; c.have_prev = false; c.have_prev_pts = false; return; }
-    const uint8_t* P = g->h_tout;
-    const size_t np = (size_t)c.oh * c.ow;
-    step_tail(c.lk_pts.data(), (const float*)(P + c.o_next), P + c.o_status, c.n, g->downscale, (const float*)(P + c.o_eig), P + c.o_ok, c.oh, c.ow, c.prev_pts, c.Hm);
-    c.prev_gray.assign(P + c.o_gray, P + c.o_gray + np);
-    c.prev_h = c.oh; c.prev_w = c.ow; c.have_prev_pts = true;
+    if (hipEventSynchronize(g->ev_done) != hipSuccess) { (void)hipGetLastError(); c.rc = -2; cam_lost(c.s); return; }
+    const uint8_t* P = g->h_tout.p;
+    tail_warp(c.s.lk_pts.data(), (const float*)(P + c.o_next), P + c.o_status, c.n, g->downscale, c.Hm);
+    tail_corners((const float*)(P + c.o_eig), P + c.o_ok, c.oh, c.ow, c.s.prev_pts);
+    c.s.prev_gray.assign(P + c.o_gray, P + c.o_gray + (size_t)c.oh * c.ow);
+    cam_advance(c.s, c.oh, c.ow);
     c.rc = 0;
 }
 
+// the workers outlive the call that starts them: mi355_gmc_multi_finish joins them
 void multi_start_workers(mi355_gmc_multi* g) {
-    const int na = (int)g->active.size(), nt = multi_threads(na);
+    const int na = (int)g->active.size(), nt = host_threads(na);
     g->workers.clear();
     for (int t = 0; t < nt; ++t)
         g->workers.emplace_back([g, t, nt, na] {
@@ -1369,7 +1336,6 @@ void multi_start_workers(mi355_gmc_multi* g) {
 
 int multi_begin_device(mi355_gmc_multi* g, const uint8_t* const* frames, const int* heights, const int* widths, int downscale) {
     GCHK(hipSetDevice(g->device));
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const int na = (int)g->active.size();
     const int resize = downscale > 1;
     // per camera: plane and pyramid geometry, its region of the arena, what it tracks
@@ -1384,31 +1350,24 @@ int multi_begin_device(mi355_gmc_multi* g, const uint8_t* const* frames, const i
         MultiCam& c = g->cams[ci];
         c.H = heights[ci]; c.W = widths[ci];
         c.oh = resize ? c.H / downscale : c.H; c.ow = resize ? c.W / downscale : c.W;
-        if (resize && !(c.tkey[0] == c.H && c.tkey[1] == c.W && c.tkey[2] == c.oh && c.tkey[3] == c.ow)) {
-            linear_table(c.ow, c.W, c.xt); linear_table(c.oh, c.H, c.yt);
-            c.tkey[0] = c.H; c.tkey[1] = c.W; c.tkey[2] = c.oh; c.tkey[3] = c.ow;
-        }
-        // the previous frame's corners are tracked only into a plane of the same size (as mi355_gmc_track_begin)
-        const bool lk = c.have_prev_pts && c.prev_h == c.oh && c.prev_w == c.ow && !c.prev_pts.empty() && c.have_prev && c.ph == c.oh && c.pw == c.ow;
-        c.lk_pts.clear();
-        if (lk) c.lk_pts = c.prev_pts;
-        c.n = (int)(c.lk_pts.size() / 2);
+        if (resize) cam_tables(c.s, c.H, c.W, c.oh, c.ow);
+        c.n = cam_decide(c.s, c.oh, c.ow, true);
         GmcCam& d = desc[k];
         std::memset(&d, 0, sizeof(d));
-        size_t off[kMaxLevels], pyr_bytes = 0;
-        const int levels = pyr_geometry(c.oh, c.ow, kLkLevels, kLkWin, d.h, d.w, off, &pyr_bytes);
-        for (int l = 0; l < levels; ++l) d.lvl[l] = (unsigned)off[l];
-        d.top = levels - 1; max_top = std::max(max_top, d.top);
-        const size_t need = 2 * pyr_bytes + al((size_t)c.ow * 12) + al((size_t)c.oh * 12);
+        const PyrGeom q = pyr_geometry(c.oh, c.ow, kLkLevels, kLk.win);
+        for (int l = 0; l < q.levels; ++l) { d.h[l] = q.hs[l]; d.w[l] = q.ws[l]; d.lvl[l] = (unsigned)q.off[l]; }
+        d.top = q.levels - 1; max_top = std::max(max_top, d.top);
+        const size_t need = 2 * q.bytes + al((size_t)c.ow * 12) + al((size_t)c.oh * 12);
+        bool moved = c.pyr_bytes != q.bytes;
         if (c.region_cap < need) {                              // a larger plane than this camera ever had: a new region at the arena's end
             c.region = al(g->arena_used + new_bytes); new_bytes = c.region + need - g->arena_used; c.region_cap = need;
             placed.push_back(ci);
-            c.have_prev = false; c.tab_key[0] = 0; c.n = 0; c.lk_pts.clear();
+            moved = true;
         }
-        if (c.pyr_bytes != pyr_bytes) { c.pyr_bytes = pyr_bytes; c.have_prev = false; c.tab_key[0] = 0; c.n = 0; c.lk_pts.clear(); }
+        if (moved) { c.pyr_bytes = q.bytes; c.s.have_prev = false; c.s.tab_key[0] = 0; c.n = 0; c.s.lk_pts.clear(); }     // neither pyramid nor tables are where they were
         d.H = c.H; d.W = c.W; d.row_stride = c.W * 3; d.resize = resize; d.oh = c.oh; d.ow = c.ow;
-        d.xtab = c.region + 2 * pyr_bytes; d.ytab = d.xtab + al((size_t)c.ow * 12);
-        d.prev = c.region + (size_t)c.slot * pyr_bytes; d.cur = c.region + (size_t)(c.slot ^ 1) * pyr_bytes;
+        d.xtab = c.region + 2 * q.bytes; d.ytab = d.xtab + al((size_t)c.ow * 12);
+        d.prev = c.region + (size_t)c.s.slot * q.bytes; d.cur = c.region + (size_t)(c.s.slot ^ 1) * q.bytes;
         d.n_pts = c.n; d.max_idx = k;
         const size_t np = (size_t)c.oh * c.ow;
         c.t_frame = t_total; t_total += al((size_t)c.H * c.W * 3);                  // frame starts 256-byte aligned: the detector reads them in place
@@ -1424,34 +1383,30 @@ int multi_begin_device(mi355_gmc_multi* g, const uint8_t* const* frames, const i
     std::vector<size_t> t_tab((size_t)na, 0);                   // resize tables that have to go up, staged behind the points
     for (int k = 0; k < na; ++k) {
         MultiCam& c = g->cams[g->active[k]];
-        if (resize && !(c.tab_key[0] == c.H && c.tab_key[1] == c.W && c.tab_key[2] == c.oh && c.tab_key[3] == c.ow)) {
-            t_tab[k] = t_total; t_total += al((size_t)c.ow * 12) + al((size_t)c.oh * 12);
-        }
+        if (resize && !key_is(c.s.tab_key, c.H, c.W, c.oh, c.ow)) { t_tab[k] = t_total; t_total += al((size_t)c.ow * 12) + al((size_t)c.oh * 12); }
     }
     if (new_bytes) {
         const size_t need = g->arena_used + new_bytes;
-        if (g->arena_cap < need) {                              // grow-only: the cameras' previous pyramids move with it
-            const size_t cap = std::max(need + need / 2, (size_t)1 << 20);
-            uint8_t* a = nullptr;
+        if (g->arena.cap < need) {                              // grow-only: the cameras' previous pyramids move with it
+            Buf a;
             auto unplace = [&] { for (int ci : placed) g->cams[ci].region = g->cams[ci].region_cap = 0; };
-            if (hipMalloc(&a, cap) != hipSuccess) { (void)hipGetLastError(); unplace(); return -2; }
-            if (g->arena && g->arena_used) {
-                if (hipMemcpyAsync(a, g->arena, g->arena_used, hipMemcpyDeviceToDevice, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess) {
-                    (void)hipGetLastError(); (void)hipFree(a); unplace(); return -2;
+            if (buf_grow(a, need, std::max(need + need / 2, (size_t)1 << 20)) < 0) { unplace(); return -2; }
+            if (g->arena.p && g->arena_used) {
+                if (hipMemcpyAsync(a.p, g->arena.p, g->arena_used, hipMemcpyDeviceToDevice, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess) {
+                    (void)hipGetLastError(); buf_free(a); unplace(); return -2;
                 }
             }
-            if (g->arena) (void)hipFree(g->arena);
-            g->arena = a; g->arena_cap = cap;
+            buf_free(g->arena);
+            g->arena = a;
         }
         g->arena_used = need;
     }
-    if (grow_pair(g->d_tin, g->h_tin, g->tin_cap, t_total)) return -2;
-    if (grow_pair(g->d_tout, g->h_tout, g->tout_cap, o_total)) return -2;
+    if (grow_pair(g->d_tin, g->h_tin, t_total) < 0 || grow_pair(g->d_tout, g->h_tout, o_total) < 0) return -2;
     // descriptors (+ prefix tables): one image, uploaded only when its bytes differ from what the device holds
     for (int k = 0; k < na; ++k) {
         const MultiCam& c = g->cams[g->active[k]];
         const GmcCam& d = desc[k];
-        desc[k].src = g->d_tin + c.t_frame;
+        desc[k].src = g->d_tin.p + c.t_frame;
         int* p = prefix.data();
         p[kPrefixPlane * (na + 1) + k + 1] = p[kPrefixPlane * (na + 1) + k] + (int)(((size_t)c.oh * c.ow + 255) / 256);
         for (int l = 1; l < kMaxLevels; ++l)
@@ -1459,46 +1414,44 @@ int multi_begin_device(mi355_gmc_multi* g, const uint8_t* const* frames, const i
         p[kPrefixLk * (na + 1) + k + 1] = p[kPrefixLk * (na + 1) + k] + (c.n + kLkWaves - 1) / kLkWaves;
     }
     const size_t desc_b = al((size_t)na * sizeof(GmcCam)), bytes = desc_b + al(prefix.size() * 4);
-    if (g->desc_cap < bytes) { g->desc_bytes = 0; if (grow_pair(g->d_desc, g->h_desc, g->desc_cap, bytes)) return -2; }
+    {
+        const int r = grow_pair(g->d_desc, g->h_desc, bytes);
+        if (r) g->desc_bytes = 0;                               // the device holds no image any more
+        if (r < 0) return -2;
+    }
     std::vector<char> img(bytes, 0);
     std::memcpy(img.data(), desc.data(), (size_t)na * sizeof(GmcCam));
     std::memcpy(img.data() + desc_b, prefix.data(), prefix.size() * 4);
     // stage the frames (a few threads when they are large) and the points, then ONE upload
-    uint8_t* P = g->h_tin;
-    {
-        const int nt = multi_threads(na);
-        auto copy = [&](int k) { const int ci = g->active[k]; const MultiCam& c = g->cams[ci]; std::memcpy(P + c.t_frame, frames[ci], (size_t)c.H * c.W * 3); };
-        if (nt <= 1 || t_frames_end < ((size_t)1 << 20)) { for (int k = 0; k < na; ++k) copy(k); }
-        else {
-            std::vector<std::thread> th;
-            for (int t = 0; t < nt; ++t) th.emplace_back([&, t] { for (int k = t; k < na; k += nt) copy(k); });
-            for (auto& t : th) t.join();
-        }
-    }
+    uint8_t* P = g->h_tin.p;
+    parallel_for(na, t_frames_end < ((size_t)1 << 20) ? 1 : host_threads(na), [&](int k) {
+        const int ci = g->active[k]; const MultiCam& c = g->cams[ci];
+        std::memcpy(P + c.t_frame, frames[ci], (size_t)c.H * c.W * 3);
+    });
     for (int k = 0; k < na; ++k) {
         const MultiCam& c = g->cams[g->active[k]];
-        if (c.n) std::memcpy(P + c.t_pts, c.lk_pts.data(), (size_t)c.n * 8);
-        if (t_tab[k]) { std::memcpy(P + t_tab[k], c.xt.data(), (size_t)c.ow * 12); std::memcpy(P + t_tab[k] + al((size_t)c.ow * 12), c.yt.data(), (size_t)c.oh * 12); }
+        if (c.n) std::memcpy(P + c.t_pts, c.s.lk_pts.data(), (size_t)c.n * 8);
+        if (t_tab[k]) { std::memcpy(P + t_tab[k], c.s.xt.data(), (size_t)c.ow * 12); std::memcpy(P + t_tab[k] + al((size_t)c.ow * 12), c.s.yt.data(), (size_t)c.oh * 12); }
     }
-    GCHK(hipMemcpyAsync(g->d_tin, P, t_total, hipMemcpyHostToDevice, g->stream));
+    GCHK(hipMemcpyAsync(g->d_tin.p, P, t_total, hipMemcpyHostToDevice, g->stream));
     GCHK(hipEventRecord(g->ev_up, g->stream));
     for (int k = 0; k < na; ++k) {
         MultiCam& c = g->cams[g->active[k]];
         if (!t_tab[k]) continue;
-        GCHK(hipMemcpyAsync(g->arena + desc[k].xtab, g->d_tin + t_tab[k], (size_t)c.ow * 12, hipMemcpyDeviceToDevice, g->stream));
-        GCHK(hipMemcpyAsync(g->arena + desc[k].ytab, g->d_tin + t_tab[k] + al((size_t)c.ow * 12), (size_t)c.oh * 12, hipMemcpyDeviceToDevice, g->stream));
-        c.tab_key[0] = c.H; c.tab_key[1] = c.W; c.tab_key[2] = c.oh; c.tab_key[3] = c.ow;
+        GCHK(hipMemcpyAsync(g->arena.p + desc[k].xtab, g->d_tin.p + t_tab[k], (size_t)c.ow * 12, hipMemcpyDeviceToDevice, g->stream));
+        GCHK(hipMemcpyAsync(g->arena.p + desc[k].ytab, g->d_tin.p + t_tab[k] + al((size_t)c.ow * 12), (size_t)c.oh * 12, hipMemcpyDeviceToDevice, g->stream));
+        key_set(c.s.tab_key, c.H, c.W, c.oh, c.ow);
     }
-    if (g->desc_bytes != bytes || std::memcmp(g->h_desc, img.data(), bytes) != 0) {
+    if (g->desc_bytes != bytes || std::memcmp(g->h_desc.p, img.data(), bytes) != 0) {
         // the previous upload out of h_desc has completed: every tick is collected (ev_done) before the next begins
-        std::memcpy(g->h_desc, img.data(), bytes);
-        GCHK(hipMemcpyAsync(g->d_desc, g->h_desc, bytes, hipMemcpyHostToDevice, g->stream));
+        std::memcpy(g->h_desc.p, img.data(), bytes);
+        GCHK(hipMemcpyAsync(g->d_desc.p, g->h_desc.p, bytes, hipMemcpyHostToDevice, g->stream));
         g->desc_bytes = bytes;
     }
-    GCHK(hipMemsetAsync(g->d_tout, 0, (size_t)na * 4, g->stream));
+    GCHK(hipMemsetAsync(g->d_tout.p, 0, (size_t)na * 4, g->stream));
     MultiArgs m{};
-    m.cams = (const GmcCam*)g->d_desc; m.n = na; m.arena = g->arena; m.tin = g->d_tin; m.tout = g->d_tout;
-    const int* d_prefix = (const int*)(g->d_desc + desc_b);
+    m.cams = (const GmcCam*)g->d_desc.p; m.n = na; m.arena = g->arena.p; m.tin = g->d_tin.p; m.tout = g->d_tout.p;
+    const int* d_prefix = (const int*)(g->d_desc.p + desc_b);
     auto grid_of = [&](int table) { return dim3((unsigned)prefix[(size_t)table * (na + 1) + na]); };      // blocks of a launch: the table's total
     {
         m.prefix = d_prefix + (size_t)kPrefixPlane * (na + 1);
@@ -1513,12 +1466,12 @@ int multi_begin_device(mi355_gmc_multi* g, const uint8_t* const* frames, const i
     }
     if (prefix[(size_t)kPrefixLk * (na + 1) + na] > 0) {
         m.prefix = d_prefix + (size_t)kPrefixLk * (na + 1);
-        hipLaunchKernelGGL(lk_multi_kernel, grid_of(kPrefixLk), dim3(64 * kLkWaves), 0, g->stream, m, kLkWin, kLkIters, kLkEps * kLkEps, kLkMinEig);
+        hipLaunchKernelGGL(lk_multi_kernel, grid_of(kPrefixLk), dim3(64 * kLkWaves), 0, g->stream, m, kLk.win, kLk.max_iters, kLk.eps * kLk.eps, kLk.min_eig);
     }
     GCHK(hipGetLastError());
-    GCHK(hipMemcpyAsync(g->h_tout, g->d_tout, o_total, hipMemcpyDeviceToHost, g->stream));
+    GCHK(hipMemcpyAsync(g->h_tout.p, g->d_tout.p, o_total, hipMemcpyDeviceToHost, g->stream));
     GCHK(hipEventRecord(g->ev_done, g->stream));
-    for (int k = 0; k < na; ++k) { MultiCam& c = g->cams[g->active[k]]; c.slot ^= 1; c.have_prev = true; c.ph = c.oh; c.pw = c.ow; }
+    for (int k = 0; k < na; ++k) { MultiCam& c = g->cams[g->active[k]]; c.s.slot ^= 1; c.s.have_prev = true; c.s.ph = c.oh; c.s.pw = c.ow; }
     return 0;
 }
 }  // namespace
@@ -1551,7 +1504,7 @@ extern "C" int mi355_gmc_multi_begin(mi355_gmc_multi* g, const uint8_t* const* f
         const int rc = multi_begin_device(g, frames, heights, widths, downscale);
         if (rc) {
             (void)hipStreamSynchronize(g->stream); (void)hipGetLastError();
-            for (int ci : g->active) { g->cams[ci].have_prev = false; g->cams[ci].have_prev_pts = false; }
+            for (int ci : g->active) cam_lost(g->cams[ci].s);
             return rc;
         }
     }
@@ -1581,7 +1534,7 @@ extern "C" int mi355_gmc_multi_frames(mi355_gmc_multi* g, const uint8_t** dev_fr
     if (!g || g->host || !g->job_active || !dev_frames) return -1;
     GCHK(hipSetDevice(g->device));
     if (!g->active.empty()) GCHK(hipEventSynchronize(g->ev_up));
-    for (int i = 0; i < g->n; ++i) dev_frames[i] = g->cams[i].active ? g->d_tin + g->cams[i].t_frame : nullptr;
+    for (int i = 0; i < g->n; ++i) dev_frames[i] = g->cams[i].active ? g->d_tin.p + g->cams[i].t_frame : nullptr;
     return 0;
 }
 
@@ -1591,9 +1544,7 @@ extern "C" int mi355_gmc_multi_reset(mi355_gmc_multi* g, int camera) {
     if (g->job_active) { std::vector<double> H((size_t)g->n * 6); (void)mi355_gmc_multi_finish(g, H.data()); }
     for (int i = 0; i < g->n; ++i) {
         if (camera >= 0 && i != camera) continue;
-        if (g->host) { (void)mi355_gmc_track_reset(g->single[i]); continue; }
-        MultiCam& c = g->cams[i];
-        c.have_prev_pts = false; c.prev_pts.clear(); c.prev_gray.clear(); c.prev_h = c.prev_w = 0; c.have_prev = false;
+        if (g->host) (void)mi355_gmc_track_reset(g->single[i]); else cam_forget(g->cams[i].s);
     }
     return 0;
 }
@@ -1602,12 +1553,6 @@ extern "C" int mi355_gmc_multi_reset(mi355_gmc_multi* g, int camera) {
 extern "C" int mi355_gmc_multi_state(const mi355_gmc_multi* g, int camera, int* oh, int* ow, int* n_pts, uint8_t* gray_out, float* pts_out, int pts_cap) {
     if (!g || camera < 0 || camera >= g->n || g->job_active) return -1;
     if (g->host) return mi355_gmc_track_state(g->single[camera], oh, ow, n_pts, gray_out, pts_out, pts_cap);
-    const MultiCam& c = g->cams[camera];
-    const int n = c.have_prev_pts ? (int)(c.prev_pts.size() / 2) : 0;
-    if (oh) *oh = c.have_prev_pts ? c.prev_h : 0;
-    if (ow) *ow = c.have_prev_pts ? c.prev_w : 0;
-    if (n_pts) *n_pts = n;
-    if (gray_out && c.have_prev_pts) std::memcpy(gray_out, c.prev_gray.data(), c.prev_gray.size());
-    if (pts_out && pts_cap > 0 && n > 0) std::memcpy(pts_out, c.prev_pts.data(), (size_t)std::min(n, pts_cap) * 8);
+    cam_report(g->cams[camera].s, oh, ow, n_pts, gray_out, pts_out, pts_cap);
     return 0;
 }

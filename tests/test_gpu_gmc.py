@@ -223,6 +223,47 @@ def test_batched_steps_are_the_single_steps_bit_for_bit(shape):
         bat.apply_batch([frames[0], small[0]])
 
 
+@pytest.mark.parametrize("shape", [(97, 131), (24, 40)])
+def test_batched_entry_point_meets_a_pending_step_and_a_reset(shape):
+    """the two state transitions the tests above do not cross.  (a) a single step is pending (``begin``) when ``apply_batch`` is called: the C
+    call refuses (-1 while a step is pending), and ``GMC.apply_batch`` treats the step as stale -- it collects and drops it and forgets the
+    previous frame, so the batch starts a new sequence; (b) ``reset`` between single steps and a batch does the same.  Either way the warps
+    and the state afterwards are those of a fresh object stepped frame by frame, bit for bit."""
+    import ctypes as C
+    from cvsd_amd import _lib
+    h, w = shape
+    g = _smooth_noise(h + 40, w + 120, seed=41, sigma=1.8)
+    frames = [np.repeat(g[3 + (k % 4):3 + (k % 4) + h, 5 * k:5 * k + w, None], 3, axis=2).copy() for k in range(6)]
+
+    def fresh(fs):
+        ref = gmc.GMC(device=0)
+        return np.stack([ref.apply(f) for f in fs]), ref
+
+    want, ref = fresh(frames[2:])
+    # (a) at the C level the call is refused and the step stays pending ...
+    a = gmc.GMC(device=0)
+    a.begin(frames[0])
+    ptrs = (C.c_void_p * 2)(frames[2].ctypes.data, frames[3].ctypes.data)
+    H = np.empty((2, 2, 3), np.float64)
+    assert _lib.lib().mi355_gmc_track_batch(a._obj(), ptrs, 2, h, w, a.downscale, H.ctypes.data) == -1
+    assert a.pending_device_frame() is not None
+    # ... and the Python object drops it and starts over
+    np.testing.assert_array_equal(a.apply_batch(frames[2:]), want)
+    np.testing.assert_array_equal(want[0], np.eye(2, 3))
+    np.testing.assert_array_equal(a.prev_frame, ref.prev_frame)
+    np.testing.assert_array_equal(a.prev_points, ref.prev_points)
+    assert a.pending_device_frame() is None
+    # (b) reset between single steps and a batch
+    b = gmc.GMC(device=0)
+    b.apply(frames[0])
+    b.apply(frames[1])
+    b.reset()
+    assert b.prev_frame is None and b.prev_points is None
+    np.testing.assert_array_equal(b.apply_batch(frames[2:]), want)
+    np.testing.assert_array_equal(b.prev_frame, ref.prev_frame)
+    np.testing.assert_array_equal(b.prev_points, ref.prev_points)
+
+
 def test_pending_frame_is_the_uploaded_frame_and_track_results_do_not_depend_on_sharing_it(monkeypatch):
     """Round 4: ``model.track`` hands the detector pass the copy of the frame its tracker's motion-compensation step has just uploaded
     (``mi355_gmc_pending_frame`` -> ``mi355_yolo_infer_device``).  (a) that device copy is the frame, byte for byte, valid while the step is
