@@ -173,6 +173,9 @@ SIGNATURES = {
     "mi355_shopformer_decoder_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mi355_op_nms": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,
                                C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
+    "mi355_op_nms_ex": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,
+                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
 }
 
 _lib = None

@@ -769,5 +769,75 @@ int mi355_op_nms(int device_id, const float* pred, int n, int nc, int extra, int
     return MI355_OK;
 }
 
+// launch_nms (+ launch_compact_rows) as a pass enqueues them, with every argument the engine sets open to the caller.  Nothing is
+// chosen here: launch_nms picks the fused / two-launch / multi-launch path from n and anchors as it does for the engine.
+int mi355_op_nms_ex(int device_id, const float* pred, const float* best, int n, int nc, int extra, int anchors, float conf, float iou,
+                    const int* classes, int n_classes, int max_det, int max_nms, int kdim, const float* geom, int geom_mode, int pack,
+                    uint32_t* rows, int* counts, uint32_t* packed, int* offsets) {
+    if (!pred || !rows || !counts || n <= 0 || nc <= 0 || extra < 0 || anchors <= 0) return fail(MI355_EINVAL, "bad argument");
+    if (max_det < 1 || max_det > 1024) return fail(MI355_EINVAL, "max_det must lie in 1 .. 1024");
+    if (max_nms < 1) return fail(MI355_EINVAL, "max_nms must be at least 1");
+    if (extra > MI355_MAX_KPT_FLOATS) return fail(MI355_EINVAL, "too many extra columns");
+    if (kdim != 0 && kdim != 2 && kdim != 3) return fail(MI355_EINVAL, "kdim must be 0, 2 or 3");
+    if (kdim && (extra == 0 || extra % kdim)) return fail(MI355_EINVAL, "kdim must divide the extra columns (and needs some)");
+    if (!(conf >= 0.f)) return fail(MI355_EINVAL, "conf must be >= 0 (the sort key orders positive scores only)");
+    if (geom_mode < 0 || geom_mode > 2 || (geom_mode != 0) != (geom != nullptr))
+        return fail(MI355_EINVAL, "geom_mode: 0 without geom, 1 = seven scalars, 2 = [n][7]");
+    if (pack && (!packed || !offsets)) return fail(MI355_EINVAL, "pack needs the packed and offsets outputs");
+    if (n_classes < 0 || (n_classes > 0 && !classes)) return fail(MI355_EINVAL, "bad class list");
+    const int no = 4 + nc + extra;
+    if ((long)anchors * n * no > (1l << 28) || n > (1 << 20)) return fail(MI355_EINVAL, "too many anchors");
+    std::vector<unsigned> mask;
+    if (n_classes > 0) {
+        mask.assign((nc + 31) / 32, 0u);
+        for (int i = 0; i < n_classes; ++i) if (classes[i] >= 0 && classes[i] < nc) mask[classes[i] >> 5] |= 1u << (classes[i] & 31);
+        // the candidate filter indexes the mask with best[]'s class: it must name a class
+        if (best)
+            for (long i = 0; i < (long)anchors * n; ++i)
+                if (!(best[2 * i + 1] >= 0.f && best[2 * i + 1] < (float)nc)) return fail(MI355_EINVAL, "best[] holds a class outside 0 .. nc-1");
+    }
+    HIPCHK(hipSetDevice(device_id));
+    int ap2 = 1; while (ap2 < anchors) ap2 <<= 1;
+    const int RW = (int)(sizeof(mi355_det) / 4);
+    DevMem dm; float *d_in, *d_am, *d_geom = nullptr; float2* d_best; unsigned long long* d_keys; uint32_t *d_rows, *d_packed = nullptr;
+    int *d_counts, *d_offsets = nullptr; unsigned* d_mask = nullptr;
+    const size_t pn = (size_t)n * no * anchors, rw = (size_t)n * max_det * RW;
+    HIPCHK(dm.alloc(&d_in, pn * 4)); HIPCHK(dm.alloc(&d_am, pn * 4)); HIPCHK(dm.alloc(&d_best, (size_t)n * anchors * sizeof(float2)));
+    HIPCHK(dm.alloc(&d_keys, (size_t)n * ap2 * 8)); HIPCHK(dm.alloc(&d_rows, rw * 4));
+    HIPCHK(dm.alloc(&d_counts, (size_t)3 * n * sizeof(int)));
+    HIPCHK(hipMemcpy(d_in, pred, pn * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_rows, rows, rw * 4, hipMemcpyHostToDevice));       // whatever the caller filled them with stays where nothing is written
+    HIPCHK(hipMemset(d_counts, 0xFF, (size_t)3 * n * sizeof(int)));
+    if (pack) {
+        HIPCHK(dm.alloc(&d_packed, rw * 4)); HIPCHK(hipMemcpy(d_packed, packed, rw * 4, hipMemcpyHostToDevice));
+        HIPCHK(dm.alloc(&d_offsets, (size_t)(n + 1) * sizeof(int)));
+        HIPCHK(hipMemcpy(d_offsets, offsets, (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice));
+    }
+    if (!mask.empty()) { HIPCHK(dm.alloc(&d_mask, mask.size() * 4)); HIPCHK(hipMemcpy(d_mask, mask.data(), mask.size() * 4, hipMemcpyHostToDevice)); }
+    if (geom_mode == 2) { HIPCHK(dm.alloc(&d_geom, (size_t)n * 7 * 4)); HIPCHK(hipMemcpy(d_geom, geom, (size_t)n * 7 * 4, hipMemcpyHostToDevice)); }
+    KCHK(launch_transpose_pred(d_in, d_am, n, no, anchors, nullptr));      // [n][no][A] -> [n][A][no]
+    if (best) HIPCHK(hipMemcpy(d_best, best, (size_t)n * anchors * sizeof(float2), hipMemcpyHostToDevice));
+    else KCHK(launch_best_from_pred(d_am, n, anchors, no, nc, d_best, nullptr));
+    NmsArgs na{};
+    na.pred = d_am; na.best = d_best; na.B = n; na.A = anchors; na.no = no; na.nc = nc; na.nk = extra; na.kdim = kdim;
+    na.conf = conf; na.iou = iou; na.max_det = max_det; na.max_nms = max_nms; na.max_wh = 7680.f;
+    na.class_mask = d_mask; na.keys = d_keys; na.Apow2 = ap2; na.scale_back = geom_mode ? 1 : 0; na.gain = 1.f;
+    if (geom_mode == 1) {
+        na.gain = geom[0]; na.pad_x = geom[1]; na.pad_y = geom[2]; na.kpad_x = geom[3]; na.kpad_y = geom[4]; na.orig_w = geom[5]; na.orig_h = geom[6];
+    }
+    na.frame_geom = d_geom;
+    na.out_rows = d_rows; na.out_counts = d_counts;
+    KCHK(launch_nms(na, nullptr));
+    if (pack) KCHK(launch_compact_rows(d_rows, d_counts, n, max_det, RW, d_offsets, d_packed, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(rows, d_rows, rw * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(counts, d_counts, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    if (pack) {
+        HIPCHK(hipMemcpy(packed, d_packed, rw * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(offsets, d_offsets, (size_t)(n + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    return MI355_OK;
+}
+
 }  // extern "C"
 

@@ -493,7 +493,7 @@ __device__ __forceinline__ void nms_greedy_body(const NmsArgs& a, const int b, c
         } else if (q - 7 < nkf) {
             const int j = q - 7;
             float v = p[4 + a.nc + j];
-            if (a.scale_back && (j % kd) < 2) {
+            if (a.scale_back && a.kdim > 0 && (j % kd) < 2) {         // kdim 0: the extra columns are no keypoints, they pass untouched
                 const bool isx = (j % kd) == 0;
                 v -= isx ? kpad_x : kpad_y;
                 v /= gain;

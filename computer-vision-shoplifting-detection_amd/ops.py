@@ -374,6 +374,76 @@ def nms(pred: np.ndarray, nc: int, conf: float = 0.25, iou: float = 0.7, classes
     return out
 
 
+class PostprocessResult:
+    """What :func:`postprocess` hands back: ``rows`` [n, max_det, 58] uint32 (every slot, SENTINEL_BITS where nothing was written),
+    ``counts`` [n] int32 and, with ``pack``, ``packed`` [n * max_det, 58] uint32, ``offsets`` [n + 1] int32 and ``total``."""
+
+    def __init__(self, rows, counts, packed=None, offsets=None):
+        self.rows, self.counts, self.packed, self.offsets = rows, counts, packed, offsets
+        self.total = None if offsets is None else int(offsets[-1])
+
+
+def postprocess(pred: np.ndarray, nc: int, conf: float = 0.25, iou: float = 0.7, classes: Optional[Sequence[int]] = None,
+                max_det: int = 300, max_nms: int = 30000, kdim: int = 0, geom=None, best: Optional[np.ndarray] = None,
+                pack: bool = False, device: int = 0) -> PostprocessResult:
+    """The detector's tail as a pass runs it: candidate filter, sort, greedy suppression, scale-back, rows and (``pack``) row
+    compaction, on pred [n, 4+nc+extra, A].  ``best`` [n, A, 2] (score, class) is the caller's, or computed from pred.  ``kdim``
+    0, 2 or 3 says how scale-back reads the extra columns.  ``geom``: None = rows stay in letterboxed pixels; 7 floats (gain,
+    pad_x, pad_y, kpad_x, kpad_y, orig_w, orig_h) = one geometry for every frame (the kernel's scalars); [n, 7] = one per frame
+    (the mixed-batch table).  Which launches run follows from n and A alone: A > 16384 the multi-launch sort, else n <= 16 the fused
+    sort + greedy kernel, else the two-launch pair.  Rows, packed rows and offsets are filled with SENTINEL_BITS before the launch."""
+    p = _f32(pred)
+    if p.ndim != 3:
+        raise ValueError("pred must be [n, 4+nc+extra, A]")
+    n, no, a = p.shape
+    extra = no - 4 - nc
+    if n <= 0 or a <= 0 or nc <= 0 or extra < 0:
+        raise ValueError("pred must be [n, 4+nc+extra, A] with n, A, nc positive")
+    if not 1 <= max_det <= 1024:
+        raise ValueError("max_det must lie in 1 .. 1024")
+    if max_nms < 1:
+        raise ValueError("max_nms must be at least 1")
+    if extra > _lib.MAX_KPT_FLOATS:
+        raise ValueError("too many extra columns")
+    if kdim not in (0, 2, 3) or (kdim and (extra == 0 or extra % kdim)):
+        raise ValueError("kdim must be 0, 2 or 3 and, with keypoints, divide the extra columns")
+    if not conf >= 0:
+        raise ValueError("conf must be >= 0 (the sort key orders positive scores only)")
+    g, mode = None, 0
+    if geom is not None:
+        g = _f32(geom)
+        if g.shape == (7,):
+            mode = 1
+        elif g.shape == (n, 7):
+            mode = 2
+        else:
+            raise ValueError("geom must be 7 floats or [n, 7]")
+    cls_arr, ncls = None, 0
+    if classes is not None:
+        if len(classes) == 0:
+            raise ValueError("an empty class list keeps nothing: pass None for every class")
+        cls_arr = (C.c_int * len(classes))(*[int(c) for c in classes])
+        ncls = len(classes)
+    b = None
+    if best is not None:
+        b = _f32(best)
+        if b.shape != (n, a, 2):
+            raise ValueError("best must be [n, A, 2]")
+        if ncls and not ((b[..., 1] >= 0) & (b[..., 1] < nc)).all():
+            raise ValueError("with a class list every class of best[] must lie in 0 .. nc-1")
+    rows = np.full((n, max_det, _lib.DET_WORDS), SENTINEL_BITS, np.uint32)
+    counts = np.full(n, -1, np.int32)
+    packed = offsets = None
+    if pack:
+        packed = np.full((n * max_det, _lib.DET_WORDS), SENTINEL_BITS, np.uint32)
+        offsets = np.full(n + 1, SENTINEL_BITS, np.uint32).view(np.int32)
+    _lib.check(_lib.lib().mi355_op_nms_ex(device, p.ctypes.data, b.ctypes.data if b is not None else None, n, nc, extra, a, float(conf),
+                                          float(iou), cls_arr, ncls, int(max_det), int(max_nms), int(kdim),
+                                          g.ctypes.data if g is not None else None, mode, int(pack), rows.ctypes.data, counts.ctypes.data,
+                                          packed.ctypes.data if pack else None, offsets.ctypes.data if pack else None))
+    return PostprocessResult(rows, counts, packed, offsets)
+
+
 def plan_versions(n: int, h: int, w: int, cin: int, cout: int, k: int, stride: int = 1, src_cs: int = 0, dst_cs: int = 0, res_cs: int = 0,
                   f2_cout: int = 0, f2_dst_cs: int = 0, half: bool = False):
     """Kernel versions of the candidate launch plans the planner offers for this conv (host-only query, runs without a GPU):

@@ -455,6 +455,18 @@ int  mi355_op_letterbox_multi(int device_id, const uint8_t* const* frames, const
 int  mi355_op_nms(int device_id, const float* pred, int n, int nc, int extra, int anchors, float conf, float iou,
                   const int* classes, int n_classes, int max_det, mi355_det* out_rows, int out_capacity_per_image,
                   int* out_counts);
+/* The same launches with every argument a pass sets open to the caller, plus the row compaction behind them.  pred as above; best
+ * [n][A][2] (score, class) or NULL (then computed from pred's class columns as mi355_op_nms does).  kdim 0, 2 or 3: how the `extra`
+ * columns are read by scale-back (x, y[, conf] per keypoint; 0 = no keypoints).  geom_mode 0: no scale-back (geom NULL); 1: geom =
+ * {gain, pad_x, pad_y, kpad_x, kpad_y, orig_w, orig_h} for every frame; 2: geom[n][7], one row per frame.  rows[n][max_det][58 words]
+ * and, with pack != 0, packed[n * max_det][58 words] and offsets[n + 1] are read in and handed back, so whatever the launches do not
+ * write keeps the caller's bits; counts[n] receives the kept rows per frame.  Which launch path runs follows from n and anchors
+ * alone: anchors > 16384 the multi-launch sort, else n <= 16 the fused kernel, else sort + greedy.  Refused with
+ * MI355_EINVAL before any device call: max_det outside 1 .. 1024, max_nms < 1, extra > MI355_MAX_KPT_FLOATS, kdim not 0 / 2 / 3 or
+ * not dividing extra, conf < 0, and -- with a class list -- a class of a supplied best[] outside 0 .. nc-1. */
+int  mi355_op_nms_ex(int device_id, const float* pred, const float* best, int n, int nc, int extra, int anchors, float conf, float iou,
+                     const int* classes, int n_classes, int max_det, int max_nms, int kdim, const float* geom, int geom_mode, int pack,
+                     uint32_t* rows, int* counts, uint32_t* packed, int* offsets);
 
 /* ---- Shopformer: pose windows -> anomaly score ----------------------------------------------------------------
  * The score path of the reference's shopformer/ network in eval() mode as one fused kernel launch per call, whatever n is.
