@@ -2,7 +2,8 @@
 from .graph import build_program, parse_model_name  # noqa: F401
 from .results import Boxes, Keypoints, Results  # noqa: F401
 from .engine import YOLO  # noqa: F401
-from .shopformer import Shopformer, StreamScorer, score_poselift, windows_from_poselift  # noqa: F401
+from .shopformer import (MultiStreamScorer, Shopformer, StreamScorer, score_poselift, score_poselift_many,  # noqa: F401
+                         windows_from_poselift)
 
 __all__ = ["YOLO", "Results", "Boxes", "Keypoints", "build_program", "parse_model_name",
-           "Shopformer", "StreamScorer", "score_poselift", "windows_from_poselift"]
+           "Shopformer", "StreamScorer", "MultiStreamScorer", "score_poselift", "score_poselift_many", "windows_from_poselift"]

@@ -50,6 +50,7 @@ class Timing(C.Structure):
 
 
 DET_WORDS = C.sizeof(Det) // 4          # 58 32-bit words per row
+POSE_F32, POSE_F64 = 0, 1               # MI355_POSE_F32 / MI355_POSE_F64: the element type of a pose array
 _P = C.POINTER
 _u8p, _f32p, _i32p = _P(C.c_uint8), _P(C.c_float), _P(C.c_int)
 
@@ -171,6 +172,8 @@ SIGNATURES = {
     "mi355_shopformer_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mi355_shopformer_decode_device_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "mi355_shopformer_decoder_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi355_pose_windows": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mi355_shopformer_score_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mi355_op_nms": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,
                                C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
     "mi355_op_nms_ex": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,

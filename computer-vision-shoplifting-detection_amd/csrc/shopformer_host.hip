@@ -2,8 +2,10 @@
 // mi355_shopformer_* of include/mi355_yolo.h.  One kernel launch per call whatever the number of windows for variant 1, two for variant 2
 // (version-2 images): tokenizer, then the transformer over row groups of up to 16 windows (shopformer_kernels.hip).
 // Version-3 images hold either variant plus the GCAE decoder: one more launch (shopformer_decoder.hip), only when asked.
+// mi355_shopformer_score_poses takes poses and window starts instead of windows: one launch more, pose_windows.hip.
 #include "engine_internal.h"
 #include "shopformer.h"
+#include "pose_windows.h"
 
 #include <cmath>
 #include <cstddef>
@@ -35,11 +37,17 @@ struct mi355_shopformer {
     long long macs_dec = 0;
     float *d_pose = nullptr, *d_perr = nullptr;
     size_t cap_dec = 0;                 // windows d_pose / d_perr hold
+    // mi355_shopformer_score_poses: the uploaded poses and window starts
+    void* d_pose_in = nullptr;
+    int* d_starts = nullptr;
+    size_t cap_pose_in = 0, cap_starts = 0;     // bytes / entries
     ~mi355_shopformer() {
         if (d_weights) (void)hipFree(d_weights);
         if (d_params) (void)hipFree(d_params);
         if (d_dec) (void)hipFree(d_dec);
         for (float* q : {d_win, d_score, d_tok, d_rec, d_tsc, d_tok_scratch, d_pose, d_perr}) if (q) (void)hipFree(q);
+        if (d_pose_in) (void)hipFree(d_pose_in);
+        if (d_starts) (void)hipFree(d_starts);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -325,6 +333,20 @@ int ensure_scratch(mi355_shopformer* h, size_t n) {
     return MI355_OK;
 }
 
+int ensure_pose_in(mi355_shopformer* h, size_t bytes, size_t n) {
+    if (bytes > h->cap_pose_in) {
+        if (h->d_pose_in) { (void)hipFree(h->d_pose_in); h->d_pose_in = nullptr; h->cap_pose_in = 0; }
+        HIPCHK(hipMalloc(&h->d_pose_in, bytes));
+        h->cap_pose_in = bytes;
+    }
+    if (n > h->cap_starts) {
+        if (h->d_starts) { (void)hipFree(h->d_starts); h->d_starts = nullptr; h->cap_starts = 0; }
+        HIPCHK(hipMalloc(&h->d_starts, n * 4));
+        h->cap_starts = n;
+    }
+    return MI355_OK;
+}
+
 constexpr int kOutputsOld = (int)offsetof(mi355_shopformer_outputs_t, poses);      // the struct before the decoder's two pointers
 
 }  // namespace
@@ -373,6 +395,33 @@ static int run2_device(mi355_shopformer* h, const float* win, int n, float* scor
     return MI355_OK;
 }
 
+// n windows wait in h->d_win (enqueued on h->stream, the staging buffers large enough): the score launch(es), the decoder's when
+// `out` asks for poses, the downloads into `out`'s host pointers, and the wait for them
+static int score_staged(mi355_shopformer* h, int n, const mi355_shopformer_outputs_t* out) {
+    const SfParams& p = h->p;
+    const size_t per = (size_t)p.ntok * p.Din * 4;
+    if (p.variant == 2) {
+        const int rc = run2_device(h, h->d_win, n, out->scores ? h->d_score : nullptr, out->token_scores ? h->d_tsc : nullptr, h->d_tok,
+                                   out->recon ? h->d_rec : nullptr, h->stream);
+        if (rc) return rc;
+    } else {
+        KCHK(launch_shopformer(h->d_params, p.G, h->d_win, n, h->d_score, out->tokens || out->poses ? h->d_tok : nullptr,
+                               out->recon ? h->d_rec : nullptr, h->stream, &h->launches));
+    }
+    if (out->poses) {
+        KCHK(launch_shopformer_decoder(h->d_dec, h->dp.G, h->lds_dec, h->d_tok, n, h->d_pose, out->pose_error ? h->d_perr : nullptr, h->d_win,
+                                       h->stream, &h->launches));
+        HIPCHK(hipMemcpyAsync(out->poses, h->d_pose, (size_t)n * 2 * p.T * p.V * 4, hipMemcpyDeviceToHost, h->stream));
+        if (out->pose_error) HIPCHK(hipMemcpyAsync(out->pose_error, h->d_perr, (size_t)n * p.T * p.V * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (out->scores) HIPCHK(hipMemcpyAsync(out->scores, h->d_score, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (out->token_scores) HIPCHK(hipMemcpyAsync(out->token_scores, h->d_tsc, (size_t)n * p.ntok * 4, hipMemcpyDeviceToHost, h->stream));
+    if (out->tokens) HIPCHK(hipMemcpyAsync(out->tokens, h->d_tok, n * per, hipMemcpyDeviceToHost, h->stream));
+    if (out->recon) HIPCHK(hipMemcpyAsync(out->recon, h->d_rec, n * per, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MI355_OK;
+}
+
 int mi355_shopformer_score_ex_device_async(mi355_shopformer* h, const float* windows_dev, int n, const mi355_shopformer_outputs_t* out,
                                            void* stream) {
     if (!h || n < 0 || (n > 0 && !windows_dev)) return fail(MI355_EINVAL, "null argument or negative count");
@@ -405,28 +454,8 @@ int mi355_shopformer_score_ex(mi355_shopformer* h, const float* windows, int n, 
     HIPCHK(hipSetDevice(h->device));
     rc = ensure_cap(h, (size_t)n); if (rc) return rc;
     if (out->poses) { rc = ensure_cap_dec(h, (size_t)n); if (rc) return rc; }
-    const SfParams& p = h->p;
-    const size_t per = (size_t)p.ntok * p.Din * 4;
-    HIPCHK(hipMemcpyAsync(h->d_win, windows, (size_t)n * 2 * p.T * p.V * 4, hipMemcpyHostToDevice, h->stream));
-    if (p.variant == 2) {
-        rc = run2_device(h, h->d_win, n, out->scores ? h->d_score : nullptr, out->token_scores ? h->d_tsc : nullptr, h->d_tok,
-                         out->recon ? h->d_rec : nullptr, h->stream);
-        if (rc) return rc;
-    } else {
-        KCHK(launch_shopformer(h->d_params, p.G, h->d_win, n, h->d_score, h->d_tok, out->recon ? h->d_rec : nullptr, h->stream, &h->launches));
-    }
-    if (out->poses) {
-        KCHK(launch_shopformer_decoder(h->d_dec, h->dp.G, h->lds_dec, h->d_tok, n, h->d_pose, out->pose_error ? h->d_perr : nullptr, h->d_win,
-                                       h->stream, &h->launches));
-        HIPCHK(hipMemcpyAsync(out->poses, h->d_pose, (size_t)n * 2 * p.T * p.V * 4, hipMemcpyDeviceToHost, h->stream));
-        if (out->pose_error) HIPCHK(hipMemcpyAsync(out->pose_error, h->d_perr, (size_t)n * p.T * p.V * 4, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (out->scores) HIPCHK(hipMemcpyAsync(out->scores, h->d_score, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (out->token_scores) HIPCHK(hipMemcpyAsync(out->token_scores, h->d_tsc, (size_t)n * p.ntok * 4, hipMemcpyDeviceToHost, h->stream));
-    if (out->tokens) HIPCHK(hipMemcpyAsync(out->tokens, h->d_tok, n * per, hipMemcpyDeviceToHost, h->stream));
-    if (out->recon) HIPCHK(hipMemcpyAsync(out->recon, h->d_rec, n * per, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MI355_OK;
+    HIPCHK(hipMemcpyAsync(h->d_win, windows, (size_t)n * 2 * h->p.T * h->p.V * 4, hipMemcpyHostToDevice, h->stream));
+    return score_staged(h, n, out);
 }
 
 int mi355_shopformer_score_device_async(mi355_shopformer* h, const float* windows_dev, int n, float* scores_dev, float* tokens_dev,
@@ -458,6 +487,26 @@ int mi355_shopformer_score(mi355_shopformer* h, const float* windows, int n, flo
     if (recon) HIPCHK(hipMemcpyAsync(recon, h->d_rec, n * per, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return MI355_OK;
+}
+
+int mi355_shopformer_score_poses(mi355_shopformer* h, const void* poses, int dtype, int P, int V_src, const int* starts, int n, int neck,
+                                 const mi355_shopformer_outputs_t* out) {
+    if (!h) return fail(MI355_EINVAL, "null argument");
+    mi355_shopformer_outputs_t full;
+    int rc = outputs_ok(h, out, &full); if (rc) return rc;
+    const SfParams& p = h->p;
+    rc = pose_windows_validate(poses, dtype, P, V_src, starts, n, p.T, p.V, neck); if (rc) return rc;
+    if (n == 0) return MI355_OK;
+    if (p.variant != 2 && !full.scores) return fail(MI355_EINVAL, "the shopformer/ variant needs the scores output");
+    HIPCHK(hipSetDevice(h->device));
+    rc = ensure_cap(h, (size_t)n); if (rc) return rc;
+    if (full.poses) { rc = ensure_cap_dec(h, (size_t)n); if (rc) return rc; }
+    const size_t pose_bytes = (size_t)P * V_src * 2 * (dtype == MI355_POSE_F64 ? 8 : 4);
+    rc = ensure_pose_in(h, pose_bytes, (size_t)n); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(h->d_pose_in, poses, pose_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_starts, starts, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    KCHK(launch_pose_windows(h->d_pose_in, dtype, V_src, h->d_starts, n, p.T, p.V, neck, h->d_win, h->stream, &h->launches));
+    return score_staged(h, n, &full);
 }
 
 int mi355_shopformer_decode_device_async(mi355_shopformer* h, const float* tokens_dev, int n, float* poses_dev, void* stream) {

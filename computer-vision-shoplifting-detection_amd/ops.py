@@ -137,6 +137,31 @@ def decode(levels, nc: int, nkpt: int = 0, kdim: int = 0, mode: str = "full", ga
     return (pred, best, count.value) if mode == "split" else (pred, best)
 
 
+def pose_array(poses):
+    """-> (poses as a C-contiguous [P, V_src, 2] array, its MI355_POSE_* code); anything but float32 / float64 is refused, because the
+    window arithmetic runs in the poses' own type"""
+    p = np.asarray(poses)
+    if p.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"poses must be float32 or float64, got {p.dtype}")
+    if p.ndim != 3 or p.shape[2] != 2:
+        raise ValueError(f"poses must be [P, V_src, 2] (x, y), got {tuple(p.shape)}")
+    return np.ascontiguousarray(p), (_lib.POSE_F64 if p.dtype == np.float64 else _lib.POSE_F32)
+
+
+def pose_windows(poses: np.ndarray, starts, seq_len: int, num_keypoints: int, neck: bool = False, device: int = 0) -> np.ndarray:
+    """The pose-window kernel alone (csrc/pose_windows.hip): ``poses`` [P, V_src, 2] float32 or float64, window i = the ``seq_len``
+    consecutive poses from ``starts[i]`` -> [n, 2, seq_len, num_keypoints] float32, the bits ``shopformer._window_tensor`` gives for
+    those poses.  ``device=-1`` runs the kernel's per-window routine compiled for the host (no GPU is touched).  Starts that leave
+    the array, ``neck`` without 18 keypoints or without both shoulders are refused before any launch (ValueError).  The output is
+    filled with SENTINEL before the launch."""
+    p, code = pose_array(poses)
+    st = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1)
+    out = _sentinel((len(st), 2, int(seq_len), int(num_keypoints)))
+    _lib.check(_lib.lib().mi355_pose_windows(int(device), p.ctypes.data, code, p.shape[0], p.shape[1], st.ctypes.data, len(st), int(seq_len),
+                                             int(num_keypoints), int(bool(neck)), out.ctypes.data))
+    return out
+
+
 class SparseBoxResult:
     """What :func:`sparse_box` hands back: ``pred`` [n, A, no]; per level ``mid`` [n, h, w, mid_cs], ``dil`` / ``cand`` (the first
     min(count, cap) list entries, int32, in the kernel's order), ``n_dil`` / ``n_cand`` (the counts the device holds, also beyond

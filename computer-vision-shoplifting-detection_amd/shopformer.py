@@ -16,7 +16,9 @@ model gains the reference's fourth output: ``forward(x, poses=True)`` adds ``gca
 
 This module holds (a) the loader: reference-named state dict -> folded tensors -> a small self-describing weight image whose
 matrices are already in the kernel's MFMA fragment order, (b) ``Shopformer``, the ctypes front of ``mi355_shopformer_*``, and (c) the
-host side between the tracker and the network: ``windows_from_poselift``, ``score_poselift``, ``StreamScorer``.
+host side between the tracker and the network: ``windows_from_poselift``, ``score_poselift``, ``StreamScorer``, and their forms that
+build the windows on the device (csrc/pose_windows.hip): ``Shopformer.score_poses``, ``score_poselift(on_device=True)``,
+``score_poselift_many``, ``MultiStreamScorer``.
 """
 from __future__ import annotations
 
@@ -681,6 +683,24 @@ class Shopformer:
     def predict(self, windows, threshold: float = 0.5) -> np.ndarray:
         return (self.score(windows) > threshold).astype(np.int64)
 
+    def score_poses(self, poses, starts, reduction: str = "mean") -> np.ndarray:
+        """``score`` on windows the device builds itself: ``poses`` [P, V_src, 2] float32 or float64 (the x, y of
+        every retained pose), window i = the ``seq_len`` consecutive poses from ``starts[i]``.  One upload, the window launch, the
+        score launch(es): the same bits as ``score(_window_tensor(...))`` of those poses.  The neck joint follows ``self.neck``."""
+        from . import ops
+        if reduction not in ("mean", "none"):
+            raise ValueError(f"Unknown reduction: {reduction}")
+        if reduction == "none" and self.variant != 2:
+            raise ValueError("reduction='none' exists only for the shopformer_2 variant: the shopformer/ network has no per-token score")
+        p, code = ops.pose_array(poses)
+        st = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1)
+        res = np.empty(len(st) if reduction == "mean" else (len(st), self.n_tokens), np.float32)
+        o = _outputs(scores=res.ctypes.data) if reduction == "mean" else _outputs(token_scores=res.ctypes.data)
+        if len(st):
+            _lib.check(_lib.lib().mi355_shopformer_score_poses(self._h, p.ctypes.data, code, p.shape[0], p.shape[1], st.ctypes.data, len(st),
+                                                               int(self.neck), C.byref(o)))
+        return res
+
     def score_device_async(self, windows_dev: int, n: int, scores_dev: int, stream: int = 0, tokens_dev: int = 0, recon_dev: int = 0,
                            token_scores_dev: int = 0, poses_dev: int = 0, pose_error_dev: int = 0) -> None:
         """device pointers in, device pointers out, enqueued on the caller's stream (0 = the null stream); returns without waiting.
@@ -747,17 +767,7 @@ def windows_from_poselift(data: dict, seq_len: int = 12, stride: int = 6, max_ga
     without it joints beyond those delivered are zero."""
     if neck and num_keypoints != 18:
         raise ValueError("neck=True needs num_keypoints=18 (17 COCO joints + the neck)")
-    per: Dict[int, Dict[int, np.ndarray]] = {}
-    for fnum, people in data.items():
-        if not people or not isinstance(people, dict):
-            continue
-        for pid, rec in people.items():
-            if not isinstance(rec, (list, tuple)) or len(rec) < 2:
-                continue
-            k = np.array(rec[1])
-            if np.isnan(k).any() or np.isinf(k).any():
-                continue
-            per.setdefault(pid, {})[int(fnum)] = k
+    per = _people(data)
     xs, index = [], []
     for pid, fr in per.items():
         idx = sorted(fr)
@@ -771,11 +781,84 @@ def windows_from_poselift(data: dict, seq_len: int = 12, stride: int = 6, max_ga
     return x, index
 
 
-def score_poselift(model, data: dict, stride: int = 6, max_gap: int = 5):
-    """-> (scores [n], index) for every window of every person of one video's PoseLift dict"""
+def _people(data: dict) -> Dict[int, Dict[int, np.ndarray]]:
+    """person -> {frame: keypoints} in order of first appearance; records without keypoints and poses with NaN / inf are left out"""
+    per: Dict[int, Dict[int, np.ndarray]] = {}
+    for fnum, people in data.items():
+        if not people or not isinstance(people, dict):
+            continue
+        for pid, rec in people.items():
+            if not isinstance(rec, (list, tuple)) or len(rec) < 2:
+                continue
+            k = np.array(rec[1])
+            if np.isnan(k).any() or np.isinf(k).any():
+                continue
+            per.setdefault(pid, {})[int(fnum)] = k
+    return per
+
+
+def pack_poselift(data: dict, seq_len: int = 12, stride: int = 6, max_gap: int = 5):
+    """The offline loader's window cut without building a window: -> (poses, starts, index).  ``poses`` [P, rows, 2] holds the x, y
+    of every retained pose, persons in order of first appearance, each person's frames sorted; window i is the ``seq_len`` poses from
+    ``starts[i]`` (int32); ``index`` is what ``windows_from_poselift`` returns.  The cut comes from each person's sorted frame numbers
+    alone: starts 0, stride, ..., a start dropped when one of its ``seq_len - 1`` frame gaps exceeds ``max_gap``.
+    ``poses`` is None when the dict is not one the device path covers: its poses must share ONE float dtype (float32 or float64) and
+    ONE row count; mixed dtypes, integer poses and ragged row counts are left to the host path (where numpy promotes or refuses)."""
+    per = _people(data)
+    chunks, starts, index, off = [], [], [], 0
+    sig = {(k.dtype, k.size // 3 if k.size % 3 == 0 else -1) for fr in per.values() for k in fr.values()}
+    ok = len(sig) == 1 and next(iter(sig))[0] in (np.dtype(np.float32), np.dtype(np.float64)) and next(iter(sig))[1] > 0
+    for pid, fr in per.items():
+        idx = np.array(sorted(fr), np.int64)
+        if ok:
+            chunks.append(np.asarray([fr[int(f)] for f in idx]).reshape(len(idx), -1, 3)[:, :, :2])     # (V, 3) or the flat (3 V,) form
+        s = np.arange(0, len(idx) - seq_len + 1, stride)
+        if len(s):
+            broken = np.concatenate([[0], np.cumsum(np.diff(idx) > max_gap)])         # gaps above max_gap before each position
+            s = s[broken[s + seq_len - 1] == broken[s]]
+            starts.append(off + s)
+            index += [(int(pid), int(a), int(b)) for a, b in zip(idx[s], idx[s + seq_len - 1])]
+        off += len(idx)
+    st = np.concatenate(starts).astype(np.int32) if starts else np.zeros(0, np.int32)
+    return (np.concatenate(chunks) if ok else None), st, index
+
+
+def _device_poses(model, poses) -> bool:
+    """the rule of ``score_poselift(on_device=True)``: the model scores poses itself, the dict packed to one float array, and a neck
+    model got at least the 17 COCO rows (with fewer, the host path pads with float64 zeros and numpy promotes the window)"""
+    return hasattr(model, "score_poses") and poses is not None and not (bool(getattr(model, "neck", False)) and poses.shape[1] < 17)
+
+
+def score_poselift(model, data: dict, stride: int = 6, max_gap: int = 5, on_device: bool = False):
+    """-> (scores [n], index) for every window of every person of one video's PoseLift dict.
+    ``on_device=True``: the windows are built on the GPU (``model.score_poses``: one upload of the poses, one window launch, the score
+    launches) instead of one by one on the host; same scores, same index, bit for bit.  That path covers dicts whose poses all share
+    one float dtype (float32 or float64) and one row count, at least 17 rows when the model has a neck joint; any other dict (mixed
+    dtypes, integer poses, ragged row counts, a neck model fed fewer than 17 rows), and a model without ``score_poses``, takes the host
+    path for that call."""
+    if on_device:
+        poses, starts, index = pack_poselift(data, model.seq_len, stride, max_gap)
+        if _device_poses(model, poses):
+            return model.score_poses(poses, starts), index
     x, index = windows_from_poselift(data, seq_len=model.seq_len, stride=stride, max_gap=max_gap, num_keypoints=model.num_keypoints,
                                      neck=bool(getattr(model, "neck", False)))
     return model.score(x), index
+
+
+def score_poselift_many(model, datas, stride: int = 6, max_gap: int = 5, on_device: bool = True):
+    """``score_poselift`` for every dict of ``datas`` (a tree of videos) -> ``[(scores, index), ...]``.  With ``on_device`` the whole
+    tree is ONE ``model.score_poses`` call: the videos' pose arrays concatenated, each video's offset added to its starts.  That needs
+    every dict that holds poses to pass ``score_poselift``'s device rule with the same dtype and row count; otherwise each dict is
+    scored by ``score_poselift`` on the host path."""
+    datas = list(datas)
+    packed = [pack_poselift(d, model.seq_len, stride, max_gap) for d in datas] if on_device else []
+    full = [p for p in packed if p[0] is not None or p[2]]                            # dicts without a retained pose contribute nothing
+    if not on_device or not full or not all(_device_poses(model, p[0]) for p in full) or len({(p[0].dtype, p[0].shape[1]) for p in full}) != 1:
+        return [score_poselift(model, d, stride, max_gap) for d in datas]
+    offs = np.cumsum([0] + [len(p[0]) if p[0] is not None else 0 for p in packed])
+    scores = model.score_poses(np.concatenate([p[0] for p in full]), np.concatenate([p[1] + o for p, o in zip(packed, offs)]).astype(np.int32))
+    cuts = np.cumsum([0] + [len(p[2]) for p in packed])
+    return [(scores[a:b], p[2]) for p, a, b in zip(packed, cuts, cuts[1:])]
 
 
 class StreamScorer:
@@ -793,8 +876,10 @@ class StreamScorer:
         self._ring: Dict[int, list] = {}
         self._seen: Dict[int, int] = {}
 
-    def update(self, frame_num: int, track_rows, keypoints):
-        done, xs = [], []
+    def cut(self, frame_num: int, track_rows, keypoints) -> list:
+        """take one frame in -> ``[(person_id, first_frame, last_frame, poses)]``, the windows it completes, ``poses`` the window's
+        ``seq_len`` keypoint arrays (float32, (rows, 3)); the half of ``update`` that ``MultiStreamScorer`` shares"""
+        done = []
         for pid in [p for p, ring in self._ring.items() if frame_num - ring[-1][0] > self.max_gap]:
             del self._ring[pid]
         for row, kp in zip(np.asarray(track_rows), np.asarray(keypoints)):
@@ -810,9 +895,50 @@ class StreamScorer:
                 fr = [f for f, _ in ring]
                 if any(b - a > self.max_gap for a, b in zip(fr, fr[1:])):
                     continue
-                xs.append(_window_tensor([p for _, p in ring], self.num_keypoints, self.neck))
-                done.append((pid, fr[0], fr[-1]))
+                done.append((pid, fr[0], fr[-1], [p for _, p in ring]))
+        return done
+
+    def update(self, frame_num: int, track_rows, keypoints):
+        done = self.cut(frame_num, track_rows, keypoints)
         if not done:
             return []
-        scores = self.model.score(np.stack(xs))
-        return [(pid, a, b, float(s)) for (pid, a, b), s in zip(done, scores)]
+        scores = self.model.score(np.stack([_window_tensor(poses, self.num_keypoints, self.neck) for _, _, _, poses in done]))
+        return [(pid, a, b, float(s)) for (pid, a, b, _), s in zip(done, scores)]
+
+
+class MultiStreamScorer:
+    """``StreamScorer`` for the N cameras of one store: ``update(frame_num, cams)`` takes one tick, ``cams[i]`` = ``(track_rows,
+    keypoints)`` of camera i or None for a camera without a frame (it is not stepped); ``frame_num`` is one int or one per camera.
+    It returns, per camera, the list that camera's own ``StreamScorer.update`` would return, the same floats: every camera cuts its
+    windows with ``StreamScorer.cut`` on state of its own, and the tick's completed windows of ALL cameras go through ONE
+    ``model.score_poses`` call (poses stacked, ``starts = arange(n) * seq_len``): one upload and one window launch per tick instead of
+    N window builders, N uploads and N score calls.  A tick whose poses do not share one row count (at least 17 with a neck model),
+    and a model without ``score_poses``, builds the windows on the host and calls ``model.score`` once."""
+
+    def __init__(self, model, n_cameras: int, stride: int = 6, max_gap: int = 5):
+        self.model, self.seq_len = model, model.seq_len
+        self.cameras = [StreamScorer(model, stride, max_gap) for _ in range(int(n_cameras))]
+
+    def update(self, frame_num, cams):
+        cams = list(cams)
+        if len(cams) != len(self.cameras):
+            raise ValueError(f"one entry per camera: expected {len(self.cameras)}, got {len(cams)}")
+        frames = [int(frame_num)] * len(cams) if np.ndim(frame_num) == 0 else [int(f) for f in frame_num]
+        if len(frames) != len(cams):
+            raise ValueError("frame_num is one int or one per camera")
+        done = [cam.cut(f, *c) if c is not None else [] for cam, f, c in zip(self.cameras, frames, cams)]
+        wins = [w for d in done for w in d]
+        if not wins:
+            return [[] for _ in cams]
+        rows = {k.shape[0] for w in wins for k in w[3]}
+        first = self.cameras[0]
+        if hasattr(self.model, "score_poses") and len(rows) == 1 and not (first.neck and min(rows) < 17):
+            poses = np.stack([k[:, :2] for w in wins for k in w[3]])
+            scores = self.model.score_poses(poses, np.arange(len(wins), dtype=np.int32) * self.seq_len)
+        else:
+            scores = self.model.score(np.stack([_window_tensor(w[3], first.num_keypoints, first.neck) for w in wins]))
+        out, at = [], 0
+        for d in done:
+            out.append([(pid, a, b, float(s)) for (pid, a, b, _), s in zip(d, scores[at:at + len(d)])])
+            at += len(d)
+        return out

@@ -531,6 +531,26 @@ typedef struct {
 } mi355_shopformer_decoder_info_t;
 int  mi355_shopformer_decoder_info(const mi355_shopformer* h, mi355_shopformer_decoder_info_t* info);
 
+/* ---- Pose windows on the device -------------------------------------------------------------------------------
+ * poses [P][V_src][2]: the x, y of every retained pose, MI355_POSE_F32 or MI355_POSE_F64; window i is the seq_len consecutive poses
+ * starts[i] .. starts[i] + seq_len - 1 (windows may overlap).  windows [n][2][seq_len][V] fp32 = what the host loader
+ * (cvsd_amd/shopformer.py:_window_tensor) makes of them, bit for bit: joints beyond min(V, V_src) zero, with `neck` joint 17 from the
+ * shoulders (joints 5, 6), centred on the mean of the non-zero joints, divided by the largest |offset| + 1e-6, every operation in the
+ * poses' own type in numpy's order, non-finite quotients zeroed, one rounding to fp32.
+ * Refused with MI355_EINVAL on the host, before any device call: starts[i] < 0 or starts[i] + seq_len > P, V_src < 1, neck with
+ * V != 18 or V_src < 7, seq_len * V > 768, an unknown dtype.  n == 0 launches nothing.
+ * mi355_pose_windows is the parity hook: host memory in, host memory out (words of windows_out the kernel does not write keep the
+ * caller's content); device = -1 runs the same per-window routine compiled for the host and never touches a GPU.
+ * mi355_shopformer_score_poses is the whole path in one call: ONE upload of poses and starts, the window launch into the handle's
+ * window buffer (seq_len and V are the model's), the score launch(es) of mi355_shopformer_score_ex unchanged, the download of what
+ * `out` asks for (host pointers).  The handle's launch counter counts the window launch too. */
+#define MI355_POSE_F32 0
+#define MI355_POSE_F64 1
+int  mi355_pose_windows(int device_or_minus1, const void* poses, int dtype, int P, int V_src, const int* starts, int n, int seq_len, int V,
+                        int neck, float* windows_out);
+int  mi355_shopformer_score_poses(mi355_shopformer* h, const void* poses, int dtype, int P, int V_src, const int* starts, int n, int neck,
+                                  const mi355_shopformer_outputs_t* out);
+
 #ifdef __cplusplus
 }
 #endif
