@@ -9,6 +9,7 @@
 // window sums are associated differently -- lane-wise then butterfly -- so results agree to rounding, not bit for bit).
 // The pyramids (5-tap Gaussian pyrDown, integer arithmetic: exact) are built by a kernel per level.
 #include "../../include/mi355_yolo.h"
+#include "dev_buf.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -439,25 +440,8 @@ __global__ __launch_bounds__(256) void corner_mask_kernel(const float* eig, int 
 
 constexpr size_t al(size_t v) { return (v + 255) & ~(size_t)255; }          // every part of a staging / scratch buffer starts 256 bytes aligned
 
-// Grow-only buffer in device or pinned host memory.  The owner says what it needs and, where it keeps slack, what to allocate instead;
-// what a reallocation invalidates is the owner's business too: buf_grow tells it.
-struct Buf {
-    bool pinned = false;
-    uint8_t* p = nullptr; size_t cap = 0;
-};
-void buf_free(Buf& b) {
-    if (b.p) (void)(b.pinned ? hipHostFree(b.p) : hipFree(b.p));
-    b.p = nullptr; b.cap = 0;
-}
-// 0 = large enough as it is, 1 = reallocated at max(need, alloc) bytes (the contents are gone), -2 = HIP error (the buffer is empty)
-int buf_grow(Buf& b, size_t need, size_t alloc = 0) {
-    if (b.cap >= need) return 0;
-    buf_free(b);
-    alloc = std::max(alloc, need);
-    GCHK(b.pinned ? hipHostMalloc(&b.p, alloc) : hipMalloc(&b.p, alloc));
-    b.cap = alloc;
-    return 1;
-}
+// the grow-only buffer in device or pinned host memory (dev_buf.h): buf_grow -> 0 as it is, 1 reallocated, -2 HIP error
+using mi355::Buf; using mi355::buf_free; using mi355::buf_grow;
 // a device buffer and its pinned mirror, a quarter of slack on both
 int grow_pair(Buf& d, Buf& h, size_t need) {
     const int rd = buf_grow(d, need, need + need / 4), rh = buf_grow(h, need, need + need / 4);

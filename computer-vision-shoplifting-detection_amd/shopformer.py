@@ -597,53 +597,34 @@ class Shopformer:
             raise ValueError(f"windows must be [N, 2, {self.seq_len}, {self.num_keypoints}], got {tuple(w.shape)}")
         return w
 
+    def _run(self, want, n: int, call) -> Dict[str, np.ndarray]:
+        """allocates the host outputs ``want`` names (fields of ``ShopformerOutputs``) for ``n`` windows, builds the struct and, for
+        n > 0, hands it to ``call``: the window form or the poses form of the ``_ex`` entry points -> {field: array}"""
+        tok, win = (self.n_tokens, self.token_dim), (self.seq_len, self.num_keypoints)
+        shapes = {"scores": (), "token_scores": tok[:1], "tokens": tok, "recon": tok, "poses": (2,) + win, "pose_error": win}
+        out = {k: np.empty((n,) + shapes[k], np.float32) for k in want}
+        if n:
+            _lib.check(call(C.byref(_outputs(**{k: a.ctypes.data for k, a in out.items()}))))
+        return out
+
     def forward(self, windows, outputs: bool = True, poses: bool = False) -> Dict[str, np.ndarray]:
         """-> ``normality_score`` [N]; with ``outputs`` also ``tokens`` and ``reconstructed_tokens`` [N, n_tokens, token_dim] and, for
         the shopformer_2 variant, ``token_scores`` [N, n_tokens]; with ``poses`` (a model loaded with ``decoder=True``) also
         ``gcae_reconstructed`` [N, 2, T, V] = the decoder on ``tokens`` (the same array as ``reconstructed_poses``, shopformer_2's name)
         and ``pose_error`` [N, T, V], the mean over the 2 channels of (reconstruction - window)^2"""
         w = self._check(windows)
-        n = len(w)
-        if poses:
-            return self._forward_poses(w, outputs)
-        score = np.empty(n, np.float32)
-        tok = np.empty((n, self.n_tokens, self.token_dim), np.float32) if outputs else None
-        rec = np.empty((n, self.n_tokens, self.token_dim), np.float32) if outputs else None
-        ts = np.empty((n, self.n_tokens), np.float32) if outputs and self.variant == 2 else None
-        if n and self.variant == 2:
-            o = _outputs(score.ctypes.data, ts.ctypes.data if ts is not None else None, tok.ctypes.data if outputs else None,
-                         rec.ctypes.data if outputs else None)
-            _lib.check(_lib.lib().mi355_shopformer_score_ex(self._h, w.ctypes.data, n, C.byref(o)))
-        elif n:
-            _lib.check(_lib.lib().mi355_shopformer_score(self._h, w.ctypes.data, n, score.ctypes.data,
-                                                         tok.ctypes.data if outputs else None, rec.ctypes.data if outputs else None))
-        out = {"normality_score": score}
-        if outputs:
-            out["tokens"], out["reconstructed_tokens"] = tok, rec
-        if ts is not None:
-            out["token_scores"] = ts
-        return out
-
-    def _forward_poses(self, w: np.ndarray, outputs: bool) -> Dict[str, np.ndarray]:
-        if not self.has_decoder:
+        if poses and not self.has_decoder:
             raise ValueError(NO_DECODER)
-        n, ptr = len(w), lambda a: a.ctypes.data if a is not None else None
-        score = np.empty(n, np.float32)
-        tok = np.empty((n, self.n_tokens, self.token_dim), np.float32) if outputs else None
-        rec = np.empty((n, self.n_tokens, self.token_dim), np.float32) if outputs else None
-        ts = np.empty((n, self.n_tokens), np.float32) if outputs and self.variant == 2 else None
-        pose = np.empty((n, 2, self.seq_len, self.num_keypoints), np.float32)
-        err = np.empty((n, self.seq_len, self.num_keypoints), np.float32)
-        if n:
-            o = _outputs(ptr(score), ptr(ts), ptr(tok), ptr(rec), ptr(pose), ptr(err))
-            _lib.check(_lib.lib().mi355_shopformer_score_ex(self._h, w.ctypes.data, n, C.byref(o)))
-        out = {"normality_score": score}
+        want = ["scores"] + (["tokens", "recon"] + ["token_scores"] * (self.variant == 2) if outputs else []) + (["poses", "pose_error"] if poses else [])
+        a = self._run(want, len(w), lambda o: _lib.lib().mi355_shopformer_score_ex(self._h, w.ctypes.data, len(w), o))
+        out = {"normality_score": a["scores"]}
         if outputs:
-            out["tokens"], out["reconstructed_tokens"] = tok, rec
-        if ts is not None:
-            out["token_scores"] = ts
-        out["gcae_reconstructed"] = out["reconstructed_poses"] = pose
-        out["pose_error"] = err
+            out["tokens"], out["reconstructed_tokens"] = a["tokens"], a["recon"]
+        if "token_scores" in a:
+            out["token_scores"] = a["token_scores"]
+        if poses:
+            out["gcae_reconstructed"] = out["reconstructed_poses"] = a["poses"]
+            out["pose_error"] = a["pose_error"]
         return out
 
     def decode(self, tokens) -> np.ndarray:
@@ -674,11 +655,7 @@ class Shopformer:
         if self.variant != 2:
             raise ValueError("reduction='none' exists only for the shopformer_2 variant: the shopformer/ network has no per-token score")
         w = self._check(windows)
-        ts = np.empty((len(w), self.n_tokens), np.float32)
-        if len(w):
-            o = _outputs(token_scores=ts.ctypes.data)
-            _lib.check(_lib.lib().mi355_shopformer_score_ex(self._h, w.ctypes.data, len(w), C.byref(o)))
-        return ts
+        return self._run(["token_scores"], len(w), lambda o: _lib.lib().mi355_shopformer_score_ex(self._h, w.ctypes.data, len(w), o))["token_scores"]
 
     def predict(self, windows, threshold: float = 0.5) -> np.ndarray:
         return (self.score(windows) > threshold).astype(np.int64)
@@ -694,12 +671,9 @@ class Shopformer:
             raise ValueError("reduction='none' exists only for the shopformer_2 variant: the shopformer/ network has no per-token score")
         p, code = ops.pose_array(poses)
         st = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1)
-        res = np.empty(len(st) if reduction == "mean" else (len(st), self.n_tokens), np.float32)
-        o = _outputs(scores=res.ctypes.data) if reduction == "mean" else _outputs(token_scores=res.ctypes.data)
-        if len(st):
-            _lib.check(_lib.lib().mi355_shopformer_score_poses(self._h, p.ctypes.data, code, p.shape[0], p.shape[1], st.ctypes.data, len(st),
-                                                               int(self.neck), C.byref(o)))
-        return res
+        field = "scores" if reduction == "mean" else "token_scores"
+        return self._run([field], len(st), lambda o: _lib.lib().mi355_shopformer_score_poses(
+            self._h, p.ctypes.data, code, p.shape[0], p.shape[1], st.ctypes.data, len(st), int(self.neck), o))[field]
 
     def score_device_async(self, windows_dev: int, n: int, scores_dev: int, stream: int = 0, tokens_dev: int = 0, recon_dev: int = 0,
                            token_scores_dev: int = 0, poses_dev: int = 0, pose_error_dev: int = 0) -> None:
@@ -710,12 +684,8 @@ class Shopformer:
             raise ValueError(NO_DECODER)
         if token_scores_dev and self.variant != 2:
             raise ValueError("token_scores exist only for the shopformer_2 variant")
-        if token_scores_dev or self.variant == 2 or poses_dev or pose_error_dev:
-            o = _outputs(scores_dev, token_scores_dev, tokens_dev, recon_dev, poses_dev, pose_error_dev)
-            _lib.check(_lib.lib().mi355_shopformer_score_ex_device_async(self._h, windows_dev, int(n), C.byref(o), stream or None))
-            return
-        _lib.check(_lib.lib().mi355_shopformer_score_device_async(self._h, windows_dev, int(n), scores_dev, tokens_dev or None,
-                                                                  recon_dev or None, stream or None))
+        o = _outputs(scores_dev, token_scores_dev, tokens_dev, recon_dev, poses_dev, pose_error_dev)
+        _lib.check(_lib.lib().mi355_shopformer_score_ex_device_async(self._h, windows_dev, int(n), C.byref(o), stream or None))
 
 
 # ---------------------------------------------------------------------------------------------- tracks -> windows -> scores

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import _shopformer_numpy as R
+from _shopformer_c_forms import old_c_forms_equal_forward
 
 pytestmark = pytest.mark.gpu
 CONFIGS = ["default", "kp18_t24", "h32_l4"]
@@ -107,6 +108,7 @@ def test_device_async_entry_point_equals_the_blocking_one(models):
     stream.synchronize()
     assert np.array_equal(sc.cpu().numpy(), want["normality_score"])
     assert np.array_equal(tk.cpu().numpy(), want["tokens"]) and np.array_equal(rc.cpu().numpy(), want["reconstructed_tokens"])
+    old_c_forms_equal_forward(model, x, want, xd, stream)
 
 
 def test_video_to_scores_end_to_end(fix, models, v8n_pose):

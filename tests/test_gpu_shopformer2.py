@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import _shopformer2_numpy as R2
+from _shopformer_c_forms import old_c_forms_equal_forward
 
 pytestmark = pytest.mark.gpu
 CONFIGS = ["paper", "default24", "paper_t24"]
@@ -119,6 +120,7 @@ def test_device_async_entry_point_equals_the_blocking_one(models, name):
     model.score_device_async(xd.data_ptr(), len(x), sc2.data_ptr())              # scores alone: tokens stay in the handle's scratch
     torch.cuda.synchronize()
     assert np.array_equal(sc2.cpu().numpy(), want["normality_score"])
+    old_c_forms_equal_forward(model, x, want, xd, stream)
 
 
 def test_video_to_scores_end_to_end(fix, models, v8n_pose):
