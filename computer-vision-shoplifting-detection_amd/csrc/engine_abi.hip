@@ -41,22 +41,37 @@ int mi355_yolo_info(const mi355_yolo* h, mi355_model_info* info) {
     return MI355_OK;
 }
 
+// the filter arguments every infer entry point takes
+static InferCall filtered(float conf, float iou, const int* classes, int n_classes, int max_det, int imgsz) {
+    InferCall c;
+    c.conf = conf; c.iou = iou; c.classes = classes; c.n_classes = n_classes; c.max_det = max_det; c.imgsz = imgsz;
+    return c;
+}
+
 int mi355_yolo_infer(mi355_yolo* h, const uint8_t* bgr, int n, int height, int width, int row_stride, float conf, float iou,
                      const int* classes, int n_classes, int max_det, int imgsz, mi355_det* out_rows, int cap, int* out_counts) {
-    return infer_impl(h, bgr, false, n, height, width, row_stride, conf, iou, classes, n_classes, max_det, imgsz, out_rows, cap, out_counts);
+    InferCall c = filtered(conf, iou, classes, n_classes, max_det, imgsz);
+    c.src = bgr; c.n = n; c.height = height; c.width = width; c.row_stride = row_stride;
+    c.out_rows = out_rows; c.cap = cap; c.out_counts = out_counts;
+    return infer_impl(h, c);
 }
 
 int mi355_yolo_infer_device(mi355_yolo* h, const uint8_t* bgr_dev, int n, int height, int width, float conf, float iou,
                             const int* classes, int n_classes, int max_det, int imgsz, mi355_det* out_rows, int cap, int* out_counts) {
-    return infer_impl(h, bgr_dev, true, n, height, width, 0, conf, iou, classes, n_classes, max_det, imgsz, out_rows, cap, out_counts);
+    InferCall c = filtered(conf, iou, classes, n_classes, max_det, imgsz);
+    c.src = bgr_dev; c.on_device = true; c.n = n; c.height = height; c.width = width;
+    c.out_rows = out_rows; c.cap = cap; c.out_counts = out_counts;
+    return infer_impl(h, c);
 }
 
 int mi355_yolo_infer_device_async(mi355_yolo* h, const uint8_t* bgr_dev, int n, int height, int width, float conf, float iou,
                                   const int* classes, int n_classes, int max_det, int imgsz, mi355_det* rows_dev, int* counts_dev,
                                   int* total_dev) {
     if (!rows_dev) return fail(MI355_EINVAL, "null argument");
-    return infer_impl(h, bgr_dev, true, n, height, width, 0, conf, iou, classes, n_classes, max_det, imgsz, nullptr, 1, nullptr,
-                      rows_dev, counts_dev, total_dev);
+    InferCall c = filtered(conf, iou, classes, n_classes, max_det, imgsz);
+    c.src = bgr_dev; c.on_device = true; c.n = n; c.height = height; c.width = width;
+    c.dev_rows = rows_dev; c.dev_counts = counts_dev; c.dev_total = total_dev;
+    return infer_impl(h, c);
 }
 
 void* mi355_yolo_stream(mi355_yolo* h) { return h ? (void*)h->stream : nullptr; }
@@ -130,44 +145,10 @@ int mi355_yolo_raw_head(mi355_yolo* h, const uint8_t* bgr, int n, int height, in
                         float* out, int* out_channels, int* out_anchors) {
     if (!h || !out_channels || !out_anchors) return fail(MI355_EINVAL, "null argument");
     if (n <= 0 || height <= 0 || width <= 0) return fail(MI355_EINVAL, "n, height and width must be positive");
-    if (imgsz <= 0) imgsz = 640;
-    if (imgsz % 32) return fail(MI355_EINVAL, "imgsz must be a multiple of 32");
-    const Geometry g = make_geometry(height, width, imgsz);
-    int A = 0;
-    for (const FileLevel& lv : h->levels) A += (g.Hl / lv.stride) * (g.Wl / lv.stride);
-    *out_channels = h->no(); *out_anchors = A;
-    if (!out) return MI355_OK;
-    if (!bgr) return fail(MI355_EINVAL, "null argument");
-    if (row_stride == 0) row_stride = width * 3;
-    HIPCHK(hipSetDevice(h->device));
-    const int nb = std::min(n, h->chunk);
-    int rc = ensure_shape(h, nb, g.Hl, g.Wl); if (rc) return rc;
-    rc = prepare_geometry(h, g, imgsz); if (rc) return rc;
-    const size_t frame_bytes = (size_t)height * width * 3;
-    if (h->d_in_bytes < frame_bytes * n) {
-        if (h->d_in) (void)hipFree(h->d_in);
-        h->d_in = nullptr; h->d_in_bytes = 0;
-        HIPCHK(hipMalloc(&h->d_in, frame_bytes * n)); h->d_in_bytes = frame_bytes * n;
-    }
-    HIPCHK(hipMemcpy2DAsync(h->d_in, (size_t)width * 3, bgr, (size_t)row_stride, (size_t)width * 3, (size_t)height * n,
-                            hipMemcpyHostToDevice, h->stream));
-    const size_t per = (size_t)A * h->no();
-    if (h->rawhead_floats < per * nb) {
-        if (h->d_rawhead) (void)hipFree(h->d_rawhead); h->d_rawhead = nullptr; h->rawhead_floats = 0;
-        HIPCHK(hipMalloc(&h->d_rawhead, per * nb * 4)); h->rawhead_floats = per * nb;
-    }
-    Prof pf{h};
-    const bool was = h->profiling; h->profiling = false;
-    for (int s = 0; s < n; s += nb) {
-        const int m = std::min(nb, n - s);
-        rc = run_chunk(h, pf, h->d_in + (size_t)s * frame_bytes, m, g, true);
-        if (rc) { h->profiling = was; return rc; }
-        KCHK(launch_transpose_pred(h->pred, h->d_rawhead, m, A, h->no(), h->stream));
-        HIPCHK(hipMemcpyAsync(out + (size_t)s * per, h->d_rawhead, per * m * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    h->profiling = was;
-    return MI355_OK;
+    RawHeadCall c;
+    c.bgr = bgr; c.n = n; c.height = height; c.width = width; c.row_stride = row_stride;
+    c.imgsz = imgsz; c.out = out; c.out_channels = out_channels; c.out_anchors = out_anchors;
+    return raw_head_impl(h, c);
 }
 
 // ------------------------------------------------------------------------------------- single operators

@@ -4,6 +4,7 @@
 // BasePredictor.stream_inference (preprocess -> model -> postprocess).
 #pragma once
 #include "common.h"
+#include "dev_buf.h"
 #include "../../include/mi355_yolo.h"
 
 #include <algorithm>
@@ -35,6 +36,20 @@ inline int fail(int code, const std::string& msg) { g_err = msg; return code; }
         const char* m_ = (expr);                                                             \
         if (m_) return fail(MI355_EHIP, std::string("launch failed: ") + m_);                \
     } while (0)
+// one launch inside a profiling span of `kind` (Prof below: two branches on a flag when profiling is off)
+#define TIMED(pf, kind, expr)                                                                \
+    do {                                                                                     \
+        if ((pf).begin(kind)) return fail(MI355_EHIP, "event");                              \
+        KCHK(expr);                                                                          \
+        (pf).end();                                                                          \
+    } while (0)
+// grow-only scratch (dev_buf.h).  grow_or_fail -> 1 when it reallocated: the owner says beside the call what that invalidates
+inline int grow_or_fail(Buf& b, size_t need, const char* name) {
+    const int r = buf_grow(b, need);
+    if (r < 0) fail(MI355_EHIP, std::string("out of device or pinned memory: ") + name);
+    return r;
+}
+#define GROW(buf, need) do { if (grow_or_fail(buf, need, #buf) < 0) return MI355_EHIP; } while (0)
 
 // OP_DWCONV / OP_ATTN (YOLO11, file version 2): FileOp.r0 = groups (== channels) / heads; for OP_ATTN k = key_dim, s = head_dim
 enum { OP_STEM = 0, OP_CONV = 1, OP_UPSAMPLE = 2, OP_SPPF_POOL = 3, OP_DWCONV = 4, OP_ATTN = 5 };
@@ -178,7 +193,6 @@ struct mi355_yolo {
                                                   // batch 8 6,150 vs 6,360): the cross-stream event waits cost more than the overlap buys
     std::vector<hipStream_t> aux;             // streams 1 .. n_streams-1 (0 = `stream`)
     std::vector<hipEvent_t> op_done;          // per op: recorded after its launch when someone on another stream waits for it
-    hipEvent_t ev_fork = nullptr;
     std::vector<int> sched_order, op_stream;  // launch order (depth, index) and stream of each op
     std::vector<std::vector<int>> op_xdeps;   // producers on other streams
     std::vector<char> op_signals;             // op has a consumer on another stream (or is a head output: decode joins on it)
@@ -206,9 +220,9 @@ struct mi355_yolo {
     bool sparse_shape = false; int sparse_why = 1;   // why the current shape keeps the dense head (prepare_sparse_shape), 0 = it does not
     int sparse_min_batch = 32;          // frames per pass from which the sparse branch wins
     float sparse_cap = 1.0f;            // share of a level's positions the lists hold; beyond it the dense launches run
-    ConvLaunch sp_cls[3], sp_box[3], sp_b1l[3]; bool sp_has_cls[3] = {false, false, false};
+    ConvLaunch sp_cls[3], sp_box[3], sp_b1l[3];
     int* sp_state = nullptr;            // device: 12 ints of SparseArgs.state + [12] dense fall-backs so far
-    int* sp_lists = nullptr; size_t sp_lists_ints = 0;
+    Buf sp_lists;                       // int: per level the dilated list, then the candidate list
     int sp_cap[3] = {0, 0, 0}; size_t sp_off_dil[3] = {0, 0, 0}, sp_off_cand[3] = {0, 0, 0};   // list capacities / offsets into sp_lists of the current shape
     float pass_conf = 0.25f; const unsigned* pass_cmask = nullptr;   // the call's candidate filter (infer_impl sets them before its chunks)
     long long sp_passes = 0;
@@ -225,19 +239,23 @@ struct mi355_yolo {
     std::vector<std::pair<int, hipGraphExec_t>> graphs;   // (frames in chunk, captured stem..decode sequence)
     int use_graph = 0;                  // MI355_GRAPH=1: replay stem..decode as a hipGraph (measured: no gain, the small-batch
                                         // regime is bound by per-kernel latency of tiny grids, not by host launches)
-    // per-call scratch (grown on demand)
-    uint8_t* d_in = nullptr; size_t d_in_bytes = 0;
-    mi355_det* d_rows = nullptr; int* d_counts = nullptr; size_t rows_cap = 0; int counts_cap = 0;
-    mi355_det* h_rows = nullptr; int* h_counts = nullptr; size_t h_rows_cap = 0; int h_counts_cap = 0;
-    mi355_det* d_packed = nullptr; int* d_offsets = nullptr; size_t packed_cap = 0; int offsets_cap = 0;   // rows compacted on the GPU before the D2H copy
-    unsigned* d_cmask = nullptr; unsigned* h_cmask = nullptr; int cmask_words = 0;
-    int* d_xtab = nullptr; int* d_ytab = nullptr; int tab_h0 = -1, tab_w0 = -1, tab_imgsz = -1;
-    float* d_rawhead = nullptr; size_t rawhead_floats = 0;
+    // per-call scratch, grow-only (dev_buf.h; h_* = pinned host memory)
+    Buf d_in;                           // staged host frames: two chunk slots (infer), all n frames (raw_head)
+    Buf d_rows, d_counts;               // mi355_det [n][max_det]; int [2n + 3 * chunk]: counts, sort scratch, one chunk's temporary block
+    Buf d_packed, d_offsets;            // rows compacted on the GPU before the D2H copy; int [n + 1]
+    Buf h_rows{true}, h_counts{true};
+    Buf d_cmask, h_cmask{true};         // unsigned [ceil(nc / 32)]
+    Buf d_xtab, d_ytab; int tab_h0 = -1, tab_w0 = -1, tab_imgsz = -1;
+    Buf d_rawhead;                      // float [nb][A][no]
+    mi355_det* rows_dev() const { return (mi355_det*)d_rows.p; }
+    int* counts_dev() const { return (int*)d_counts.p; }
+    mi355_det* rows_host() const { return (mi355_det*)h_rows.p; }
+    int* counts_host() const { return (int*)h_counts.p; }
     // batches of frames of different sizes (engine_multi.hip): pinned staging of host frames (two chunk slots), and ONE device buffer
     // holding the per-frame letterbox descriptors, the per-frame scale-back constants and the resize tables, uploaded from a pinned
     // image of it (h_multi) -- only when that image changed since the last upload (the same cameras call after call)
-    uint8_t* h_stage = nullptr; size_t h_stage_bytes = 0;
-    char* d_multi = nullptr; char* h_multi = nullptr; size_t multi_cap = 0, multi_bytes = 0;
+    Buf h_stage{true};
+    Buf d_multi, h_multi{true}; size_t multi_bytes = 0;   // multi_bytes: what d_multi holds of h_multi's image (0 = nothing)
     unsigned long long plan_hash = 0;   // fingerprint of the candidate lists + the chosen indices of the current shape
     int plan_source = 0, plan_launches = 0;   // 0 static guess (autotune off), 1 memory, 2 this machine's plan cache, 3 tuned now, 4 shipped plan file; launches of one pass (stem..last conv)
     bool async_pending = false;         // mi355_yolo_infer_device_async work may still be in flight on `stream`
@@ -293,12 +311,6 @@ int ensure_shape(mi355_yolo* h, int nb, int Hl, int Wl);
 int launch_net(mi355_yolo* h, Prof& pf, const uint8_t* stem_in, int nb, const Geometry& g, bool full_pred);
 int run_chunk(mi355_yolo* h, Prof& pf, const uint8_t* frames_dev, int nb, const Geometry& g, bool full_pred);
 int prepare_geometry(mi355_yolo* h, const Geometry& g, int imgsz);
-struct MultiFrames;
-int infer_impl(mi355_yolo* h, const uint8_t* src, bool src_on_device, int n, int height, int width, int row_stride,
-               float conf, float iou, const int* classes, int n_classes, int max_det, int imgsz,
-               mi355_det* out_rows, int cap, int* out_counts, mi355_det* dev_rows = nullptr, int* dev_counts = nullptr,
-               int* dev_total = nullptr, const MultiFrames* mf = nullptr);
-
 // engine_multi.hip: one call over frames of different sizes (mi355_yolo_infer_multi).  All frames the same shape: the rect
 // geometry of make_geometry (what mi355_yolo_infer does with them stacked); otherwise every frame is letterboxed into the square
 // imgsz x imgsz canvas (auto_pad = false) -- Ultralytics' BasePredictor.pre_transform rule.
@@ -313,10 +325,34 @@ struct MultiCall {
     size_t slot_bytes = 0;                    // host frames: bytes of the largest chunk
     const LetterboxFrame* d_desc = nullptr; const float* d_geom = nullptr; const int* d_tabs = nullptr;
 };
+// the host image of a call's per-frame data: [descriptors | scale-back rows [n][7] | resize tables], each part 256-byte aligned
+struct MultiImage {
+    std::vector<char> bytes; size_t geom_off = 0, tabs_off = 0, tab_ints = 0;
+};
 int multi_check(const MultiFrames& mf, int n);
 void multi_prepare(const MultiFrames& mf, int n, int nb, int imgsz, MultiCall& mc);
+void multi_image(const MultiFrames& mf, const MultiCall& mc, int n, int nb, const uint8_t* staged, MultiImage& img);
 int multi_upload(mi355_yolo* h, const MultiFrames& mf, int n, int nb, MultiCall& mc);
-int multi_stage_chunk(mi355_yolo* h, const MultiFrames& mf, const MultiCall& mc, int s0, int m, int nb, int slot);
+int multi_stage_chunk(mi355_yolo* h, const MultiFrames& mf, const MultiCall& mc, int s0, int m, int slot);
 int run_chunk_multi(mi355_yolo* h, Prof& pf, const MultiCall& mc, int s0, int m, bool full_pred);
+
+// engine_run.hip: one infer call.  An entry point fills what it uses: the frames (one dense block of one shape, or `multi`), the
+// filter, and one of the two output forms.
+struct InferCall {
+    const uint8_t* src = nullptr; bool on_device = false;
+    int n = 0, height = 0, width = 0, row_stride = 0;         // row_stride 0 = width * 3; host frames only
+    const MultiFrames* multi = nullptr;                       // frames of different sizes: src, on_device and the sizes above are not read
+    float conf = 0.25f, iou = 0.7f; const int* classes = nullptr; int n_classes = 0, max_det = 0, imgsz = 0;
+    mi355_det* out_rows = nullptr; int cap = 1; int* out_counts = nullptr;                        // host rows [n][cap] and counts
+    mi355_det* dev_rows = nullptr; int* dev_counts = nullptr; int* dev_total = nullptr;          // or: packed device rows, asynchronous
+};
+int infer_impl(mi355_yolo* h, const InferCall& call);
+// ... and one raw_head call: n frames of one shape on the host (bgr), or `multi`; out = NULL asks for the shape only
+struct RawHeadCall {
+    const uint8_t* bgr = nullptr; int n = 0, height = 0, width = 0, row_stride = 0;
+    const MultiFrames* multi = nullptr;
+    int imgsz = 0; float* out = nullptr; int* out_channels = nullptr; int* out_anchors = nullptr;
+};
+int raw_head_impl(mi355_yolo* h, const RawHeadCall& call);
 
 }  // namespace mi355

@@ -27,22 +27,14 @@ mi355_yolo::~mi355_yolo() {
     for (auto& c : dconv) { if (c.wpk) (void)hipFree(c.wpk); if (c.bias) (void)hipFree(c.bias); if (c.w_raw) (void)hipFree(c.w_raw); if (c.w_frag) (void)hipFree(c.w_frag); }
     if (lut) (void)hipFree(lut);
     if (zeros) (void)hipFree(zeros);
-    if (sp_state) (void)hipFree(sp_state); if (sp_lists) (void)hipFree(sp_lists); if (h_sp) (void)hipHostFree(h_sp);
-    if (d_in) (void)hipFree(d_in);
-    if (d_rows) (void)hipFree(d_rows); if (d_counts) (void)hipFree(d_counts);
-    if (d_packed) (void)hipFree(d_packed); if (d_offsets) (void)hipFree(d_offsets);
-    if (h_rows) (void)hipHostFree(h_rows); if (h_counts) (void)hipHostFree(h_counts);
-    if (d_cmask) (void)hipFree(d_cmask); if (h_cmask) (void)hipHostFree(h_cmask);
-    if (d_xtab) (void)hipFree(d_xtab); if (d_ytab) (void)hipFree(d_ytab);
-    if (d_rawhead) (void)hipFree(d_rawhead);
-    if (h_stage) (void)hipHostFree(h_stage);
-    if (d_multi) (void)hipFree(d_multi); if (h_multi) (void)hipHostFree(h_multi);
+    if (sp_state) (void)hipFree(sp_state); if (h_sp) (void)hipHostFree(h_sp);
+    for (Buf* b : {&sp_lists, &d_in, &d_rows, &d_counts, &d_packed, &d_offsets, &h_rows, &h_counts, &d_cmask, &h_cmask, &d_xtab, &d_ytab,
+                   &d_rawhead, &h_stage, &d_multi, &h_multi}) buf_free(*b);
     if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1);
     for (auto e : pev) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) { if (ev_copied[i]) (void)hipEventDestroy(ev_copied[i]); if (ev_consumed[i]) (void)hipEventDestroy(ev_consumed[i]); }
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
     for (auto e : op_done) if (e) (void)hipEventDestroy(e);
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
     for (auto st : aux) if (st) (void)hipStreamDestroy(st);
     if (stream) (void)hipStreamDestroy(stream);
 }
@@ -327,7 +319,6 @@ static int build_schedule(mi355_yolo* h) {
     if (h->host_only) return MI355_OK;
     for (int i = 0; i < n; ++i)
         if (h->op_signals[i]) HIPCHK(hipEventCreateWithFlags(&h->op_done[i], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     h->aux.assign(std::max(0, h->n_streams - 1), nullptr);
     for (auto& st : h->aux) HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     return MI355_OK;
