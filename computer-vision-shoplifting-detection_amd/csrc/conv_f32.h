@@ -142,6 +142,39 @@ __device__ __forceinline__ void store_tile(f32x4 v, const float* bias, int act, 
     }
 }
 
+// Halo staging of the LDS-staged kernels (conv_igemm_f32, conv_splitk_f32): the block's input tile (with halo), channels [c0, c0 + ck),
+// zero-filled outside the image / beyond Cin, as 16-byte slots (pixel, channel quad) dealt to the 256 threads.  Loads are issued in batches
+// of 8 per thread BEFORE any of them is consumed (out-of-image / beyond-Cin slots read a zero page instead of branching), so one HBM/L2
+// latency is paid per batch, not per float4.  The last batch is a whole one too: taking the remainder as 4- / 2- / 1-deep pieces was tried
+// and showed no gain on the kernel trace.
+template <class KA>
+__device__ __forceinline__ void stage_halo(const KA& a, float* lds, const float* srcb, int tid, int c0, int iy0, int ix0, bool no_src = false) {
+    const int ck4m = (a.ck >> 2) - 1;
+    const int total_f4 = a.npix_in << a.ck4_shift;
+    for (int base = 0; base < total_f4; base += 8 * 256) {
+        f32x4 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int idx = base + u * 256 + tid;
+            const int pix = idx >> a.ck4_shift, q = idx & ck4m;
+            const int iy = (int)(((float)pix + 0.5f) * a.inv_TWin);
+            const int ix = pix - iy * a.TWin;
+            const int gy = iy0 + iy, gx = ix0 + ix, c = c0 + 4 * q;
+            const bool inb = idx < total_f4 && (unsigned)gy < (unsigned)a.Hin && (unsigned)gx < (unsigned)a.Win && c < a.cin4 && !no_src;
+            const float* g = inb ? srcb + ((size_t)gy * a.Win + gx) * a.src_cs + c : a.zeros;
+            v[u] = *(const f32x4*)g;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int idx = base + u * 256 + tid;
+            if (idx < total_f4) {
+                const int pix = idx >> a.ck4_shift, q = idx & ck4m;
+                *(f32x4*)(lds + pix * a.ldp + 4 * q) = v[u];
+            }
+        }
+    }
+}
+
 // F2 = a pointwise conv fused behind this one (Conv3x3 -> SiLU -> Conv1x1 whose only reader is that 1x1: the stride-2
 // convs in front of every C2f, and the last two convs of every head branch): the block keeps its PT*WP*16 output pixels x ALL
 // of the first conv's channels in LDS ([pixel][channel], exactly the image a 1x1 kernel would have staged from HBM), and
@@ -156,6 +189,20 @@ __device__ __forceinline__ void store_tile(f32x4 v, const float* bias, int act, 
 #ifndef MI355_V1_MINWAVES
 #define MI355_V1_MINWAVES 4      // min waves per SIMD asked of the register allocator for the PT*CT == 4 instances (A/B with
                                  // tools/ab_build.sh: 1 -> 4 costs a 12-byte spill outside the loop, buys 2-3 % on the stride-2 layers, 0-1 % elsewhere)
+#endif
+// Five pixel tiles per wave (P = 80 / 160 / 320 pixels per block: the 20x20 and 40x40 maps tile exactly), CT 1 / 2 / 3
+// Registers as compiled (hipcc -S, gfx950; 512 per SIMD lane): PT*CT == 5 takes the 128 of four waves per SIMD without scratch; its fused
+// form spilled 8-16 registers at that limit, is therefore built for three waves (a budget of 168) and takes 145.  PT*CT == 10 takes 212 (fused
+// 197-199): two waves.  PT*CT == 15 takes 280 (fused 264), 60 of them accumulation registers that hold the block partials: one wave, as the
+// 3 x 5 tile (MI355_V1_MINWAVES16).  No instance uses scratch and none moves an accumulator inside the K loop.
+#ifndef MI355_V1_MINWAVES5
+#define MI355_V1_MINWAVES5 4
+#endif
+#ifndef MI355_V1_MINWAVES5F
+#define MI355_V1_MINWAVES5F 3
+#endif
+#ifndef MI355_V1_MINWAVES10
+#define MI355_V1_MINWAVES10 2
 #endif
 template <int KS, int STRIDE, int PT, int CT, int WP, bool F2 = false, class KA = ConvKArgs>
 __device__ __forceinline__ void conv_igemm_f32_body(const KA& a_in, float* lds, const BlockId& bid) {
@@ -198,8 +245,6 @@ __device__ __forceinline__ void conv_igemm_f32_body(const KA& a_in, float* lds, 
         xoff[pt] = __mul24(__mul24(ly * STRIDE, a.TWin) + lx * STRIDE, a.ldp) + (lane >> 4) * 4;
     }
     const float* srcb = a.src + (size_t)b * (size_t)a.img_src;
-    const int ck4m = (a.ck >> 2) - 1;
-    const int total_f4 = a.npix_in << a.ck4_shift;
     const int wstep = a.cib * 256;
     int xt[TAPS], wt[TAPS];
 #pragma unroll
@@ -235,31 +280,7 @@ __device__ __forceinline__ void conv_igemm_f32_body(const KA& a_in, float* lds, 
         for (int c0 = 0; c0 < a.Cin; c0 += a.ck) {
             if (cg == 0) {
                 if (c0) __syncthreads();
-                // ---- stage the halo tile, channels [c0, c0+ck), zero-filled outside the image / beyond Cin ----
-                // Loads are issued in batches of 8 per thread BEFORE any of them is consumed (out-of-image / beyond-Cin slots
-                // read a zero page instead of branching), so one HBM/L2 latency is paid per batch, not per float4.
-                for (int base = 0; base < total_f4; base += 8 * 256) {
-                    f32x4 v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int idx = base + u * 256 + tid;
-                        const int pix = idx >> a.ck4_shift, q = idx & ck4m;
-                        const int iy = (int)(((float)pix + 0.5f) * a.inv_TWin);
-                        const int ix = pix - iy * a.TWin;
-                        const int gy = iy0 + iy, gx = ix0 + ix, c = c0 + 4 * q;
-                        const bool inb = idx < total_f4 && (unsigned)gy < (unsigned)a.Hin && (unsigned)gx < (unsigned)a.Win && c < a.cin4 && !(diag & 1);
-                        const float* g = inb ? srcb + ((size_t)gy * a.Win + gx) * a.src_cs + c : a.zeros;
-                        v[u] = *(const f32x4*)g;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int idx = base + u * 256 + tid;
-                        if (idx < total_f4) {
-                            const int pix = idx >> a.ck4_shift, q = idx & ck4m;
-                            *(f32x4*)(lds + pix * a.ldp + 4 * q) = v[u];
-                        }
-                    }
-                }
+                stage_halo(a, lds, srcb, tid, c0, iy0, ix0, (diag & 1) != 0);     // channels [c0, c0 + ck) of the halo tile
                 __syncthreads();
             }
             const int rem = a.Cin - c0;
@@ -493,7 +514,8 @@ __device__ __forceinline__ void conv_igemm_f32_body(const KA& a_in, float* lds, 
 }
 
 template <int KS, int STRIDE, int PT, int CT, int WP, bool F2 = false>
-__global__ __launch_bounds__(256, (PT * CT == 4 ? MI355_V1_MINWAVES : PT * CT == 8 ? MI355_V1_MINWAVES8 : PT * CT >= 15 ? MI355_V1_MINWAVES16 : 1)) void conv_igemm_f32(ConvKArgs a) {
+__global__ __launch_bounds__(256, (PT * CT == 4 ? MI355_V1_MINWAVES : PT * CT == 5 ? (F2 ? MI355_V1_MINWAVES5F : MI355_V1_MINWAVES5) : PT * CT == 8 ? MI355_V1_MINWAVES8 :
+                                   PT * CT == 10 ? MI355_V1_MINWAVES10 : PT * CT >= 15 ? MI355_V1_MINWAVES16 : 1)) void conv_igemm_f32(ConvKArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (a.gate && *a.gate == 0) return;                  // block-uniform: one scalar load and a branch
     conv_igemm_f32_body<KS, STRIDE, PT, CT, WP, F2>(a, lds, MI355_BLOCK_ID());
@@ -538,8 +560,6 @@ __device__ __forceinline__ void conv_splitk_f32_body(const KA& a, float* lds, co
         const int ctile = (ct0 + ct) < a.n_ctiles ? (ct0 + ct) : (a.n_ctiles - 1);
         wbase[ct] = a.wpk + (size_t)ctile * TAPS * a.cib * 256 + lane * 4;
     }
-    const int ck4m = (a.ck >> 2) - 1;
-    const int total_f4 = a.npix_in << a.ck4_shift;
     const int wstep = a.cib * 256;
     int xt[TAPS], wt[TAPS];
 #pragma unroll
@@ -547,28 +567,7 @@ __device__ __forceinline__ void conv_splitk_f32_body(const KA& a, float* lds, co
 
     for (int c0 = 0; c0 < a.Cin; c0 += a.ck) {
         if (c0) __syncthreads();
-        for (int base = 0; base < total_f4; base += 8 * 256) {  // stage the halo tile of this chunk (as in conv_igemm_f32)
-            f32x4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int idx = base + u * 256 + tid;
-                const int pix = idx >> a.ck4_shift, q = idx & ck4m;
-                const int iy = (int)(((float)pix + 0.5f) * a.inv_TWin);
-                const int ix = pix - iy * a.TWin;
-                const int gy = iy0 + iy, gx = ix0 + ix, c = c0 + 4 * q;
-                const bool inb = idx < total_f4 && (unsigned)gy < (unsigned)a.Hin && (unsigned)gx < (unsigned)a.Win && c < a.cin4;
-                const float* g = inb ? srcb + ((size_t)gy * a.Win + gx) * a.src_cs + c : a.zeros;
-                v[u] = *(const f32x4*)g;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int idx = base + u * 256 + tid;
-                if (idx < total_f4) {
-                    const int pix = idx >> a.ck4_shift, q = idx & ck4m;
-                    *(f32x4*)(lds + pix * a.ldp + 4 * q) = v[u];
-                }
-            }
-        }
+        stage_halo(a, lds, srcb, tid, c0, iy0, ix0);           // the halo tile of this chunk (as in conv_igemm_f32)
         __syncthreads();
         const int rem = a.Cin - c0;
         const int nkk = ((rem < a.ck ? rem : a.ck) + 15) >> 4;

@@ -9,6 +9,7 @@ typedef void (*KernelFn)(ConvKArgs);
 
 // conv_igemm_f32<KS, STRIDE, PT, CT, WP>: PT 0 = the default wave tile (4 pixel tiles, 3 with CT 5), CT in 1..5;
 // PT 1 / 2 = small wave tiles for latency-bound launches, CT in {1, 2}; WP in {1, 2, 4}
+// PT 5 (3x3 only, plain and fused) = five pixel tiles per wave, CT in {1, 2, 3}: blocks of WP * 80 pixels, which tile 20x20 and 40x40 maps exactly
 KernelFn pick_f32_k3s1(int CT, int WP, int PT);       // conv_f32_k3s1.hip
 KernelFn pick_f32_k3s2(int CT, int WP, int PT);       // conv_f32_k3s2.hip
 KernelFn pick_f32_k1(int CT, int WP, int PT);         // conv_f32_k1.hip

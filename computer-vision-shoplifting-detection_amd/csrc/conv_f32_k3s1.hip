@@ -18,6 +18,9 @@ KernelFn pick_f32_k3s1(int CT, int WP, int PT) {
 #define MI355_CASE(pt, ct, wp) if (PT == pt && CT == ct && WP == wp) return &conv_igemm_f32<3, 1, pt, ct, wp>;
     MI355_CASE(1, 1, 4) MI355_CASE(1, 2, 4) MI355_CASE(1, 1, 2) MI355_CASE(1, 2, 2) MI355_CASE(1, 1, 1) MI355_CASE(1, 2, 1)
     MI355_CASE(2, 1, 4) MI355_CASE(2, 2, 4) MI355_CASE(2, 1, 2) MI355_CASE(2, 2, 2) MI355_CASE(2, 1, 1) MI355_CASE(2, 2, 1)
+    // five pixel tiles per wave (blocks of 80 / 160 / 320 pixels): the 20x20 and 40x40 maps of a 640x640 frame tile exactly
+    MI355_CASE(5, 1, 4) MI355_CASE(5, 2, 4) MI355_CASE(5, 3, 4) MI355_CASE(5, 1, 2) MI355_CASE(5, 2, 2) MI355_CASE(5, 3, 2)
+    MI355_CASE(5, 1, 1) MI355_CASE(5, 2, 1) MI355_CASE(5, 3, 1)
 #undef MI355_CASE
     return nullptr;
 }

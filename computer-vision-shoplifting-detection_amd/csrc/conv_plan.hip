@@ -31,7 +31,7 @@ void pack_conv_weights(const float* w, int cout, int cin, int k, float* out) {
 namespace {
 
 struct Plan { int CT, WP, TW, TH, ck; size_t lds; double cost; int version; int buf_floats; int PT; int G = 1; bool f2 = false; };
-// PT 0 = default (4, or 3 with CT 5); G = groups of CT cout tiles a wave walks over one staged input; f2 = fused pointwise stage
+// PT 0 = default (4, or 3 with CT 5), 5 = five pixel tiles (CT <= 3); G = groups of CT cout tiles a wave walks over one staged input; f2 = fused pointwise stage
 
 KernelFn pick_kernel(int ks, int stride, int CT, int WP, int PT) {
     if (ks == 1 && stride == 1) return pick_f32_k1(CT, WP, PT);
@@ -88,7 +88,7 @@ std::vector<Plan> enumerate_plans(int H, int W, int images, int n_ctiles, int ci
     const bool latency_bound = !half && small_pt && (latency_factor(sh, blocks_default, 4, 1) > 1.0 || blocks_default < 1536);
     // Pixel tiles per wave.  fp16: wave tiles of 8 pixel tiles (128 pixels x CT*16 couts) halve the weight bytes fetched per
     // MFMA -- the f16 MFMA retires a 1-KiB fragment pair in 16 cycles, so those kernels are bound by L1/L2 fragment traffic.
-    // fp32: 0 = the default (4, or 3 with CT 5); 2 and 1 for latency-bound launches.
+    // fp32: 0 = the default (4, or 3 with CT 5); 2 and 1 for latency-bound launches; 5 for maps only blocks of 80 pixels tile exactly.
     std::vector<int> pt_sel = {0};
     static const int small_k_pt2 = env_int("MI355_SMALLK_PT2", 1);
     // fp16, thin launches (the default wave tile makes fewer than ~1.5 waves per SIMD: config 5 at its stated 2 frames per GPU): also
@@ -99,19 +99,35 @@ std::vector<Plan> enumerate_plans(int H, int W, int images, int n_ctiles, int ci
     else if (latency_bound) { pt_sel.push_back(2); pt_sel.push_back(1); }
     else if (small_k_pt2 && ks == 3 && cin16 * ks * ks <= 288) pt_sel.push_back(2);   // short K loops: staging + epilogue weigh as much
                                                                                      // as the MFMAs, so more (narrower) waves per SIMD pay
+    // fp32 3x3, throughput regime: FIVE pixel tiles per wave (blocks of WP * 80 pixels) for the maps the default wave tile cannot cover
+    // without computing pixels that do not exist -- 20x20 as five 20x4 tiles, 40x40 as ten 40x4 or five 40x8 tiles.
+    // Offered per wave arrangement WP, and only where the default tile of WP * 64 pixels has no exact tiling of this map while WP * 80
+    // has one: maps that tile exactly today (80x80, 160x160) and every latency-bound launch keep their candidate lists unchanged.
+    static const int use_pt5 = env_int("MI355_PT5", 1);
+    auto tiles_exactly = [&](int P) {
+        for (int TW = 1; TW <= P && TW <= W; ++TW) {
+            const int TH = std::min(P / TW, H);
+            if (TH >= 1 && (long)((W + TW - 1) / TW) * ((H + TH - 1) / TH) * P == (long)W * H) return true;
+        }
+        return false;
+    };
+    if (use_pt5 && !half && ks == 3 && !latency_bound) pt_sel.push_back(5);
     for (int PTsel : pt_sel)
     for (int WC = 1; WC <= 4; WC *= 2)
         for (int CT = 1; CT <= 5; ++CT) {
             if (CT > max_ct || WC < min_wc) continue;
             if (PTsel == 8 && CT > 4) continue;
-            if (PTsel != 0 && PTsel != 8 && CT > 2) continue;          // small wave tiles exist for CT 1 and 2
+            if (PTsel != 0 && PTsel != 8 && PTsel != 5 && CT > 2) continue;          // small wave tiles exist for CT 1 and 2
             const int WP = 4 / WC, PT = PTsel ? PTsel : (CT == 5 ? 3 : 4), P = WP * PT * 16;
+            if (PTsel == 5 && (CT > 3 || tiles_exactly(WP * 64) || !tiles_exactly(P))) continue;
             // cout groups: G = 1 (one group; more cout tiles = more blocks along grid.y, each staging the input again) or, when
             // all of Cin is staged at once, G = as many groups as cover every cout tile from ONE staged input (fp32 kernels)
             const int g_full = (n_ctiles + CT * WC - 1) / (CT * WC);
             for (int G : (half || g_full < 2 || g_full > 8) ? std::vector<int>{1} : std::vector<int>{1, g_full}) {
             const int cover = CT * WC * G, nblk = (n_ctiles + cover - 1) / cover;
-            if (cover >= 2 * n_ctiles && cover > CT) continue;          // more than half of the cout tiles would be padding
+            // more than half of the cout tiles would be padding (five pixel tiles: a 20x20 map is tiled exactly by the block of 80 alone, which
+            // puts all four waves along the couts -- offered up to four times the cout tiles there are, `infl` prices the idle waves)
+            if (cover >= 2 * n_ctiles && cover > CT && !(PTsel == 5 && cover <= 4 * n_ctiles)) continue;
             if (f2_cin16 && nblk != 1) continue;                        // a fused pointwise stage needs ALL first-conv channels in the block
             const double waste_c = (double)nblk * cover / n_ctiles;
             // staged channels per chunk, in 4-byte units; the fp16 kernels (2 channels per unit) also get 128: their K loop
@@ -124,6 +140,7 @@ std::vector<Plan> enumerate_plans(int H, int W, int images, int n_ctiles, int ci
                     int TH = P / TW; if (TH > H) TH = H;
                     if (TH < 1) continue;
                     const long tiles = (long)((W + TW - 1) / TW) * ((H + TH - 1) / TH);
+                    if (PTsel == 5 && tiles * P != (long)W * H) continue;     // five pixel tiles: exact covers only (where one fits in LDS)
                     const int THin = (TH - 1) * stride + ks, TWin = (TW - 1) * stride + ks;
                     const int stage_floats = round_up(THin * TWin * (ck + lds_pad()), 4);
                     // fused pointwise stage: the first conv's output image [P pixels][f2_cin16 + 4] lives behind the halo tile
@@ -137,7 +154,8 @@ std::vector<Plan> enumerate_plans(int H, int W, int images, int n_ctiles, int ci
                     double cost = infl * (1.0 + 0.03 * halo * nblk) * (1.0 + 0.04 * (stages - 1)) * (1.0 + 0.04 * (CT - 1))
                                   + (lds > LDS_SOFT ? 0.15 : 0.0);
                     if (latency_bound) cost *= latency_factor(sh, tiles * images * nblk, PT, CT * G);
-                    if (cost < best.cost) { best = Plan{CT, WP, TW, TH, ck, lds, cost, 1, f2_cin16 ? stage_floats : 0, PTsel}; best.G = G; best.f2 = f2_cin16 != 0; }
+                    // (five pixel tiles: of two exact tiles of equal cost, 4x20 and 20x4, the one with the longer rows)
+                    if (cost < best.cost || (PTsel == 5 && cost == best.cost)) { best = Plan{CT, WP, TW, TH, ck, lds, cost, 1, f2_cin16 ? stage_floats : 0, PTsel}; best.G = G; best.f2 = f2_cin16 != 0; }
                 }
                 if (best.cost < 1e30) out.push_back(best);
                 // fused pointwise stage, one cout group: the first conv's output image may take the halo tile's place in LDS (the tile is

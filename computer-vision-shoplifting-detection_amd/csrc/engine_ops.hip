@@ -650,9 +650,9 @@ int mi355_bench_conv2d_f16(int device_id, int n, int h, int w, int cin, int cout
 
 // Host-only view of the launch planner (no kernel is launched, no device memory is touched): which kernel versions would be
 // offered for a conv of this shape and these buffer strides.  Used by the CPU tests of the planner's guards.
-int mi355_plan_query(int n, int h, int w, int cin, int cout, int k, int stride, int src_cs, int dst_cs, int res_cs, int f2_cout,
-                     int f2_dst_cs, int half, int* versions, int cap, int* n_plans) {
-    if (!n_plans || n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || cap < 0 || (cap > 0 && !versions)) return fail(MI355_EINVAL, "bad argument");
+static int plan_query_impl(int n, int h, int w, int cin, int cout, int k, int stride, int src_cs, int dst_cs, int res_cs, int f2_cout, int f2_dst_cs,
+                           int half, int* out, int cap, int* n_plans, bool tiles) {
+    if (!n_plans || n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || cap < 0 || (cap > 0 && !out)) return fail(MI355_EINVAL, "bad argument");
     if (stride != 1 && stride != 2) return fail(MI355_EINVAL, "stride must be 1 or 2");
     float* fake = (float*)(uintptr_t)0x10000;                    // aligned, never dereferenced
     ConvArgs a{};
@@ -664,8 +664,25 @@ int mi355_plan_query(int n, int h, int w, int cin, int cout, int k, int stride, 
     std::vector<ConvLaunch> cands;
     if (const char* e = plan_conv_candidates(a, &cands)) { *n_plans = 0; return fail(MI355_EINVAL, e); }
     *n_plans = (int)cands.size();
-    for (int i = 0; i < (int)cands.size() && i < cap; ++i) versions[i] = cands[i].version + (cands[i].a.w2 ? 100 : 0);
+    for (int i = 0; i < (int)cands.size() && i < cap; ++i) {
+        const ConvLaunch& l = cands[i];
+        const int version = l.version + (l.a.w2 ? 100 : 0);
+        if (!tiles) { out[i] = version; continue; }
+        const int f[MI355_PLAN_TILE_FIELDS] = {version, l.PT, l.CT, l.WP, l.a.TW, l.a.TH, l.a.cgroups, (int)l.grid_x, (int)l.grid_y};
+        std::copy(f, f + MI355_PLAN_TILE_FIELDS, out + (size_t)i * MI355_PLAN_TILE_FIELDS);
+    }
     return MI355_OK;
+}
+
+int mi355_plan_query(int n, int h, int w, int cin, int cout, int k, int stride, int src_cs, int dst_cs, int res_cs, int f2_cout,
+                     int f2_dst_cs, int half, int* versions, int cap, int* n_plans) {
+    return plan_query_impl(n, h, w, cin, cout, k, stride, src_cs, dst_cs, res_cs, f2_cout, f2_dst_cs, half, versions, cap, n_plans, false);
+}
+
+// ... and every candidate's wave tile, output tile and grid (which tile a conv of this shape can run with: tests, tools/plan_tiles.py)
+int mi355_plan_query_tiles(int n, int h, int w, int cin, int cout, int k, int stride, int src_cs, int dst_cs, int res_cs, int f2_cout,
+                           int f2_dst_cs, int half, int* tiles, int cap, int* n_plans) {
+    return plan_query_impl(n, h, w, cin, cout, k, stride, src_cs, dst_cs, res_cs, f2_cout, f2_dst_cs, half, tiles, cap, n_plans, true);
 }
 
 static int op_stem_impl(int device_id, const uint8_t* bgr, int n, int h, int w, const float* w_oihw, const float* bias, int cout,

@@ -9,7 +9,7 @@ namespace mi355 {
 // process) need not repeat it.  The autotuner's CHOICES -- an index into each conv's candidate list -- are kept in a small
 // text file keyed by (model image hash, precision, frames, H, W, planner version); a file whose candidate counts do not
 // match the running planner is ignored.  MI355_PLAN_CACHE=<dir> moves the directory, MI355_PLAN_CACHE=0 turns it off.
-static const char* kPlanVersion = "mi355-plans-r03a";
+static const char* kPlanVersion = "mi355-plans-r06a";
 
 // What a persisted choice (an INDEX into a candidate list) means depends on the lists themselves: the planner build, its env
 // knobs, the GPU.  The file therefore carries a fingerprint of every candidate's launch geometry plus the device's arch name
@@ -608,13 +608,22 @@ int ensure_shape(mi355_yolo* h, int nb, int Hl, int Wl) {
         for (size_t i = 0; i < h->ops.size(); ++i) h->plan_launches += launched((int)i) && !(h->sparse_shape && h->sp_skip[i]);
     }
     // the sparse tail's conv launches (plan_launches counts stem .. last conv): 2 gated dense convs per level, stages A and B
-    if (h->sparse_shape) h->plan_launches += 2 + 2 * h->sp_levels;
+    // (the gated pairs are enqueued only when a list is shorter than the chunk's positions: launch_sparse_tail)
+    const bool can_overflow = h->sparse_shape && sparse_lists_can_overflow(h, nb);
+    if (h->sparse_shape) h->plan_launches += 2 + (can_overflow ? 2 * h->sp_levels : 0);
     if (getenv("MI355_SCHED_LOG")) {      // launch order of a pass for tools/layer_report.py: position, op index, stream, launched
         for (size_t pos = 0; pos < h->sched_order.size(); ++pos) {
             const int idx = h->sched_order[pos];
             fprintf(stderr, "[sched] %zu %d %d %d\n", pos, idx, h->op_stream[idx], !(h->ops[idx].type == OP_UPSAMPLE && h->fused_away[idx]) && !h->skip_op[idx] && !(h->sparse_shape && h->sp_skip[idx]));
         }
-        fprintf(stderr, "[sparse] %d %d\n", h->sparse_shape ? 1 : 0, h->sp_levels);
+        // the chosen launch of every conv for tools/plan_tiles.py: wave tile, output tile, grid and the map the grid walks
+        for (size_t i = 0; i < h->ops.size(); ++i) {
+            if (h->ops[i].type != OP_CONV || h->skip_op[i]) continue;
+            const ConvLaunch& l = h->plans[i];
+            fprintf(stderr, "[tile] %s v%d PT%d CT%d WP%d tile %dx%d G%d grid %ux%u map %dx%d x%d%s\n", h->convs[h->ops[i].conv].name, l.version, l.PT, l.CT, l.WP,
+                    l.a.TW, l.a.TH, l.a.cgroups, l.grid_x, l.grid_y, l.a.Wout, l.a.Hout, l.a.Hout > 1 ? nb : 1, l.a.w2 ? " +1x1" : "");
+        }
+        fprintf(stderr, "[sparse] %d %d %d\n", h->sparse_shape ? 1 : 0, h->sp_levels, can_overflow ? 1 : 0);    // third field: gated dense launches enqueued
     }
     return MI355_OK;
 }

@@ -71,6 +71,16 @@ static int sparse_list_cap(const mi355_yolo* h, long long pos) {
     return (int)std::min<long long>(pos, std::max<long long>(64, (long long)std::ceil((double)h->sparse_cap * (double)pos)));
 }
 
+// A position enters each list at most once per pass, so a list that holds every position of the chunk cannot overflow: the gated dense
+// fall-back is then not enqueued at all (launch_sparse_tail), and is not counted among the pass's launches (ensure_shape).
+bool sparse_lists_can_overflow(const mi355_yolo* h, int nb) {
+    for (int l = 0; l < h->sp_levels; ++l) {
+        const long long pos = (long long)nb * (h->cur_H / h->levels[l].stride) * (h->cur_W / h->levels[l].stride);
+        if (std::min(h->sp_cap[l], sparse_list_cap(h, pos)) < pos) return true;      // (a tail chunk uses the head of the full chunk's lists)
+    }
+    return false;
+}
+
 int prepare_sparse_shape(mi355_yolo* h, int nb, int Hl, int Wl) {
     h->sparse_shape = false;
     // sparse_why (plan_info): 0 runs, 1 the program has no such head / half / switched off, 2 below the frames-per-pass threshold
@@ -244,6 +254,7 @@ static int launch_op(const Pass& p, size_t i, hipStream_t st) {
 // Everything is enqueued; which of the two forms does the work is decided on the device (SparseArgs.state[8]).
 static int launch_sparse_tail(mi355_yolo* h, Prof& pf, int nb, DecodeArgs& d) {
     SparseArgs sa{};
+    const bool can_overflow = sparse_lists_can_overflow(h, nb);
     sa.n_levels = h->sp_levels; sa.B = nb; sa.A = h->A; sa.no = h->no(); sa.pred = h->pred; sa.best = h->best;
     sa.conf = h->pass_conf; sa.class_mask = h->pass_cmask; sa.state = h->sp_state;
     int* lists = (int*)h->sp_lists.p;
@@ -266,12 +277,16 @@ static int launch_sparse_tail(mi355_yolo* h, Prof& pf, int nb, DecodeArgs& d) {
     HIPCHK(hipMemsetAsync(h->sp_state, 0, 12 * sizeof(int), h->stream));
     KCHK(launch_sparse_lists(sa, h->stream));
     pf.end();
-    for (int l = 0; l < h->sp_levels; ++l) {
-        TIMED(pf, K_CONV, run_conv(fit_frames(h, h->sp_box[l], 3, nb, 0), h->stream));
-        TIMED(pf, K_CONV, run_conv(fit_frames(h, h->sp_b1l[l], 3, nb, 0), h->stream));
+    // the gated dense fall-back (two convs per level and the box decode) is enqueued only where the flag can be raised at all: with the
+    // default sparse_cap of 1.0 every list holds the whole chunk, and the launches would each leave at their first instruction
+    if (can_overflow) {
+        for (int l = 0; l < h->sp_levels; ++l) {
+            TIMED(pf, K_CONV, run_conv(fit_frames(h, h->sp_box[l], 3, nb, 0), h->stream));
+            TIMED(pf, K_CONV, run_conv(fit_frames(h, h->sp_b1l[l], 3, nb, 0), h->stream));
+        }
+        d.gate = h->sp_state + 8; d.fallback_count = h->sp_state + 12;
+        TIMED(pf, K_DECODE, launch_decode(d, false, h->stream, 2));
     }
-    d.gate = h->sp_state + 8; d.fallback_count = h->sp_state + 12;
-    TIMED(pf, K_DECODE, launch_decode(d, false, h->stream, 2));
     TIMED(pf, K_CONV, launch_sparse_box(sa, h->stream));
     // this chunk's counts travel to pinned host memory behind the kernels (no wait here): infer_impl judges them after the call's
     // own final synchronisation

@@ -482,6 +482,32 @@ def plan_versions(n: int, h: int, w: int, cin: int, cout: int, k: int, stride: i
     return [out[i] for i in range(min(cap, npl.value))]
 
 
+PLAN_TILE_FIELDS = ("version", "PT", "CT", "WP", "TW", "TH", "G", "grid_x", "grid_y")
+
+
+def plan_tiles(n: int, h: int, w: int, cin: int, cout: int, k: int, stride: int = 1, src_cs: int = 0, dst_cs: int = 0, res_cs: int = 0,
+               f2_cout: int = 0, f2_dst_cs: int = 0, half: bool = False):
+    """The candidate launch plans of :func:`plan_versions`, in the same order, each as a dict of its launch geometry (host-only
+    query): ``version``, ``PT`` / ``CT`` (pixel / cout tiles of 16 per wave), ``WP`` (waves along pixels), ``TW`` x ``TH`` (output
+    tile), ``G`` (cout groups per wave), ``grid_x`` / ``grid_y``; and, worked out here for the LDS-staged kernels, ``P`` (pixels a
+    block computes = WP * PT * 16) and ``tiles_x`` / ``tiles_y`` (tiles over the output map): tiles_x * tiles_y * P pixels are
+    computed per image for the map's Wout * Hout."""
+    cap, nf = 4096, len(PLAN_TILE_FIELDS)
+    out = (C.c_int * (cap * nf))()
+    npl = C.c_int(0)
+    r4 = lambda c: (c + 3) // 4 * 4
+    _lib.check(_lib.lib().mi355_plan_query_tiles(n, h, w, cin, cout, k, stride, src_cs or r4(cin), dst_cs or r4(cout), res_cs, f2_cout,
+                                                 f2_dst_cs or r4(f2_cout), int(half), out, cap, C.byref(npl)))
+    wo, ho = (n * h * w, 1) if k == 1 else (w // stride, h // stride)
+    plans = []
+    for i in range(min(cap, npl.value)):
+        p = dict(zip(PLAN_TILE_FIELDS, out[i * nf:(i + 1) * nf]))
+        p["P"] = p["WP"] * p["PT"] * 16
+        p["tiles_x"], p["tiles_y"] = -(-wo // p["TW"]), -(-ho // p["TH"])
+        plans.append(p)
+    return plans
+
+
 def memory_plan(blob: bytes, n: int, height: int, width: int, imgsz: int = 640, half: bool = False, reuse: bool = True):
     """Where the engine would place the activation buffers of weight image ``blob`` for ``n`` frames per pass (host-only query):
     -> (offsets [n_buffers], sizes [n_buffers], arena_bytes, unshared_bytes)."""

@@ -273,6 +273,12 @@ int  mi355_bench_conv2d_f16(int device_id, int n, int h, int w, int cin, int cou
  * (f2_cout > 0).  res_cs = 0: no residual.  For the planner's unit tests (address-range guards). */
 int  mi355_plan_query(int n, int h, int w, int cin, int cout, int k, int stride, int src_cs, int dst_cs, int res_cs,
                       int f2_cout, int f2_dst_cs, int half, int* versions, int cap, int* n_plans);
+/* The same query with every candidate's launch geometry: tiles[9 * i ..] = version (as above), PT (pixel tiles of 16 per wave), CT
+ * (cout tiles per wave), WP (waves along pixels), TW, TH (output tile), G (cout groups a wave walks), grid.x, grid.y.  A block of
+ * the LDS-staged kernels covers WP * PT * 16 pixels.  cap counts candidates (9 ints each). */
+#define MI355_PLAN_TILE_FIELDS 9
+int  mi355_plan_query_tiles(int n, int h, int w, int cin, int cout, int k, int stride, int src_cs, int dst_cs, int res_cs,
+                            int f2_cout, int f2_dst_cs, int half, int* tiles, int cap, int* n_plans);
 /* HOST computation (no GPU): pyramidal Lucas-Kanade optical flow of n points between two gray uint8 frames [height][width] --
  * the cv2.calcOpticalFlowPyrLK step of BoT-SORT's global motion compensation (ultralytics/trackers/utils/gmc.py, reached
  * from /root/reference/model.py:38).  win x win windows (odd), max_level + 1 pyramid levels, at most max_iters iterations or

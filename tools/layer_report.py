@@ -23,15 +23,21 @@ tail_label = ["decode_kernel"]
 # A shape that runs the sparse box branch ("[sparse] 1 <levels>" in the engine log): the box chain's ops are
 # not launched ("[sched]" marks them 0) and the tail is score stage, position lists, per level the two gated dense launches (they leave
 # at once unless a list overflowed), the gated box decode, and the two sparse stages.
-sparse_levels = 0
+# A third field 0 ("[sparse] 1 <levels> 0"): every list holds all of the chunk's positions, so the gated launches are not enqueued at all.
+sparse_levels, gated = 0, True
 if len(sys.argv) > 6 and os.path.exists(sys.argv[6]):
     for l in open(sys.argv[6]):
-        if l.startswith("[sparse] "): sparse_levels = int(l.split()[2]) if l.split()[1] == "1" else 0
+        if l.startswith("[sparse] "):
+            sparse_levels = int(l.split()[2]) if l.split()[1] == "1" else 0
+            gated = len(l.split()) < 4 or l.split()[3] != "0"
 if sparse_levels:
-    tail = ["decode_kernel", "sparse_lists"] + ["conv"] * (2 * sparse_levels) + ["decode_kernel", "sparse_conv_a", "sparse_conv_b"]
-    tail_label = ["score stage (decode part 1)", "sparse_lists"]
-    for lv in range(sparse_levels): tail_label += [f"cv2.{lv}.0 box couts (gated dense)", f"cv2.{lv}.1+cv2.{lv}.2 (gated dense)"]
-    tail_label += ["box decode (gated dense)", "sparse stage A: cv2.i.0 at dilated positions", "sparse stage B: cv2.i.1+cv2.i.2+DFL at candidates"]
+    tail, tail_label = ["decode_kernel", "sparse_lists"], ["score stage (decode part 1)", "sparse_lists"]
+    if gated:
+        tail += ["conv"] * (2 * sparse_levels) + ["decode_kernel"]
+        for lv in range(sparse_levels): tail_label += [f"cv2.{lv}.0 box couts (gated dense)", f"cv2.{lv}.1+cv2.{lv}.2 (gated dense)"]
+        tail_label += ["box decode (gated dense)"]
+    tail += ["sparse_conv_a", "sparse_conv_b"]
+    tail_label += ["sparse stage A: cv2.i.0 at dilated positions", "sparse stage B: cv2.i.1+cv2.i.2+DFL at candidates"]
 orders = [list(range(len(prog.ops)))]                       # program order (profiling passes) ...
 launched = {i: True for i in range(len(prog.ops))}
 if sched_log and os.path.exists(sched_log):
