@@ -49,6 +49,13 @@ class Timing(C.Structure):
                 ("nms_ms", C.c_float), ("conv_launches", C.c_int), ("frames", C.c_int)]
 
 
+class YuvFrame(C.Structure):
+    """mi355_yuv_frame: one NV12 / I420 frame by plane pointers (NV12: u = the interleaved UV plane, v = NULL)"""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("height", C.c_int), ("width", C.c_int),
+                ("y_stride", C.c_int), ("uv_stride", C.c_int), ("format", C.c_int), ("reserved", C.c_int)]
+
+
+PIX_NV12, PIX_I420 = 1, 2               # MI355_PIX_*
 DET_WORDS = C.sizeof(Det) // 4          # 58 32-bit words per row
 POSE_F32, POSE_F64 = 0, 1               # MI355_POSE_F32 / MI355_POSE_F64: the element type of a pose array
 _P = C.POINTER
@@ -71,6 +78,11 @@ SIGNATURES = {
                                          _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
     "mi355_yolo_raw_head_multi": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             _i32p, _i32p]),
+    "mi355_yolo_infer_yuv": (C.c_int, [C.c_void_p, _P(YuvFrame), C.c_int, C.c_int, C.c_float, C.c_float, _i32p, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_int, _i32p]),
+    "mi355_yolo_infer_yuv_device_async": (C.c_int, [C.c_void_p, _P(YuvFrame), C.c_int, C.c_float, C.c_float, _i32p, C.c_int, C.c_int, C.c_int,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi355_op_yuv_to_bgr": (C.c_int, [C.c_int, _P(YuvFrame), C.c_int, _P(C.c_void_p)]),
     "mi355_yolo_stream": (C.c_void_p, [C.c_void_p]),
     "mi355_yolo_sync": (C.c_int, [C.c_void_p]),
     "mi355_yolo_raw_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -184,6 +184,17 @@ struct LetterboxMultiArgs {
     uint8_t* dst; int Hd, Wd, B;                     // canvas; Wd % 4 == 0
 };
 const char* launch_letterbox_multi(const LetterboxMultiArgs& a, hipStream_t st);
+// 4:2:0 YUV -> dense BGR at ingest (yuv_kernels.hip): one descriptor per frame in device memory, one launch for all
+// frames of a chunk whatever their sizes.  format 1 = NV12 (u = the interleaved UV plane, v unused), 2 = I420.  vec: the frame takes
+// the 16-pixels-per-lane path (yuv_vector_ok), 0 = one 2x2 block per lane with byte accesses.  dst = dense [H][W][3].
+struct YuvFrameDesc {
+    const uint8_t* y; const uint8_t* u; const uint8_t* v; uint8_t* dst;
+    int H, W, y_stride, uv_stride, format, vec, pad_[2];
+};
+bool yuv_vector_ok(const YuvFrameDesc& f);
+// frames_host = the same B descriptors as the host sees them (the grid is sized from their shapes)
+const char* launch_yuv_to_bgr(const YuvFrameDesc* frames_dev, const YuvFrameDesc* frames_host, int B, hipStream_t st);
+void yuv_to_bgr_host(const YuvFrameDesc* frames, int B);     // the host twin: the same per-block routine in a plain loop
 
 // ---- head decode + NMS, post_kernels.hip ----------------------------------------------------------------
 struct HeadLevelArgs { const float* buf; int cs; int box_off, cls_off, kpt_off; int H, W, stride, anchor0; };

@@ -256,6 +256,9 @@ struct mi355_yolo {
     // image of it (h_multi) -- only when that image changed since the last upload (the same cameras call after call)
     Buf h_stage{true};
     Buf d_multi, h_multi{true}; size_t multi_bytes = 0;   // multi_bytes: what d_multi holds of h_multi's image (0 = nothing)
+    // NV12 / I420 frames (engine_yuv.hip): the packed planes of host frames (two chunk slots; pinned staging is h_stage), and the
+    // per-frame conversion descriptors of a call with their pinned image
+    Buf d_yuv, d_yuvdesc, h_yuvdesc{true};
     unsigned long long plan_hash = 0;   // fingerprint of the candidate lists + the chosen indices of the current shape
     int plan_source = 0, plan_launches = 0;   // 0 static guess (autotune off), 1 memory, 2 this machine's plan cache, 3 tuned now, 4 shipped plan file; launches of one pass (stem..last conv)
     bool async_pending = false;         // mi355_yolo_infer_device_async work may still be in flight on `stream`
@@ -337,12 +340,33 @@ int multi_upload(mi355_yolo* h, const MultiFrames& mf, int n, int nb, MultiCall&
 int multi_stage_chunk(mi355_yolo* h, const MultiFrames& mf, const MultiCall& mc, int s0, int m, int slot);
 int run_chunk_multi(mi355_yolo* h, Prof& pf, const MultiCall& mc, int s0, int m, bool full_pred);
 
-// engine_run.hip: one infer call.  An entry point fills what it uses: the frames (one dense block of one shape, or `multi`), the
+// engine_yuv.hip: NV12 / I420 frames.  Per chunk ONE conversion launch in front of run_chunk / run_chunk_multi writes
+// the dense BGR frames into the d_in slot those read, laid out as a host-frame call's staging would be: frames of one size back to back
+// (the single-shape path follows), frames of different sizes at MultiCall.stage_off (the `multi` path follows, fed by YuvCall.mf).  Host
+// planes travel chunk by chunk through pinned staging into the two slots of d_yuv, rows packed.
+struct YuvCall {
+    std::vector<int> heights, widths;         // per frame
+    bool same = true;                         // all frames one (h, w)
+    MultiFrames mf{};                         // the converted frames of different sizes as the multi path sees them (staged: host layout)
+    std::vector<size_t> bgr_off;              // frame i's BGR bytes inside its chunk's d_in slot
+    std::vector<size_t> plane_off;            // host planes: frame i's packed planes inside its chunk's d_yuv slot (Y, then chroma)
+    size_t yuv_slot_bytes = 0;
+    const YuvFrameDesc* d_desc = nullptr;     // device [n]
+};
+int yuv_check(const mi355_yuv_frame* frames, int n);
+YuvFrameDesc yuv_desc(const mi355_yuv_frame& f, uint8_t* dst);     // a frame where it lies, with the caller's strides
+void yuv_layout(const mi355_yuv_frame* frames, int n, int nb, YuvCall& yc);
+int yuv_upload(mi355_yolo* h, const mi355_yuv_frame* frames, bool on_device, int n, int nb, size_t bgr_slot_bytes, YuvCall& yc);
+int yuv_stage_chunk(mi355_yolo* h, const mi355_yuv_frame* frames, const YuvCall& yc, int s0, int m, int slot);
+int yuv_convert_chunk(mi355_yolo* h, Prof& pf, const YuvCall& yc, int s0, int m);
+
+// engine_run.hip: one infer call.  An entry point fills what it uses: the frames (one dense block of one shape, `multi`, or `yuv`), the
 // filter, and one of the two output forms.
 struct InferCall {
     const uint8_t* src = nullptr; bool on_device = false;
     int n = 0, height = 0, width = 0, row_stride = 0;         // row_stride 0 = width * 3; host frames only
     const MultiFrames* multi = nullptr;                       // frames of different sizes: src, on_device and the sizes above are not read
+    const mi355_yuv_frame* yuv = nullptr;                     // n NV12 / I420 frames (on_device: where their planes live): src, multi and the sizes are not read
     float conf = 0.25f, iou = 0.7f; const int* classes = nullptr; int n_classes = 0, max_det = 0, imgsz = 0;
     mi355_det* out_rows = nullptr; int cap = 1; int* out_counts = nullptr;                        // host rows [n][cap] and counts
     mi355_det* dev_rows = nullptr; int* dev_counts = nullptr; int* dev_total = nullptr;          // or: packed device rows, asynchronous

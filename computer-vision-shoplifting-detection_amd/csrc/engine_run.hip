@@ -388,7 +388,7 @@ static int collect_timing(mi355_yolo* h, Prof& pf, int frames) {
 struct CallState {
     InferCall c;
     bool async_out = false;             // packed rows, counts and the row total stay in the caller's DEVICE buffers
-    Geometry g{}; int nb = 0; MultiCall mc;
+    Geometry g{}; int nb = 0; MultiCall mc; YuvCall yc;
     size_t frame_bytes = 0, slot_bytes = 0;     // one dense frame (single shape); one staging slot = one chunk of host frames
     const unsigned* cmask = nullptr;
     bool single_chunk = false, direct_host = false, sp_adaptive = false;
@@ -399,11 +399,20 @@ struct CallState {
 static int check_call(mi355_yolo* h, CallState& s) {
     InferCall& c = s.c;
     s.async_out = c.dev_rows != nullptr;
-    if (!h || !(c.src || c.multi) || (!s.async_out && (!c.out_rows || !c.out_counts)) || (s.async_out && (!c.dev_counts || !c.dev_total)))
+    if (!h || !(c.src || c.multi || c.yuv) || (!s.async_out && (!c.out_rows || !c.out_counts)) || (s.async_out && (!c.dev_counts || !c.dev_total)))
         return fail(MI355_EINVAL, "null argument");
+    if (c.yuv) {                        // NV12 / I420 frames: one size -> the single-shape call on the converted frames, else `multi`
+        const int rc = yuv_check(c.yuv, c.n); if (rc) return rc;
+        YuvCall& yc = s.yc;
+        for (int i = 0; i < c.n; ++i) { yc.heights.push_back(c.yuv[i].height); yc.widths.push_back(c.yuv[i].width); }
+        for (int i = 1; i < c.n; ++i) yc.same = yc.same && yc.heights[i] == yc.heights[0] && yc.widths[i] == yc.widths[0];
+        yc.mf = MultiFrames{nullptr, yc.heights.data(), yc.widths.data(), nullptr, false};    // the converted frames lie where host frames are staged
+        c.src = nullptr; c.multi = yc.same ? nullptr : &yc.mf;
+        c.height = yc.heights[0]; c.width = yc.widths[0]; c.row_stride = 0;
+    }
     if (c.multi) {                      // frames of different sizes: the size arguments are per frame (mi355_yolo_infer_multi)
-        const int rc = multi_check(*c.multi, c.n); if (rc) return rc;
-        c.on_device = c.multi->on_device; c.height = c.width = 1; c.row_stride = 0;
+        if (!c.yuv) { const int rc = multi_check(*c.multi, c.n); if (rc) return rc; c.on_device = c.multi->on_device; }
+        c.height = c.width = 1; c.row_stride = 0;
     }
     if (c.n <= 0 || c.height <= 0 || c.width <= 0) return fail(MI355_EINVAL, "n, height and width must be positive");
     if (c.max_det <= 0) c.max_det = 300;
@@ -423,13 +432,16 @@ static int call_shape(mi355_yolo* h, CallState& s) {
     s.g = make_geometry(c.height, c.width, c.imgsz);
     s.nb = std::min(c.n, h->chunk);
     s.single_chunk = c.n <= s.nb;
+    if (c.yuv && !c.on_device) yuv_layout(c.yuv, c.n, s.nb, s.yc);
     if (c.multi) {
         multi_prepare(*c.multi, c.n, s.nb, c.imgsz, s.mc);
         s.slot_bytes = s.mc.slot_bytes;                     // the largest chunk's frames, packed
+        s.yc.bgr_off = s.mc.stage_off;                      // (YUV frames: where the conversion writes them)
         return ensure_shape(h, s.nb, s.mc.Hd, s.mc.Wd);
     }
     s.frame_bytes = (size_t)c.height * c.width * 3;
     s.slot_bytes = (size_t)s.nb * s.frame_bytes;
+    for (int i = 0; c.yuv && i < c.n; ++i) s.yc.bgr_off.push_back((size_t)(i % s.nb) * s.frame_bytes);
     const int rc = ensure_shape(h, s.nb, s.g.Hl, s.g.Wl); if (rc) return rc;
     return prepare_geometry(h, s.g, c.imgsz);
 }
@@ -450,6 +462,7 @@ static int grow_scratch(mi355_yolo* h, const CallState& s) {
 // run; a slot is only overwritten after the kernels that read it (letterbox / stem) have been passed.
 static int copy_chunk(mi355_yolo* h, const CallState& s, int s0, int m, int slot) {
     const InferCall& c = s.c;
+    if (c.yuv) return yuv_stage_chunk(h, c.yuv, s.yc, s0, m, slot);
     if (c.multi) return multi_stage_chunk(h, *c.multi, s.mc, s0, m, slot);
     HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_consumed[slot], 0));
     HIPCHK(hipMemcpy2DAsync(h->d_in.p + (size_t)slot * s.slot_bytes, (size_t)c.width * 3, c.src + (size_t)s0 * c.height * c.row_stride,
@@ -510,9 +523,13 @@ static int run_chunks(mi355_yolo* h, const CallState& s, Prof& pf) {
     const int n = c.n, nb = s.nb;
     for (int s0 = 0, ci = 0; s0 < n; s0 += nb, ++ci) {
         const int m = std::min(nb, n - s0);
-        const uint8_t* chunk_frames = c.multi ? nullptr : c.src + (size_t)s0 * s.frame_bytes;
+        const uint8_t* chunk_frames = c.multi || c.yuv ? nullptr : c.src + (size_t)s0 * s.frame_bytes;
         if (!c.on_device) {
             HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copied[ci & 1], 0));
+            chunk_frames = h->d_in.p + (size_t)(ci & 1) * s.slot_bytes;
+        }
+        if (c.yuv) {                    // NV12 / I420 planes (staged, or the caller's on the device) -> the BGR frames of this chunk's d_in slot
+            const int rc = yuv_convert_chunk(h, pf, s.yc, s0, m); if (rc) return rc;
             chunk_frames = h->d_in.p + (size_t)(ci & 1) * s.slot_bytes;
         }
         int rc = c.multi ? run_chunk_multi(h, pf, s.mc, s0, m, false) : run_chunk(h, pf, chunk_frames, m, s.g, false); if (rc) return rc;
@@ -568,7 +585,8 @@ int infer_impl(mi355_yolo* h, const InferCall& call) {
         h->async_pending = false;
     }
     rc = call_shape(h, s); if (rc) return rc;
-    if (!c.on_device) GROW(h->d_in, 2 * s.slot_bytes);      // host frames: a double-buffered staging area of two chunks
+    if (!c.on_device || c.yuv) GROW(h->d_in, 2 * s.slot_bytes);     // host frames / converted YUV frames: a double-buffered staging area of two chunks
+    if (c.yuv) { rc = yuv_upload(h, c.yuv, c.on_device, c.n, s.nb, s.slot_bytes, s.yc); if (rc) return rc; }
     if (c.multi) { rc = multi_upload(h, *c.multi, c.n, s.nb, s.mc); if (rc) return rc; }    // descriptors point into d_in (host frames)
     if (!c.on_device) {
         HIPCHK(hipEventRecord(h->ev_consumed[0], h->stream));

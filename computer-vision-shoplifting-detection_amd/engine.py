@@ -19,6 +19,7 @@ import torch
 from . import _lib
 from .results import Results
 from .weights import build_from_state_dict, from_bytes
+from .yuv import YUVFrame, as_frames, struct_array
 
 COCO_NAMES = ["person", "bicycle", "car", "motorcycle", "airplane", "bus", "train", "truck", "boat", "traffic light",
               "fire hydrant", "stop sign", "parking meter", "bench", "bird", "cat", "dog", "horse", "sheep", "cow",
@@ -171,10 +172,32 @@ class YOLO:
             self.row_strides = np.array([3 * s[1] for s in self.shapes], np.int32)
             self.ptrs = (C.c_void_p * n)(*[int(p) for p in ptrs])
 
+    class _YuvBatch:
+        """NV12 / I420 frames (:class:`YUVFrame`) of any sizes in one call, all on the host or all on the engine's GPU, passed to
+        ``mi355_yolo_infer_yuv`` by plane pointers: the engine converts them to BGR on the GPU in front of the letterbox."""
+        def __init__(self, frames):
+            self.frames = list(frames)                          # kept alive for the call: the engine reads the planes by pointer
+            on_dev = {f.on_device for f in self.frames}
+            if len(on_dev) != 1:
+                raise ValueError("a list of YUVFrames must be all host planes or all CUDA planes")
+            self.on_device = on_dev.pop()
+            self.shape = (len(self.frames),)
+            self.shapes = [f.shape for f in self.frames]
+            self.structs = struct_array(self.frames)
+
+        def check_device(self, device: int):
+            if self.on_device:
+                if any(p.device.index != device for f in self.frames for p in f._planes()):
+                    raise ValueError("frames live on a different GPU than the engine")
+                torch.cuda.current_stream(self.frames[0].y.device).synchronize()     # the engine runs on its own stream
+
     @staticmethod
     def _as_batch(source):
         """-> (array-or-tensor [N,H,W,3] uint8, list of originals or None); a list of frames of different shapes -> (_Ragged, list of
-        originals or None)"""
+        originals or None); YUVFrames -> (_YuvBatch, None)"""
+        yuv = as_frames(source)
+        if yuv is not None:
+            return YOLO._YuvBatch(yuv), None
         if isinstance(source, torch.Tensor):
             if source.dtype != torch.uint8 or source.ndim != 4 or source.shape[-1] != 3:
                 raise ValueError("tensor sources must be uint8 [N,H,W,3] BGR frames")
@@ -214,7 +237,7 @@ class YOLO:
         hnd = self._handle(half)
         self._last_handle = hnd
         n = int(batch.shape[0])
-        h, w = (0, 0) if isinstance(batch, YOLO._Ragged) else (int(batch.shape[1]), int(batch.shape[2]))
+        h, w = (0, 0) if isinstance(batch, (YOLO._Ragged, YOLO._YuvBatch)) else (int(batch.shape[1]), int(batch.shape[2]))
         rows = np.empty((n, max_det, _lib.DET_WORDS), dtype=np.float32)    # only rows[i, :counts[i]] are written / meaningful
         counts = np.zeros(n, dtype=np.int32)
         cls_arr = None
@@ -225,6 +248,11 @@ class YOLO:
             ncls = len(cl)
         cp = counts.ctypes.data_as(C.POINTER(C.c_int))
         with self._lock:
+            if isinstance(batch, YOLO._YuvBatch):
+                batch.check_device(self.device)
+                _lib.check(lib.mi355_yolo_infer_yuv(hnd, batch.structs, int(batch.on_device), n, conf, iou, cls_arr, ncls, max_det, imgsz,
+                                                    rows.ctypes.data, max_det, cp))
+                return rows, counts, batch.shapes
             if isinstance(batch, YOLO._Ragged):
                 if batch.on_device and batch.frames is not None:
                     if any(f.device.index != self.device for f in batch.frames):
@@ -261,11 +289,19 @@ class YOLO:
                     imgsz: int = 640, half=None) -> None:
         """Enqueue one batch of CUDA-resident uint8 frames [n,H,W,3]; the packed post-NMS rows (frame order), the per-frame
         counts and their sum land in ``out`` (from :meth:`new_device_rows`) -- all in HBM.  Returns at once; order other
-        streams behind :attr:`stream` (or call :meth:`sync`) before reading ``out``."""
+        streams behind :attr:`stream` (or call :meth:`sync`) before reading ``out``.  ``frames`` may also be a list of CUDA
+        :class:`YUVFrame`s of one size (NV12 / I420, formats may differ): their planes are converted on the GPU from where they lie."""
         rows, counts, total = out
-        n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-        if not frames.is_cuda or frames.dtype != torch.uint8 or frames.device.index != self.device:
-            raise ValueError("infer_async needs uint8 frames on the engine's GPU")
+        yuv = as_frames(frames)
+        if yuv is not None:
+            yuv = YOLO._YuvBatch(yuv)
+            if not yuv.on_device or len(set(yuv.shapes)) != 1:
+                raise ValueError("infer_async needs YUVFrames of one size with planes on the engine's GPU")
+            n = yuv.shape[0]
+        else:
+            n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+            if not frames.is_cuda or frames.dtype != torch.uint8 or frames.device.index != self.device:
+                raise ValueError("infer_async needs uint8 frames on the engine's GPU")
         if rows.shape[0] < n * max_det or counts.numel() < n:
             raise ValueError("output buffers are too small for n * max_det rows")
         cls_arr, ncls = None, 0
@@ -275,6 +311,11 @@ class YOLO:
         hnd = self._handle(half)
         self._async_handle = hnd              # `stream` / `sync()` refer to the engine that received the last asynchronous call
         with self._lock:
+            if yuv is not None:
+                yuv.check_device(self.device)
+                _lib.check(_lib.lib().mi355_yolo_infer_yuv_device_async(hnd, yuv.structs, n, float(conf), float(iou), cls_arr, ncls, int(max_det),
+                                                                        int(imgsz), rows.data_ptr(), counts.data_ptr(), total.data_ptr()))
+                return
             torch.cuda.current_stream(frames.device).synchronize()       # the frames must be complete; the engine has its own stream
             _lib.check(_lib.lib().mi355_yolo_infer_device_async(hnd, frames.data_ptr(), n, h, w, float(conf), float(iou), cls_arr, ncls,
                                                                 int(max_det), int(imgsz), rows.data_ptr(), counts.data_ptr(),
@@ -360,6 +401,11 @@ class YOLO:
         if self._tracker is None or not persist:
             # the frame preparation and the optical flow of its motion compensation run on the engine's GPU (csrc/gmc_kernels.hip)
             self._tracker = BYTETracker(gmc_device=getattr(self, "device", None))
+        yuv = as_frames(source)
+        if yuv is not None:
+            # the convenience form: the motion compensation takes a host BGR frame, so a YUV frame is converted on the GPU and its BGR
+            # bytes come back to the host (one device-to-host copy per frame); the call then proceeds as on BGR frames
+            source = [f.to_bgr(self.device) for f in yuv]
         batch, originals = self._as_batch(source)
         if isinstance(batch, YOLO._Ragged):
             raise ValueError("frames of different shapes in one call are not supported; call once per shape")
@@ -415,7 +461,8 @@ class YOLO:
         if unknown:                                              # show / verbose are accepted and ignored, as in track()
             raise TypeError(f"track_cameras: unsupported argument(s) {sorted(unknown)} (iou, classes, max_det, imgsz, half pass through)")
         conf = 0.1 if conf is None else float(conf)
-        frames = list(frames)
+        # a camera that delivers a YUVFrame: converted on the GPU, its BGR bytes brought to the host for the motion compensation (as track())
+        frames = [f.to_bgr(self.device) if isinstance(f, YUVFrame) else f for f in frames]
         n = len(frames)
         if n == 0:
             raise ValueError("empty list of cameras")
@@ -471,6 +518,8 @@ class YOLO:
         shapes: the square ``imgsz x imgsz`` canvas, A = its anchors)."""
         lib = _lib.lib()
         hnd = self._handle(half)
+        if as_frames(source) is not None:
+            raise TypeError("raw_head takes BGR frames: convert a YUVFrame with .to_bgr() first")
         batch, _ = self._as_batch(source)
         if isinstance(batch, YOLO._Ragged):
             ch, an = C.c_int(), C.c_int()

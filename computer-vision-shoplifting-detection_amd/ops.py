@@ -377,6 +377,29 @@ def letterbox_multi(frames: Sequence[np.ndarray], imgsz: int = 640, device: int 
     return out
 
 
+def yuv_to_bgr(frames, device: int = 0, out: Optional[Sequence[np.ndarray]] = None):
+    """NV12 / I420 frames (``cvsd_amd.YUVFrame``, any sizes and row strides, formats may be mixed) -> a list of BGR arrays [H, W, 3]: the
+    conversion the engine runs at ingest, alone.  ``device=-1`` runs the kernel's host twin and touches no GPU.  ``out``: C-contiguous
+    uint8 arrays [H, W, 3] to write into (a test passes views of guarded buffers).  Planes on the GPU are brought to the host first:
+    the hook takes host memory."""
+    from .yuv import as_frames, struct_array
+    fr = as_frames(frames)
+    if fr is None:
+        raise ValueError("frames: pass a YUVFrame or a list of them")
+    fr = [f.host() for f in fr]
+    if out is None:
+        out = [np.empty((max(f.shape[0], 0), max(f.shape[1], 0), 3), np.uint8) for f in fr]
+    out = list(out)
+    if len(out) != len(fr):
+        raise ValueError("out: one array per frame")
+    for f, o in zip(fr, out):
+        if not isinstance(o, np.ndarray) or o.dtype != np.uint8 or o.shape != (f.shape[0], f.shape[1], 3) or not o.flags.c_contiguous:
+            raise ValueError("out: C-contiguous uint8 arrays of shape [H, W, 3]")
+    ptrs = (C.c_void_p * len(out))(*[o.ctypes.data or 1 for o in out])     # (an empty array has no address; the frame is refused before any write)
+    _lib.check(_lib.lib().mi355_op_yuv_to_bgr(int(device), struct_array(fr), len(fr), ptrs))
+    return out
+
+
 def nms(pred: np.ndarray, nc: int, conf: float = 0.25, iou: float = 0.7, classes: Optional[Sequence[int]] = None,
         max_det: int = 300, device: int = 0):
     """non_max_suppression on pred [N, 4+nc+extra, A] -> list of (rows [n,6+extra], anchor_idx [n])."""

@@ -169,6 +169,52 @@ int  mi355_yolo_infer_device_async(mi355_yolo* h, const uint8_t* bgr_nhwc_dev, i
 void* mi355_yolo_stream(mi355_yolo* h);
 int  mi355_yolo_sync(mi355_yolo* h);
 
+/* ---- 4:2:0 YUV frames, as video decoders emit them -----------------------------------------------------------
+ * NV12 and I420 frames are converted to BGR on the GPU, by one launch per chunk in front of the letterbox / stem, into the dense BGR
+ * staging buffer those kernels already read: every later kernel runs unchanged, on the bytes cv2.cvtColor with COLOR_YUV2BGR_NV12 /
+ * COLOR_YUV2BGR_I420 would have handed to mi355_yolo_infer (BT.601 limited range, 20-bit fixed point, one chroma sample per 2x2 block
+ * of Y, no chroma interpolation):
+ *     uu = U - 128;  vv = V - 128;  yy = max(0, Y - 16) * 1220542
+ *     R = sat_u8((yy + (1 << 19) + 1673527 * vv) >> 20)
+ *     G = sat_u8((yy + (1 << 19) - 852492 * vv - 409993 * uu) >> 20)          (>> arithmetic: floor for negative sums)
+ *     B = sat_u8((yy + (1 << 19) + 2116026 * uu) >> 20)
+ * A frame is three plane pointers: decoders pad rows and do not keep planes adjacent.
+ *   y           [height][y_stride] bytes
+ *   u, v        NV12: u = the interleaved plane [height/2][uv_stride] holding U,V,U,V..., v = NULL (not read)
+ *               I420: u and v = separate planes [height/2][uv_stride], width/2 samples each
+ *   height, width    even and positive;  y_stride >= width;  uv_stride >= width (NV12), >= width/2 (I420); strides in bytes
+ *   format      MI355_PIX_NV12 or MI355_PIX_I420;  reserved = 0
+ * Every entry point below checks all frames before anything runs and refuses with MI355_EINVAL (the message names the field): a null
+ * y or u, a null v of an I420 frame, an odd or non-positive height or width, a stride smaller than its row, an unknown format.
+ * A frame whose width is a multiple of 16 and whose plane bases and strides are multiples of 16 bytes (8 for I420 chroma) is converted
+ * 16 pixels x 2 rows per lane with 16-byte accesses (every real video size); any other frame one 2x2 block per lane, by bytes. */
+#define MI355_PIX_NV12 1
+#define MI355_PIX_I420 2
+typedef struct mi355_yuv_frame {
+    const uint8_t* y; const uint8_t* u; const uint8_t* v;   /* NV12: u = the interleaved UV plane, v = NULL */
+    int height, width, y_stride, uv_stride, format, reserved;
+} mi355_yuv_frame;
+/* mi355_yolo_infer_multi on YUV frames: n frames that need not share a size or a format.  All frames the same (h, w): the rect
+ * letterbox, the rows are those of mi355_yolo_infer on the converted stack; otherwise the square canvas with per-frame scale-back.
+ *   frames_on_device = 0   the planes are HOST memory: packed row by row (padding is not uploaded) into pinned staging, one
+ *                          host-to-device copy per chunk on the copy stream while the previous chunk's kernels run -- 1.5 bytes per
+ *                          pixel instead of the 3 of a BGR frame
+ *   frames_on_device = 1   the planes are memory of the engine's device (a decoder's surfaces), converted from where they are
+ *   other arguments        as mi355_yolo_infer; the conversion's time is part of mi355_timing.letterbox_ms */
+int  mi355_yolo_infer_yuv(mi355_yolo* h, const mi355_yuv_frame* frames, int frames_on_device, int n, float conf, float iou,
+                          const int* classes, int n_classes, int max_det, int imgsz,
+                          mi355_det* out_rows, int out_capacity_per_image, int* out_counts);
+/* mi355_yolo_infer_device_async on YUV frames: planes in DEVICE memory, all n frames the same (h, w) (formats may differ); nothing
+ * crosses PCIe except the n frame descriptors, and the call returns once the work is enqueued. */
+int  mi355_yolo_infer_yuv_device_async(mi355_yolo* h, const mi355_yuv_frame* frames, int n, float conf, float iou,
+                                       const int* classes, int n_classes, int max_det, int imgsz,
+                                       mi355_det* rows_dev, int* counts_dev, int* total_dev);
+/* The conversion alone, for parity tests: planes and outputs are HOST memory, bgr_out[i] = dense height_i * width_i * 3 bytes.
+ * device_id >= 0 runs the kernel on planes uploaded with the caller's strides and base alignment (modulo 16), so a frame takes the
+ * path it would take in place; the device copy of every output is followed by guard bytes, and the call fails with MI355_EHIP when
+ * the launch changed one.  device_id = -1 runs the same per-block routine in a host loop and touches no GPU. */
+int  mi355_op_yuv_to_bgr(int device_id, const mi355_yuv_frame* frames, int n, uint8_t* const* bgr_out);
+
 /* The decoded pre-NMS head tensor, exactly the layout Detect/Pose.forward returns: out[n][4+nc+nk][A] fp32
  * (xywh in letterboxed pixels, sigmoid class scores, decoded keypoints).  For parity tests.
  * out may be NULL to query *out_channels / *out_anchors for the given frame size. */
