@@ -36,6 +36,9 @@ struct ConvArgs {
     // f2_lead_c is a multiple of 16 and f2_wpk is packed for f2_lead_c + Cout input channels.  0: the pointwise conv reads
     // exactly this conv's output.
     const float* f2_lead = nullptr; int f2_lead_cs = 0, f2_lead_c = 0;
+    // fp32 3x3: the engine launches this conv over its LAST sub_ctiles cout tiles alone (the class couts of a merged head conv in a shape
+    // that runs the sparse box branch); the planner may then offer tiles that cover that sub-range exactly.  0: the whole conv.
+    int sub_ctiles = 0;
 };
 // number of floats pack_conv_weights writes: ceil(cout/16) * k*k * ceil(cin/16) * 256
 size_t packed_weight_floats(int cout, int cin, int k);

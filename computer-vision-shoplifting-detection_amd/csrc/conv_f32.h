@@ -195,6 +195,10 @@ __device__ __forceinline__ void stage_halo(const KA& a, float* lds, const float*
 // form spilled 8-16 registers at that limit, is therefore built for three waves (a budget of 168) and takes 145.  PT*CT == 10 takes 212 (fused
 // 197-199): two waves.  PT*CT == 15 takes 280 (fused 264), 60 of them accumulation registers that hold the block partials: one wave, as the
 // 3 x 5 tile (MI355_V1_MINWAVES16).  No instance uses scratch and none moves an accumulator inside the K loop.
+// Five cout tiles per wave over two / one pixel tiles (3x3 of stride 1, WP 4: DESIGN.md 3.15): PT 2 x CT 5 takes 214 (fused 207), two waves like the
+// other PT*CT == 10 instances.  PT 1 x CT 5 holds 60 registers of weight ring (wf[3][5]) where PT 5 x CT 1 holds 12: at the 128 of four waves it
+// spilled 37 registers (the ring cannot shrink: RW divides the nine taps and RW = 1 has no prefetch), so it is built for three waves like the
+// fused PT*CT == 5 forms and takes 164 (fused 163), no scratch.
 #ifndef MI355_V1_MINWAVES5
 #define MI355_V1_MINWAVES5 4
 #endif
@@ -514,7 +518,7 @@ __device__ __forceinline__ void conv_igemm_f32_body(const KA& a_in, float* lds, 
 }
 
 template <int KS, int STRIDE, int PT, int CT, int WP, bool F2 = false>
-__global__ __launch_bounds__(256, (PT * CT == 4 ? MI355_V1_MINWAVES : PT * CT == 5 ? (F2 ? MI355_V1_MINWAVES5F : MI355_V1_MINWAVES5) : PT * CT == 8 ? MI355_V1_MINWAVES8 :
+__global__ __launch_bounds__(256, (PT * CT == 4 ? MI355_V1_MINWAVES : PT * CT == 5 ? ((F2 || CT == 5) ? MI355_V1_MINWAVES5F : MI355_V1_MINWAVES5) : PT * CT == 8 ? MI355_V1_MINWAVES8 :
                                    PT * CT == 10 ? MI355_V1_MINWAVES10 : PT * CT >= 15 ? MI355_V1_MINWAVES16 : 1)) void conv_igemm_f32(ConvKArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (a.gate && *a.gate == 0) return;                  // block-uniform: one scalar load and a branch

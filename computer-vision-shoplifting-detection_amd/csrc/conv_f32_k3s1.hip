@@ -21,6 +21,9 @@ KernelFn pick_f32_k3s1(int CT, int WP, int PT) {
     // five pixel tiles per wave (blocks of 80 / 160 / 320 pixels): the 20x20 and 40x40 maps of a 640x640 frame tile exactly
     MI355_CASE(5, 1, 4) MI355_CASE(5, 2, 4) MI355_CASE(5, 3, 4) MI355_CASE(5, 1, 2) MI355_CASE(5, 2, 2) MI355_CASE(5, 3, 2)
     MI355_CASE(5, 1, 1) MI355_CASE(5, 2, 1) MI355_CASE(5, 3, 1)
+    // five cout tiles per wave over two / one pixel tiles (blocks of 128 / 64 pixels, all four waves along the pixels): 80 couts in one
+    // block along grid.y, the halo tile staged once for all of them
+    MI355_CASE(2, 5, 4) MI355_CASE(1, 5, 4)
 #undef MI355_CASE
     return nullptr;
 }

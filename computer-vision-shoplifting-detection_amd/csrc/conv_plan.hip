@@ -31,7 +31,7 @@ void pack_conv_weights(const float* w, int cout, int cin, int k, float* out) {
 namespace {
 
 struct Plan { int CT, WP, TW, TH, ck; size_t lds; double cost; int version; int buf_floats; int PT; int G = 1; bool f2 = false; };
-// PT 0 = default (4, or 3 with CT 5), 5 = five pixel tiles (CT <= 3); G = groups of CT cout tiles a wave walks over one staged input; f2 = fused pointwise stage
+// PT 0 = default (4, or 3 with CT 5), 5 = five pixel tiles (CT <= 3), 2 / 1 with CT 5 = five cout tiles over small pixel tiles; G = groups of CT cout tiles a wave walks over one staged input; f2 = fused pointwise stage
 
 KernelFn pick_kernel(int ks, int stride, int CT, int WP, int PT) {
     if (ks == 1 && stride == 1) return pick_f32_k1(CT, WP, PT);
@@ -74,7 +74,7 @@ double latency_factor(const Shape& sh, long blocks, int PT, int CT, int split = 
 // Candidate launch plans for one conv: for every wave arrangement (CT, WC) the best output tile, with every
 // feasible staged-channel count.  Sorted by a static cost model; the engine may time the first few (autotune).
 std::vector<Plan> enumerate_plans(int H, int W, int images, int n_ctiles, int cin, int ks, int stride, bool have_zero_page, bool half,
-                                  int f2_cin16 = 0, bool need_v4 = false) {
+                                  int f2_cin16 = 0, bool need_v4 = false, int sub_ctiles = 0) {
     static const int max_ct = env_int("MI355_MAX_CT", 5);          // tuning knobs (experiments only)
     static const int min_wc = env_int("MI355_MIN_WC", 1);
     static const int small_pt = env_int("MI355_SMALL_PT", 1);      // 0: never offer the 1- / 2-pixel-tile wave shapes
@@ -112,14 +112,28 @@ std::vector<Plan> enumerate_plans(int H, int W, int images, int n_ctiles, int ci
         return false;
     };
     if (use_pt5 && !half && ks == 3 && !latency_bound) pt_sel.push_back(5);
-    for (int PTsel : pt_sel)
+    // fp32 3x3 of stride 1, throughput regime: FIVE cout tiles per wave over two / one pixel tiles, all four waves along the pixels (blocks of
+    // 128 / 64 pixels) -- the head's 80 class couts in ONE block along grid.y, the halo tile staged once for all of them and no cout tile
+    // computed that does not exist.  Offered only where five tiles cover the couts the launch runs over without padding
+    // (sub_ctiles: a merged head conv that is launched over its class couts alone) and the block tiles the map exactly, as for PT 5;
+    // every other shape keeps its candidate list.
+    static const int use_ct5 = env_int("MI355_CT5", 1);
+    const bool ct5_small = use_ct5 && !half && ks == 3 && stride == 1 && !latency_bound && (sub_ctiles > 0 ? sub_ctiles : n_ctiles) % 5 == 0;
+    struct Sel { int PTsel; bool ct5; };
+    std::vector<Sel> sels;
+    for (int p : pt_sel) sels.push_back({p, false});
+    if (ct5_small) { sels.push_back({2, true}); sels.push_back({1, true}); }
+    for (const Sel& sel : sels)
     for (int WC = 1; WC <= 4; WC *= 2)
         for (int CT = 1; CT <= 5; ++CT) {
+            const int PTsel = sel.PTsel;
             if (CT > max_ct || WC < min_wc) continue;
             if (PTsel == 8 && CT > 4) continue;
-            if (PTsel != 0 && PTsel != 8 && PTsel != 5 && CT > 2) continue;          // small wave tiles exist for CT 1 and 2
+            // small wave tiles exist for CT 1 and 2 -- and, in an entry of their own, for CT 5 with the four waves along the pixels
+            if (sel.ct5 ? (CT != 5 || WC != 1) : (PTsel != 0 && PTsel != 8 && PTsel != 5 && CT > 2)) continue;
             const int WP = 4 / WC, PT = PTsel ? PTsel : (CT == 5 ? 3 : 4), P = WP * PT * 16;
             if (PTsel == 5 && (CT > 3 || tiles_exactly(WP * 64) || !tiles_exactly(P))) continue;
+            if (sel.ct5 && !tiles_exactly(P)) continue;
             // cout groups: G = 1 (one group; more cout tiles = more blocks along grid.y, each staging the input again) or, when
             // all of Cin is staged at once, G = as many groups as cover every cout tile from ONE staged input (fp32 kernels)
             const int g_full = (n_ctiles + CT * WC - 1) / (CT * WC);
@@ -140,7 +154,7 @@ std::vector<Plan> enumerate_plans(int H, int W, int images, int n_ctiles, int ci
                     int TH = P / TW; if (TH > H) TH = H;
                     if (TH < 1) continue;
                     const long tiles = (long)((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-                    if (PTsel == 5 && tiles * P != (long)W * H) continue;     // five pixel tiles: exact covers only (where one fits in LDS)
+                    if ((PTsel == 5 || sel.ct5) && tiles * P != (long)W * H) continue;     // five pixel / cout tiles: exact covers only (where one fits in LDS)
                     const int THin = (TH - 1) * stride + ks, TWin = (TW - 1) * stride + ks;
                     const int stage_floats = round_up(THin * TWin * (ck + lds_pad()), 4);
                     // fused pointwise stage: the first conv's output image [P pixels][f2_cin16 + 4] lives behind the halo tile
@@ -155,7 +169,7 @@ std::vector<Plan> enumerate_plans(int H, int W, int images, int n_ctiles, int ci
                                   + (lds > LDS_SOFT ? 0.15 : 0.0);
                     if (latency_bound) cost *= latency_factor(sh, tiles * images * nblk, PT, CT * G);
                     // (five pixel tiles: of two exact tiles of equal cost, 4x20 and 20x4, the one with the longer rows)
-                    if (cost < best.cost || (PTsel == 5 && cost == best.cost)) { best = Plan{CT, WP, TW, TH, ck, lds, cost, 1, f2_cin16 ? stage_floats : 0, PTsel}; best.G = G; best.f2 = f2_cin16 != 0; }
+                    if (cost < best.cost || ((PTsel == 5 || sel.ct5) && cost == best.cost)) { best = Plan{CT, WP, TW, TH, ck, lds, cost, 1, f2_cin16 ? stage_floats : 0, PTsel}; best.G = G; best.f2 = f2_cin16 != 0; }
                 }
                 if (best.cost < 1e30) out.push_back(best);
                 // fused pointwise stage, one cout group: the first conv's output image may take the halo tile's place in LDS (the tile is
@@ -466,7 +480,7 @@ const char* plan_conv_candidates(const ConvArgs& c, std::vector<ConvLaunch>* out
             return "conv: lead channels of a fused pointwise stage must be whole 16-channel blocks of an aligned fp32 slice";
     }
     const std::vector<Plan> plans = enumerate_plans(H, W, c.k == 1 ? 1 : c.B, (c.Cout + 15) / 16, half ? (c.Cin + 1) / 2 : c.Cin, c.k,
-                                                    c.stride, c.zeros != nullptr, half, c.f2_cout ? round_up(c.Cout, 16) : 0, c.src2 != nullptr);
+                                                    c.stride, c.zeros != nullptr, half, c.f2_cout ? round_up(c.Cout, 16) : 0, c.src2 != nullptr, c.sub_ctiles);
     if (plans.empty()) return "conv: no launch plan fits in LDS";
     const char* last_err = nullptr;
     for (const Plan& p : plans) {

@@ -305,6 +305,7 @@ int create_impl(const uint8_t* blob, size_t nbytes, int device_id, const mi355_o
 void detect_sparse_head(mi355_yolo* h);
 bool sparse_wanted(const mi355_yolo* h, int nb);
 int prepare_sparse_shape(mi355_yolo* h, int nb, int Hl, int Wl);
+ConvLaunch cout_subrange(const ConvLaunch& l0, int t0, int nt);   // a planned 3x3 launch over the cout tiles [t0, t0 + nt) of its conv
 bool sparse_lists_can_overflow(const mi355_yolo* h, int nb);   // a chunk of nb frames of the current shape: is some list shorter than its level's positions?
 // engine_memory.hip: liveness-based placement of the activation buffers in ONE arena (host arithmetic only)
 void plan_memory(mi355_yolo* h, int nb, int Hl, int Wl, std::vector<size_t>* off_out, std::vector<size_t>* bytes_out,

@@ -30,7 +30,9 @@ int mi355_op_letterbox(int device_id, const uint8_t* bgr, int n, int height, int
 
 static int op_conv2d_impl(int device_id, const float* x, int n, int h, int w, int cin, const float* w_oihw, const float* bias,
                           int cout, int k, int stride, int silu, const float* residual, float* y, int plan_index, int* n_plans,
-                          bool half, bool out_f32) {
+                          bool half, bool out_f32, int sub_t0 = 0, int* sub_tile = nullptr) {
+    // sub_t0 > 0 (fp32 3x3, stride 1): the launch runs over the cout tiles [sub_t0, last] alone, as the engine launches a merged head
+    // conv's class couts in a sparse pass; y comes in holding what the other couts must still hold afterwards
     if (!x || !w_oihw || !bias || !y || n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return fail(MI355_EINVAL, "bad argument");
     if (!((k == 1 && stride == 1) || (k == 3 && (stride == 1 || stride == 2)))) return fail(MI355_EINVAL, "k/stride not supported");
     if ((h % stride) || (w % stride)) return fail(MI355_EINVAL, "h and w must be multiples of the stride");
@@ -55,6 +57,10 @@ static int op_conv2d_impl(int device_id, const float* x, int n, int h, int w, in
     int rc = upload(&d_x, dm, xin, es_in); if (rc) return rc;
     HIPCHK(dm.alloc(&d_y, yout.size() * es_out));
     HIPCHK(hipMemset(d_y, 0, yout.size() * es_out));
+    if (sub_t0 > 0) {
+        for (size_t p = 0; p < npo; ++p) std::memcpy(&yout[p * cs_out], y + p * cout, (size_t)cout * 4);
+        HIPCHK(hipMemcpy(d_y, yout.data(), yout.size() * 4, hipMemcpyHostToDevice));
+    }
     if (residual) {
         rs.assign(npo * cs_out, 0.f);
         for (size_t p = 0; p < npo; ++p) std::memcpy(&rs[p * cs_out], residual + p * cout, (size_t)cout * 4);
@@ -79,11 +85,21 @@ static int op_conv2d_impl(int device_id, const float* x, int n, int h, int w, in
     a.src = d_x; a.src_cs = cs_in; a.dst = d_y; a.dst_cs = cs_out; a.res = d_r; a.res_cs = cs_out; a.wpk = d_w; a.bias = d_b;
     a.B = n; a.Hin = h; a.Win = w; a.Hout = ho; a.Wout = wo; a.Cin = cin; a.Cout = cout; a.k = k; a.stride = stride; a.pad = k / 2; a.act = silu ? 1 : 0;
     a.zeros = d_z; a.dtype = half ? 1 : 0; a.out_f32 = (half && out_f32) ? 1 : 0;
+    const int nt = (cout + 15) / 16;
+    if (sub_t0 > 0) a.sub_ctiles = nt - sub_t0;
     std::vector<ConvLaunch> cands;
     KCHK(plan_conv_candidates(a, &cands));
     // plan_index: which candidate launch plan to run (tests sweep it to cover every kernel variant and wave shape)
-    const ConvLaunch& l = cands[(size_t)(plan_index < 0 ? 0 : plan_index) % cands.size()];
+    ConvLaunch l = cands[(size_t)(plan_index < 0 ? 0 : plan_index) % cands.size()];
     if (n_plans) *n_plans = (int)cands.size();
+    if (sub_t0 > 0) {
+        if (l.version != 1 && l.version != 6) return fail(MI355_EINVAL, "sub-range launches exist for the 3x3 kernels only");
+        l = cout_subrange(l, sub_t0, nt - sub_t0);
+    }
+    if (sub_tile) {
+        const int f[MI355_PLAN_TILE_FIELDS] = {l.version, l.PT, l.CT, l.WP, l.a.TW, l.a.TH, l.a.cgroups, (int)l.grid_x, (int)l.grid_y};
+        std::copy(f, f + MI355_PLAN_TILE_FIELDS, sub_tile);
+    }
     KCHK(run_conv(l, nullptr));
     HIPCHK(hipDeviceSynchronize());
     if (es_out == 4) {
@@ -325,6 +341,12 @@ int mi355_op_psa_attention(int device_id, const float* qkv, int n, int hw, int h
 int mi355_op_conv2d(int device_id, const float* x, int n, int h, int w, int cin, const float* w_oihw, const float* bias,
                     int cout, int k, int stride, int silu, const float* residual, float* y, int plan_index, int* n_plans) {
     return op_conv2d_impl(device_id, x, n, h, w, cin, w_oihw, bias, cout, k, stride, silu, residual, y, plan_index, n_plans, false, false);
+}
+
+int mi355_op_conv2d_subrange(int device_id, const float* x, int n, int h, int w, int cin, const float* w_oihw, const float* bias,
+                             int cout, int silu, int t0, float* y, int plan_index, int* n_plans, int* tile) {
+    if (t0 <= 0 || t0 >= (cout + 15) / 16) return fail(MI355_EINVAL, "t0 must name a cout tile behind the first and inside the conv");
+    return op_conv2d_impl(device_id, x, n, h, w, cin, w_oihw, bias, cout, 3, 1, silu, nullptr, y, plan_index, n_plans, false, false, t0, tile);
 }
 
 int mi355_op_conv2d_f16(int device_id, const float* x, int n, int h, int w, int cin, const float* w_oihw, const float* bias,

@@ -9,7 +9,7 @@ namespace mi355 {
 // process) need not repeat it.  The autotuner's CHOICES -- an index into each conv's candidate list -- are kept in a small
 // text file keyed by (model image hash, precision, frames, H, W, planner version); a file whose candidate counts do not
 // match the running planner is ignored.  MI355_PLAN_CACHE=<dir> moves the directory, MI355_PLAN_CACHE=0 turns it off.
-static const char* kPlanVersion = "mi355-plans-r06a";
+static const char* kPlanVersion = "mi355-plans-r07a";
 
 // What a persisted choice (an INDEX into a candidate list) means depends on the lists themselves: the planner build, its env
 // knobs, the GPU.  The file therefore carries a fingerprint of every candidate's launch geometry plus the device's arch name
@@ -126,6 +126,15 @@ int ensure_shape(mi355_yolo* h, int nb, int Hl, int Wl) {
     std::fill(h->skip_op.begin(), h->skip_op.end(), 0);
     std::vector<std::vector<ConvLaunch>> cands(h->ops.size()), cands_f(h->ops.size()), cands_u(h->ops.size());
     std::vector<int> n_cands(h->ops.size(), 0);
+    // A shape that runs the sparse box branch launches the merged cv2.i.0 + cv3.i.0 conv over its class couts alone (cout tiles 4 .. nt - 1:
+    // prepare_sparse_shape): sub_tiles[i] = that many tiles.  The planner is told, so that it can offer tiles that cover the sub-range
+    // exactly, and the stopwatch below times the candidates as that sub-range launch -- what runs -- and not as the whole conv.
+    std::vector<int> sub_tiles(h->ops.size(), 0);
+    if (sparse_wanted(h, nb))
+        for (int l = 0; l < h->sp_levels; ++l) {
+            const int nt = ((int)h->convs[h->ops[h->sp_m[l]].conv].cout + 15) / 16;
+            if (nt > 4) sub_tiles[h->sp_m[l]] = nt - 4;
+        }
     const size_t top = (size_t)std::max(1, h->autotune);
     for (size_t i = 0; i < h->ops.size(); ++i) {
         const FileOp& o = h->ops[i];
@@ -144,6 +153,7 @@ int ensure_shape(mi355_yolo* h, int nb, int Hl, int Wl) {
         a.wpk = h->dconv[o.conv].wpk; a.bias = h->dconv[o.conv].bias; a.zeros = h->zeros;
         a.B = nb; a.Hin = Hl / sd_in; a.Win = Wl / sd_in; a.Hout = Hl / sd_out; a.Wout = Wl / sd_out;
         a.Cin = c.cin; a.Cout = c.cout; a.k = c.k; a.stride = c.s; a.pad = c.pad; a.act = (c.act && h->fast_act) ? 2 : c.act;
+        a.sub_ctiles = sub_tiles[i];
         if (a.Hout * (int)c.s != a.Hin || a.Wout * (int)c.s != a.Win) return fail(MI355_EFORMAT, "conv resolution mismatch in program");
         if (h->fuse_up[i] >= 0) {
             const FileOp& u = h->ops[h->fuse_up[i]];
@@ -279,7 +289,12 @@ int ensure_shape(mi355_yolo* h, int nb, int Hl, int Wl) {
             if (h->ops[i].type != OP_CONV || done[i]) continue;
             const char* name = h->convs[h->ops[i].conv].name;
             int k = 0; float ms = 0.f;
-            if (cands[i].size() > 1 || !cands_f[i].empty()) { const int rc = time_list(cands[i], name, &k, &ms); if (rc) return rc; }
+            if (sub_tiles[i] > 0 && cands[i].size() > 1) {
+                // the class couts alone, as the sparse pass launches them; the choice is still an index into the op's own list
+                std::vector<ConvLaunch> sub;
+                for (const ConvLaunch& l : cands[i]) sub.push_back(cout_subrange(l, 4, sub_tiles[i]));
+                const int rc = time_list(sub, name, &k, &ms); if (rc) return rc;
+            } else if (cands[i].size() > 1 || !cands_f[i].empty()) { const int rc = time_list(cands[i], name, &k, &ms); if (rc) return rc; }
             chosen[i] = k;
             if (!cands_u[i].empty()) {
                 // upsample fused into the read side vs upsample kernel + best plan on its output

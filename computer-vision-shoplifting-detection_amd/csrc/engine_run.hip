@@ -54,7 +54,7 @@ bool sparse_wanted(const mi355_yolo* h, int nb) {
 
 // a planned 3x3 launch over the cout tiles [t0, t0 + nt) of its conv: offsets into the packed weights, the bias and the
 // destination slice, and a grid over fewer cout groups -- the op program, the weight file and the plan files stay as they are
-static ConvLaunch cout_subrange(const ConvLaunch& l0, int t0, int nt) {
+ConvLaunch cout_subrange(const ConvLaunch& l0, int t0, int nt) {
     ConvLaunch l = l0;
     l.a.wpk += (size_t)t0 * 9 * l.a.cib * 256; l.a.bias += t0 * 16; l.a.dst += t0 * 16;
     l.a.Cout = std::min(nt * 16, l0.a.Cout - t0 * 16); l.a.n_ctiles = nt;

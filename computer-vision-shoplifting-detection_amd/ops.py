@@ -47,6 +47,26 @@ def conv2d(x_nhwc: np.ndarray, w_oihw: np.ndarray, bias: np.ndarray, stride: int
     return (y, npl.value) if return_n_plans else y
 
 
+def conv2d_subrange(x_nhwc: np.ndarray, w_oihw: np.ndarray, bias: np.ndarray, t0: int, y_in: np.ndarray, silu: bool = True,
+                    device: int = 0, plan: int = 0):
+    """The 3x3 / stride 1 conv launched over its cout tiles [t0, last] alone (tiles of 16 couts), as the engine launches the class
+    couts of a merged head conv in a sparse pass: -> (y, n_plans, tile).  ``y_in`` [N,H,W,Cout] is what the output buffer holds before
+    the launch (couts below 16 * t0 must come back untouched); ``tile`` is the launch's geometry as in :func:`plan_tiles`."""
+    x, w, b = _f32(x_nhwc), _f32(w_oihw), _f32(bias)
+    n, h, wd, cin = x.shape
+    cout = w.shape[0]
+    if w.shape != (cout, cin, 3, 3) or b.shape != (cout,) or y_in.shape != (n, h, wd, cout):
+        raise ValueError("shape mismatch between x, w, bias and y_in")
+    y = np.array(y_in, dtype=np.float32, order="C", copy=True)
+    npl, tile = C.c_int(0), (C.c_int * len(PLAN_TILE_FIELDS))()
+    _lib.check(_lib.lib().mi355_op_conv2d_subrange(device, x.ctypes.data, n, h, wd, cin, w.ctypes.data, b.ctypes.data, cout, int(silu),
+                                                   int(t0), y.ctypes.data, int(plan), C.byref(npl), tile))
+    p = dict(zip(PLAN_TILE_FIELDS, tile))
+    p["P"] = p["WP"] * p["PT"] * 16
+    p["tiles_x"], p["tiles_y"] = -(-wd // p["TW"]), -(-h // p["TH"])
+    return y, npl.value, p
+
+
 def conv1x1_upcat(x_half: np.ndarray, x_skip: np.ndarray, w_oihw: np.ndarray, bias: np.ndarray, silu: bool = True, device: int = 0,
                   plan: int = 0, return_n_plans: bool = False, half: bool = False):
     """Pointwise conv over cat(upsample2x(x_half), x_skip) with the upsample fused into the read side (fp32):

@@ -259,6 +259,13 @@ int  mi355_yolo_sparse_stats(mi355_yolo* h, long long* out10);
 int  mi355_op_conv2d(int device_id, const float* x, int n, int h, int w, int cin, const float* w_oihw,
                      const float* bias, int cout, int k, int stride, int silu, const float* residual, float* y,
                      int plan_index, int* n_plans);
+/* The 3x3 / stride 1 fp32 operator launched over the cout tiles [t0, last] of its conv alone (tiles of 16 couts, 0 < t0 < tiles): the way
+ * the engine launches the class couts of a merged cv2.i.0 + cv3.i.0 head conv in a pass that runs the sparse box branch.  The
+ * candidate plans are those the planner offers when told the sub-range's length.  y[n][h][w][cout] comes in filled by the caller: couts
+ * >= 16 * t0 are overwritten and must equal mi355_op_conv2d's, bit for bit, for every plan_index; couts < 16 * t0 must come back as they
+ * were.  tile (or NULL) receives the MI355_PLAN_TILE_FIELDS ints of the launch that ran (see mi355_plan_query_tiles). */
+int  mi355_op_conv2d_subrange(int device_id, const float* x, int n, int h, int w, int cin, const float* w_oihw, const float* bias,
+                              int cout, int silu, int t0, float* y, int plan_index, int* n_plans, int* tile);
 /* The same operator on the half=True path: x, w and residual are rounded to fp16 (nearest-even) on the way in, the
  * kernel accumulates in fp32 and rounds y to fp16 once (out_f32 = 1: y is written as fp32, as for the head's final
  * convs); y is handed back as fp32 values. */
