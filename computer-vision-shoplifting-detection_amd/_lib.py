@@ -20,7 +20,7 @@ class Mi355Error(RuntimeError):
 
 class Opts(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("batch_chunk", C.c_int), ("half", C.c_int), ("fast_act", C.c_int), ("autotune", C.c_int),
-                ("streams", C.c_int), ("flags", C.c_int), ("reserved", C.c_int), ("plan_dir", C.c_char_p), ("plan_cache_dir", C.c_char_p)]
+                ("streams", C.c_int), ("flags", C.c_int), ("obj_feats", C.c_int), ("plan_dir", C.c_char_p), ("plan_cache_dir", C.c_char_p)]
 
 
 # mi355_opts.flags (include/mi355_yolo.h)
@@ -90,6 +90,11 @@ SIGNATURES = {
     "mi355_yolo_plan_info": (C.c_int, [C.c_void_p, _P(C.c_ulonglong), _i32p, _i32p, _P(C.c_longlong), _P(C.c_longlong)]),
     "mi355_memory_plan": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_longlong),
                                     _P(C.c_longlong), C.c_int, _i32p, _P(C.c_longlong), _P(C.c_longlong)]),
+    "mi355_memory_plan_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_longlong),
+                                       _P(C.c_longlong), C.c_int, _i32p, _P(C.c_longlong), _P(C.c_longlong), _i32p]),
+    "mi355_yolo_feat_dim": (C.c_int, [C.c_void_p, _i32p]),
+    "mi355_yolo_last_feats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "mi355_op_obj_feats": (C.c_int, [C.c_int, _P(C.c_void_p), _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.c_void_p]),
     "mi355_yolo_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "mi355_yolo_last_timing": (C.c_int, [C.c_void_p, _P(Timing)]),
     "mi355_yolo_sparse_stats": (C.c_int, [C.c_void_p, _P(C.c_longlong)]),
@@ -145,6 +150,9 @@ SIGNATURES = {
     "mi355_tracker_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "mi355_tracker_destroy": (None, [C.c_void_p]),
     "mi355_tracker_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "mi355_tracker_create_ex": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mi355_tracker_update_feats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "mi355_tracker_track_feat": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "mi355_tracker_last_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "mi355_tracker_state": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _i32p]),
     "mi355_tracker_tracks": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),

@@ -259,6 +259,17 @@ struct NmsArgs {
 };
 const char* launch_nms(const NmsArgs& a, hipStream_t st);
 
+// Object features of the kept rows (post_kernels.hip): per level a channel view of an NHWC map, fp32 or fp16 (all levels alike)
+struct ObjFeatLevel { const void* base; int cs, c_off, C, H, W, anchor0; };     // base = frame 0; cs, c_off, C in elements
+struct ObjFeatArgs {
+    ObjFeatLevel lv[4]; int n_levels, half;
+    int B, cap, A, dim;             // frames, row slots per frame, anchors per frame, outputs per row = min(C_l)
+    const void* rows; int row_words, anchor_word;     // [B][cap] rows of row_words 32-bit words, anchor_idx at word anchor_word
+    const int* counts;              // [B] rows kept per frame: slots at or beyond are not written
+    float* feats;                   // [B][cap][dim]
+};
+const char* launch_obj_feats(const ObjFeatArgs& a, hipStream_t st);
+
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 #if defined(__HIPCC__)

@@ -97,11 +97,18 @@ int mi355_yolo_plan_info(const mi355_yolo* h, unsigned long long* plan_hash, int
 
 int mi355_memory_plan(const void* blob, size_t nbytes, int n, int height, int width, int imgsz, int half, int reuse, long long* offsets,
                       long long* sizes, int cap, int* n_buffers, long long* arena_bytes, long long* unshared_bytes) {
+    return mi355_memory_plan_ex(blob, nbytes, n, height, width, imgsz, half, reuse, 0, offsets, sizes, cap, n_buffers, arena_bytes,
+                                unshared_bytes, nullptr);
+}
+
+int mi355_memory_plan_ex(const void* blob, size_t nbytes, int n, int height, int width, int imgsz, int half, int reuse, int obj_feats,
+                         long long* offsets, long long* sizes, int cap, int* n_buffers, long long* arena_bytes,
+                         long long* unshared_bytes, int* detect_bufs) {
     if (!blob || n <= 0 || height <= 0 || width <= 0 || cap < 0 || (cap > 0 && (!offsets || !sizes))) return fail(MI355_EINVAL, "bad argument");
     if (imgsz <= 0) imgsz = 640;
     if (imgsz % 32) return fail(MI355_EINVAL, "imgsz must be a multiple of 32");
     mi355_yolo h;
-    h.host_only = true; h.half = half != 0;
+    h.host_only = true; h.half = half != 0; h.obj_feats = obj_feats != 0;
     const int rc = parse_blob(&h, (const uint8_t*)blob, nbytes); if (rc) return rc;
     h.mem_reuse = reuse;
     const Geometry g = make_geometry(height, width, imgsz);
@@ -111,6 +118,28 @@ int mi355_memory_plan(const void* blob, size_t nbytes, int n, int height, int wi
     for (size_t i = 0; i < off.size() && (int)i < cap; ++i) { offsets[i] = (long long)off[i]; sizes[i] = (long long)bytes[i]; }
     if (arena_bytes) *arena_bytes = (long long)arena;
     if (unshared_bytes) *unshared_bytes = (long long)plain;
+    for (int l = 0; detect_bufs && l < h.feat_levels; ++l) detect_bufs[l] = h.ops[h.feat_src[l]].src_buf;
+    return MI355_OK;
+}
+
+int mi355_yolo_feat_dim(const mi355_yolo* h, int* dim) {
+    if (!h || !dim) return fail(MI355_EINVAL, "null argument");
+    *dim = h->obj_feats ? h->feat_dim : 0;
+    return MI355_OK;
+}
+
+int mi355_yolo_last_feats(const mi355_yolo* h, float* out, int cap, int n) {
+    if (!h || !out || cap < 1) return fail(MI355_EINVAL, "bad argument");
+    if (!h->obj_feats || h->last_feat_n == 0) return fail(MI355_EINVAL, "the last infer call on this handle produced no object features");
+    if (n != h->last_feat_n) return fail(MI355_EINVAL, "n differs from the last infer call's");
+    const size_t dim = (size_t)h->feat_dim;
+    const float* src = (const float*)h->h_feats.p;
+    size_t at = 0;
+    for (int i = 0; i < n; ++i) {
+        const int cnt = std::min(h->counts_host()[i], cap);
+        std::memcpy(out + (size_t)i * cap * dim, src + (h->last_feat_packed ? at : (size_t)i * h->last_feat_max_det) * dim, (size_t)cnt * dim * sizeof(float));
+        at += (size_t)h->counts_host()[i];
+    }
     return MI355_OK;
 }
 

@@ -259,6 +259,15 @@ struct mi355_yolo {
     // NV12 / I420 frames (engine_yuv.hip): the packed planes of host frames (two chunk slots; pinned staging is h_stage), and the
     // per-frame conversion descriptors of a call with their pinned image
     Buf d_yuv, d_yuvdesc, h_yuvdesc{true};
+    // Object features (opts.obj_feats): feat_src[l] = the op whose SOURCE slice is level l's Detect input (cv2.l.0, alone
+    // or merged with its siblings), found from the program at load time (feat_levels = 0: not found); feat_dim = min over the levels'
+    // channels.  With the option on plan_memory gives those buffers bytes of their own, so the maps outlive the pass until the chunk's
+    // NMS and the gather behind it have run.  d_feats [n][max_det][dim] follows d_rows, d_feats_packed d_packed, h_feats h_rows.
+    bool obj_feats = false; int feat_levels = 0, feat_src[4] = {-1, -1, -1, -1}, feat_dim = 0;
+    Buf d_feats, d_feats_packed, h_feats{true};
+    // what mi355_yolo_last_feats hands out: the last blocking call's n and max_det, and whether h_feats holds its rows packed in frame
+    // order (counts in h_counts) or at slot i * max_det (the direct-rows path); last_feat_n = 0: the last call produced none
+    int last_feat_n = 0, last_feat_max_det = 0; bool last_feat_packed = false;
     unsigned long long plan_hash = 0;   // fingerprint of the candidate lists + the chosen indices of the current shape
     int plan_source = 0, plan_launches = 0;   // 0 static guess (autotune off), 1 memory, 2 this machine's plan cache, 3 tuned now, 4 shipped plan file; launches of one pass (stem..last conv)
     bool async_pending = false;         // mi355_yolo_infer_device_async work may still be in flight on `stream`
@@ -303,6 +312,7 @@ int parse_blob(mi355_yolo* h, const uint8_t* blob, size_t n);
 int create_impl(const uint8_t* blob, size_t nbytes, int device_id, const mi355_opts* opts, mi355_yolo** out);
 // engine_run.hip: the sparse box branch: program analysis (at load), per-shape launches, statistics
 void detect_sparse_head(mi355_yolo* h);
+void detect_feature_sources(mi355_yolo* h);                       // the three Detect-input slices (object features)
 bool sparse_wanted(const mi355_yolo* h, int nb);
 int prepare_sparse_shape(mi355_yolo* h, int nb, int Hl, int Wl);
 ConvLaunch cout_subrange(const ConvLaunch& l0, int t0, int nt);   // a planned 3x3 launch over the cout tiles [t0, t0 + nt) of its conv

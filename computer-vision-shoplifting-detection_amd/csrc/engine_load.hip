@@ -29,7 +29,7 @@ mi355_yolo::~mi355_yolo() {
     if (zeros) (void)hipFree(zeros);
     if (sp_state) (void)hipFree(sp_state); if (h_sp) (void)hipHostFree(h_sp);
     for (Buf* b : {&sp_lists, &d_in, &d_rows, &d_counts, &d_packed, &d_offsets, &h_rows, &h_counts, &d_cmask, &h_cmask, &d_xtab, &d_ytab,
-                   &d_rawhead, &h_stage, &d_multi, &h_multi, &d_yuv, &d_yuvdesc, &h_yuvdesc}) buf_free(*b);
+                   &d_rawhead, &h_stage, &d_multi, &h_multi, &d_yuv, &d_yuvdesc, &h_yuvdesc, &d_feats, &d_feats_packed, &h_feats}) buf_free(*b);
     if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1);
     for (auto e : pev) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) { if (ev_copied[i]) (void)hipEventDestroy(ev_copied[i]); if (ev_consumed[i]) (void)hipEventDestroy(ev_consumed[i]); }
@@ -248,6 +248,10 @@ int parse_blob(mi355_yolo* h, const uint8_t* blob, size_t n) {
     if (const char* e = getenv("MI355_MEM_REUSE")) h->mem_reuse = atoi(e);
     if (const char* e = getenv("MI355_GROUP_MAX_BATCH")) h->group_max_batch = atoi(e);
     detect_sparse_head(h);
+    detect_feature_sources(h);
+    if (h->obj_feats && h->feat_levels == 0)
+        return fail(MI355_EFORMAT, "obj_feats: the program's Detect-input slices were not found (cv2.i.2 <- cv2.i.1 <- cv2.i.0), or their "
+                                   "channel counts are not multiples of the smallest");
     return build_schedule(h);
 }
 
@@ -343,6 +347,7 @@ int create_impl(const uint8_t* blob, size_t nbytes, int device_id, const mi355_o
     if (MI355_HAS(autotune) && opts->autotune != 0) h->autotune = std::max(0, opts->autotune);
     if (MI355_HAS(streams) && opts->streams > 0) h->n_streams = std::min(8, opts->streams);
     if (MI355_HAS(flags)) h->opt_flags = opts->flags;
+    if (MI355_HAS(obj_feats)) h->obj_feats = opts->obj_feats != 0;
     if (MI355_HAS(plan_dir) && opts->plan_dir) h->plan_dir = opts->plan_dir;
     if (const char* home = getenv("HOME")) h->plan_cache_dir = std::string(home) + "/.cache/mi355yolo"; else h->plan_cache_dir = "/tmp/mi355yolo";
     if (MI355_HAS(plan_cache_dir) && opts->plan_cache_dir) { h->plan_cache_dir = opts->plan_cache_dir; h->plan_cache_on = !h->plan_cache_dir.empty(); }

@@ -26,6 +26,8 @@ void plan_memory(mi355_yolo* h, int nb, int Hl, int Wl, std::vector<size_t>* off
         // channels (cs > channels: zeroed once here, read -- times zero weights -- by the convs' padded k-blocks, never
         // written: another tensor's bits there could be NaN patterns)
         pinned[i] = is_head || cs != (int)h->bufs[i].channels || !h->mem_reuse;
+        // ... and, with object features, the Detect-input maps: the gather reads them behind the chunk's NMS, after the last op
+        for (int l = 0; h->obj_feats && l < h->feat_levels; ++l) pinned[i] |= h->ops[h->feat_src[l]].src_buf == (int)i;
     }
     // ---- liveness-based placement.  A buffer's users = every op that reads or writes any of its channels (a conv that may
     // read an upsample's SOURCE directly counts as a user of that source).  Buffer b may take bytes of buffer a iff EVERY

@@ -190,6 +190,55 @@ int mi355_op_decode(int device_id, const float* const* bufs, const int* geom, in
     return MI355_OK;
 }
 
+// The object-feature gather as a chunk enqueues it behind NMS (engine_run.hip:run_chunks), on rows that hold the caller's anchor_idx.
+int mi355_op_obj_feats(int device_id, const void* const* bufs, const int* geom, int n_levels, int n, int half, const int* anchor_idx,
+                       const int* counts, int cap, int dim, float* feats) {
+    if (!bufs || !geom || !anchor_idx || !counts || !feats || n <= 0 || cap <= 0 || dim <= 0) return fail(MI355_EINVAL, "bad argument");
+    if (n_levels < 1 || n_levels > 4) return fail(MI355_EINVAL, "obj_feats takes 1 to 4 levels");
+    const int es = half ? 2 : 4, align = half ? 8 : 4;
+    ObjFeatArgs a{};
+    long anchors = 0; int cmin = 1 << 30;
+    for (int l = 0; l < n_levels; ++l) {
+        const int* g = geom + 5 * l;           // cs, c_off, C, h, w
+        if (!bufs[l] || g[0] <= 0 || g[1] < 0 || g[2] <= 0 || g[1] + g[2] > g[0] || g[3] <= 0 || g[4] <= 0) return fail(MI355_EINVAL, "bad level");
+        if ((g[0] % align) || (g[1] % align)) return fail(MI355_EINVAL, "a level's cs and c_off must be multiples of 4 (fp32) or 8 (fp16)");
+        if (g[2] % dim) return fail(MI355_EINVAL, "dim must divide every level's channel count");
+        if ((long)g[3] * g[4] * g[0] >= (1l << 31)) return fail(MI355_EINVAL, "a frame's map exceeds 32-bit offsets");
+        a.lv[l] = ObjFeatLevel{nullptr, g[0], g[1], g[2], g[3], g[4], (int)anchors};
+        anchors += (long)g[3] * g[4]; cmin = std::min(cmin, g[2]);
+    }
+    if (cmin != dim) return fail(MI355_EINVAL, "dim must be the smallest level's channel count");
+    if (anchors >= (1l << 31) || (long)n * cap >= (1l << 28) || (long)cap * dim >= (1l << 31)) return fail(MI355_EINVAL, "too many anchors or rows");
+    for (int i = 0; i < n; ++i) {
+        if (counts[i] < 0 || counts[i] > cap) return fail(MI355_EINVAL, "counts must lie in 0 .. cap");
+        for (int r = 0; r < counts[i]; ++r)
+            if (anchor_idx[(size_t)i * cap + r] < 0 || anchor_idx[(size_t)i * cap + r] >= anchors) return fail(MI355_EINVAL, "anchor_idx outside 0 .. A-1");
+    }
+    HIPCHK(hipSetDevice(device_id));
+    DevMem dm;
+    for (int l = 0; l < n_levels; ++l) {
+        char* d_buf;
+        const size_t bytes = (size_t)n * a.lv[l].H * a.lv[l].W * a.lv[l].cs * es;
+        HIPCHK(dm.alloc(&d_buf, bytes)); HIPCHK(hipMemcpy(d_buf, bufs[l], bytes, hipMemcpyHostToDevice));
+        a.lv[l].base = d_buf;
+    }
+    std::vector<mi355_det> rows((size_t)n * cap);
+    std::memset(rows.data(), 0, rows.size() * sizeof(mi355_det));
+    for (size_t i = 0; i < rows.size(); ++i) rows[i].anchor_idx = anchor_idx[i];
+    mi355_det* d_rows; int* d_counts; float* d_feats;
+    const size_t fn = (size_t)n * cap * dim;
+    HIPCHK(dm.alloc(&d_rows, rows.size() * sizeof(mi355_det))); HIPCHK(hipMemcpy(d_rows, rows.data(), rows.size() * sizeof(mi355_det), hipMemcpyHostToDevice));
+    HIPCHK(dm.alloc(&d_counts, (size_t)n * 4)); HIPCHK(hipMemcpy(d_counts, counts, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(dm.alloc(&d_feats, fn * 4)); HIPCHK(hipMemcpy(d_feats, feats, fn * 4, hipMemcpyHostToDevice));
+    a.n_levels = n_levels; a.half = half ? 1 : 0; a.B = n; a.cap = cap; a.A = (int)anchors; a.dim = dim;
+    a.rows = d_rows; a.row_words = (int)(sizeof(mi355_det) / 4); a.anchor_word = (int)(offsetof(mi355_det, anchor_idx) / 4);
+    a.counts = d_counts; a.feats = d_feats;
+    KCHK(launch_obj_feats(a, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(feats, d_feats, fn * 4, hipMemcpyDeviceToHost));
+    return MI355_OK;
+}
+
 // The sparse tail of a pass without its dense launches (engine_run.hip:launch_net): state zeroed, launch_sparse_lists,
 // launch_sparse_box.  ptrs: 10 per level, geom: 11 per level (include/mi355_yolo.h).
 int mi355_op_sparse_box(int device_id, void* const* ptrs, const int* geom, int n_levels, int n, const float* best, float conf,

@@ -46,6 +46,38 @@ void detect_sparse_head(mi355_yolo* h) {
     }
 }
 
+// ---- object features: the op that reads each level's Detect input.  From the level's box-logit writer (cv2.i.2: the pointwise conv
+// that fills the 4 * reg_max channels at box_off) back through cv2.i.1 (the 3x3 conv that writes exactly its input slice) to cv2.i.0
+// (the 3x3 conv whose output slice BEGINS with cv2.i.1's input: alone, or merged with cv3.i.0 / cv4.i.0 behind it).  Program
+// structure only: which of these run fused or grouped does not matter.  That op's source slice is the map Ultralytics' pre-hook sees.
+void detect_feature_sources(mi355_yolo* h) {
+    h->feat_levels = 0; h->feat_dim = 0;
+    if (h->levels.empty() || h->levels.size() > 4) return;
+    const int n = (int)h->ops.size(), box_c = 4 * (int)h->hdr.reg_max;
+    auto conv_op = [&](int i, int k) { const FileOp& o = h->ops[i]; return o.type == OP_CONV && (int)h->convs[o.conv].k == k && h->convs[o.conv].s == 1 && o.res_buf < 0; };
+    int src[4], dim = 1 << 30;
+    for (size_t l = 0; l < h->levels.size(); ++l) {
+        const FileLevel& lv = h->levels[l];
+        int b2 = -1, b1 = -1, m = -1;
+        for (int i = 0; i < n; ++i)
+            if (conv_op(i, 1) && h->ops[i].dst_buf == (int)lv.buf && h->ops[i].dst_choff == (int)lv.box_off && h->ops[i].dst_c == box_c) b2 = i;
+        if (b2 < 0) return;
+        const FileOp& o2 = h->ops[b2];
+        for (int i = 0; i < n; ++i)
+            if (conv_op(i, 3) && h->ops[i].dst_buf == o2.src_buf && h->ops[i].dst_choff == o2.src_choff && h->ops[i].dst_c == o2.src_c) b1 = i;
+        if (b1 < 0) return;
+        const FileOp& o1 = h->ops[b1];
+        for (int i = 0; i < n; ++i)
+            if (conv_op(i, 3) && h->ops[i].dst_buf == o1.src_buf && h->ops[i].dst_choff == o1.src_choff && h->ops[i].dst_c >= o1.src_c) m = i;
+        if (m < 0) return;
+        src[l] = m;
+        dim = std::min(dim, h->ops[m].src_c);
+    }
+    for (size_t l = 0; l < h->levels.size(); ++l) if (dim < 1 || h->ops[src[l]].src_c % dim) return;
+    h->feat_levels = (int)h->levels.size(); h->feat_dim = dim;
+    for (int l = 0; l < h->feat_levels; ++l) h->feat_src[l] = src[l];
+}
+
 bool sparse_wanted(const mi355_yolo* h, int nb) {
     if (h->sp_levels <= 0 || h->half || h->use_graph) return false;
     if (const char* e = getenv("MI355_SPARSE_BOX")) return atoi(e) != 0;
@@ -392,7 +424,9 @@ struct CallState {
     size_t frame_bytes = 0, slot_bytes = 0;     // one dense frame (single shape); one staging slot = one chunk of host frames
     const unsigned* cmask = nullptr;
     bool single_chunk = false, direct_host = false, sp_adaptive = false;
+    bool feats = false;                 // this call produces object features (opts.obj_feats, a blocking form)
     mi355_det* host_rows_dev = nullptr; int* host_counts_dev = nullptr;     // the pinned host buffers as the NMS kernel sees them
+    float* host_feats_dev = nullptr;    // ... and the gather kernel (direct rows)
 };
 
 // step 1: the arguments, checked and defaulted in the order the ABI documents
@@ -455,6 +489,10 @@ static int grow_scratch(mi355_yolo* h, const CallState& s) {
     GROW(h->d_offsets, (n + 1) * sizeof(int));
     if (!s.async_out) GROW(h->h_rows, rows);
     GROW(h->h_counts, n * sizeof(int));
+    if (s.feats) {                      // the features follow the rows: slots on the device, packed copy, pinned host copy
+        const size_t fb = n * s.c.max_det * h->feat_dim * sizeof(float);
+        GROW(h->d_feats, fb); GROW(h->d_feats_packed, fb); GROW(h->h_feats, fb);
+    }
     return MI355_OK;
 }
 
@@ -559,8 +597,39 @@ static int run_chunks(mi355_yolo* h, const CallState& s, Prof& pf) {
         if (pf.begin(K_NMS)) return fail(MI355_EHIP, "event");
         KCHK(launch_nms(na, h->stream));
         if (!s.single_chunk) HIPCHK(hipMemcpyAsync(h->counts_dev() + s0, na.out_counts, (size_t)m * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+        if (s.feats) {
+            // the kept rows' embeddings, while this chunk's Detect-input maps are still in the arena: the next chunk's pass is enqueued
+            // behind this launch.  Rows and counts are read where NMS has just written them (direct rows: the pinned host block).
+            ObjFeatArgs fa{};
+            fa.n_levels = h->feat_levels; fa.half = h->half ? 1 : 0;
+            fa.B = m; fa.cap = c.max_det; fa.A = h->A; fa.dim = h->feat_dim;
+            int a0 = 0;
+            for (int l = 0; l < h->feat_levels; ++l) {
+                const FileOp& o = h->ops[h->feat_src[l]];
+                const int sd = h->bufs[o.src_buf].stride_div, H = h->cur_H / sd, W = h->cur_W / sd;
+                fa.lv[l] = ObjFeatLevel{h->dbuf[o.src_buf], h->dbuf_cs[o.src_buf], o.src_choff, o.src_c, H, W, a0};
+                a0 += H * W;
+            }
+            fa.rows = na.out_rows; fa.row_words = (int)(sizeof(mi355_det) / 4); fa.anchor_word = (int)(offsetof(mi355_det, anchor_idx) / 4);
+            fa.counts = na.out_counts;
+            fa.feats = (s.direct_host ? s.host_feats_dev : (float*)h->d_feats.p) + (size_t)s0 * c.max_det * h->feat_dim;
+            KCHK(launch_obj_feats(fa, h->stream));
+        }
         pf.end();
     }
+    return MI355_OK;
+}
+
+// step 7, host forms: the features beside the rows.  Direct rows: the gather wrote h_feats at slot i * max_det, nothing is left to do.
+// Otherwise the slots are compacted with the rows' offsets and sum(counts) rows of them copied (one more wait: large calls only).
+static int fetch_feats(mi355_yolo* h, const CallState& s, size_t total) {
+    const InferCall& c = s.c;
+    if (!s.direct_host && total) {
+        KCHK(launch_compact_rows(h->d_feats.p, h->counts_dev(), c.n, c.max_det, h->feat_dim, (int*)h->d_offsets.p, h->d_feats_packed.p, h->stream));
+        HIPCHK(hipMemcpyAsync(h->h_feats.p, h->d_feats_packed.p, total * h->feat_dim * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    h->last_feat_n = c.n; h->last_feat_max_det = c.max_det; h->last_feat_packed = !s.direct_host;
     return MI355_OK;
 }
 
@@ -584,6 +653,8 @@ int infer_impl(mi355_yolo* h, const InferCall& call) {
         HIPCHK(hipStreamSynchronize(h->stream));
         h->async_pending = false;
     }
+    h->last_feat_n = 0;                 // until this call has produced its features
+    s.feats = h->obj_feats && !s.async_out;
     rc = call_shape(h, s); if (rc) return rc;
     if (!c.on_device || c.yuv) GROW(h->d_in, 2 * s.slot_bytes);     // host frames / converted YUV frames: a double-buffered staging area of two chunks
     if (c.yuv) { rc = yuv_upload(h, c.yuv, c.on_device, c.n, s.nb, s.slot_bytes, s.yc); if (rc) return rc; }
@@ -603,6 +674,7 @@ int infer_impl(mi355_yolo* h, const InferCall& call) {
     if (s.direct_host) {                // taken after the growth: the device view of the pinned blocks as they are now
         HIPCHK(hipHostGetDevicePointer((void**)&s.host_rows_dev, h->h_rows.p, 0));
         HIPCHK(hipHostGetDevicePointer((void**)&s.host_counts_dev, h->h_counts.p, 0));
+        if (s.feats) HIPCHK(hipHostGetDevicePointer((void**)&s.host_feats_dev, h->h_feats.p, 0));
     }
     rc = sparse_feedback_before(h, s); if (rc) return rc;
     Prof pf{h};
@@ -621,6 +693,7 @@ int infer_impl(mi355_yolo* h, const InferCall& call) {
     if (s.direct_host) {
         HIPCHK(hipStreamSynchronize(h->stream));
         copy_out(h, c, false);
+        if (s.feats) { rc = fetch_feats(h, s, 0); if (rc) return rc; }
         return sparse_feedback_after(h, s, pf);
     }
     // rows -> host: compact on the GPU first (a frame keeps counts[i] of its max_det slots; copying the slots would be 35 MB
@@ -641,6 +714,7 @@ int infer_impl(mi355_yolo* h, const InferCall& call) {
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     copy_out(h, c, true);
+    if (s.feats) { rc = fetch_feats(h, s, total); if (rc) return rc; }
     return sparse_feedback_after(h, s, pf);
 }
 

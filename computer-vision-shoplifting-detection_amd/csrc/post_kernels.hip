@@ -603,4 +603,89 @@ const char* launch_compact_rows(const void* rows, const int* counts, int n, int 
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 
+// ---------------------------------------------------------------------------------------------- object features
+// Ultralytics' DetectionPredictor.get_obj_feats (with_reid, model: auto) for the rows NMS kept: the Detect head's input maps read at
+// the anchor each row came from.  s = min(C_l) = dim; a row on level l (g = C_l / s) gets e[j] = mean(x[a, j*g .. j*g + g - 1]),
+// j = 0 .. s-1, in the canonical order acc = x[0]; acc += x[r] for ascending r; e = acc / (float)g (IEEE division; g == 1 copies
+// the bits).  fp16 maps are widened to fp32 first.
+// ONE WAVE PER ROW SLOT (the grid covers B * cap slots; a wave whose slot is at or beyond counts[b] leaves without a store): the
+// row's anchor_idx, hence its level and pixel, are the same for all lanes and live in scalar registers; in NHWC the pixel's C_l
+// channels are one contiguous run, lane j reads the g channels of outputs j, j + 64, ... in one load where g allows it (16 bytes for
+// g = 4, 8 for g = 2 in fp32; half that in fp16) and the 64 lanes store 256 contiguous bytes.  A frame's offsets fit 32 bits (the
+// launcher checks); the frame base is 64-bit.
+typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+
+template <bool HALF, int G>
+__device__ __forceinline__ float obj_feat_group(const void* frame, unsigned at, int g) {
+    float x[4];
+    if (HALF) {
+        const _Float16* p = (const _Float16*)frame + at;
+        if (G == 4) { const half4_t v = *(const half4_t*)p; x[0] = (float)v.x; x[1] = (float)v.y; x[2] = (float)v.z; x[3] = (float)v.w; }
+        else if (G == 2) { const half2_t v = *(const half2_t*)p; x[0] = (float)v.x; x[1] = (float)v.y; }
+        else if (G == 0) { float acc = (float)p[0]; for (int r = 1; r < g; ++r) acc += (float)p[r]; return acc / (float)g; }
+        else { for (int r = 0; r < G; ++r) x[r] = (float)p[r]; }
+    } else {
+        const float* p = (const float*)frame + at;
+        if (G == 4) { const float4 v = *(const float4*)p; x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
+        else if (G == 2) { const float2 v = *(const float2*)p; x[0] = v.x; x[1] = v.y; }
+        else if (G == 0) { float acc = p[0]; for (int r = 1; r < g; ++r) acc += p[r]; return acc / (float)g; }
+        else { for (int r = 0; r < G; ++r) x[r] = p[r]; }
+    }
+    if (G == 1) return x[0];
+    float acc = x[0];
+    for (int r = 1; r < G; ++r) acc += x[r];
+    return acc / (float)G;
+}
+
+template <bool HALF>
+__global__ __launch_bounds__(256) void obj_feats_kernel(ObjFeatArgs a) {
+    const int slot = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));     // wave-uniform from here on
+    const int lane = threadIdx.x & 63;
+    if (slot >= a.B * a.cap) return;
+    const int b = slot / a.cap, r = slot - b * a.cap;
+    if (r >= a.counts[b]) return;
+    const int anchor = __builtin_amdgcn_readfirstlane(((const int*)a.rows)[((size_t)b * a.cap + r) * a.row_words + a.anchor_word]);
+    if (anchor < 0 || anchor >= a.A) return;                      // never a row NMS wrote; an index outside the maps is not followed
+    ObjFeatLevel L = a.lv[0];                                    // the level the anchor lies on: scalar selects over constant indices
+#pragma unroll
+    for (int i = 1; i < 4; ++i) if (i < a.n_levels && anchor >= a.lv[i].anchor0) L = a.lv[i];
+    const int g = L.C / a.dim;
+    const void* frame = (const char*)L.base + (size_t)b * L.H * L.W * L.cs * (HALF ? 2 : 4);
+    const unsigned px = (unsigned)(anchor - L.anchor0) * (unsigned)L.cs + (unsigned)L.c_off;
+    float* out = a.feats + ((size_t)b * a.cap + r) * a.dim;
+    for (int o = lane; o < a.dim; o += 64) {
+        const unsigned at = px + (unsigned)(o * g);
+        float e;
+        switch (g) {
+            case 1: e = obj_feat_group<HALF, 1>(frame, at, g); break;
+            case 2: e = obj_feat_group<HALF, 2>(frame, at, g); break;
+            case 3: e = obj_feat_group<HALF, 3>(frame, at, g); break;
+            case 4: e = obj_feat_group<HALF, 4>(frame, at, g); break;
+            default: e = obj_feat_group<HALF, 0>(frame, at, g); break;
+        }
+        out[o] = e;
+    }
+}
+
+const char* launch_obj_feats(const ObjFeatArgs& a, hipStream_t st) {
+    if (a.n_levels < 1 || a.n_levels > 4 || a.B < 1 || a.cap < 1 || a.dim < 1) return "obj_feats: bad shape";
+    const int align = a.half ? 8 : 4;                             // elements: what the 8- and 16-byte loads need
+    long anchors = 0;
+    for (int l = 0; l < a.n_levels; ++l) {
+        const ObjFeatLevel& L = a.lv[l];
+        if (!L.base || L.C < a.dim || L.C % a.dim || L.c_off < 0 || L.c_off + L.C > L.cs || L.H < 1 || L.W < 1) return "obj_feats: bad level";
+        if ((L.cs % align) || (L.c_off % align) || ((uintptr_t)L.base % 16)) return "obj_feats: a level's stride, offset or base is not aligned for vector loads";
+        if ((long)L.H * L.W * L.cs >= (1l << 31)) return "obj_feats: a frame's map exceeds 32-bit offsets";
+        if (L.anchor0 != (int)anchors) return "obj_feats: level starts do not follow the anchor order";
+        anchors += (long)L.H * L.W;
+    }
+    if (anchors != a.A || (long)a.cap * a.dim >= (1l << 31) || (long)a.B * a.cap >= (1l << 31) - 4) return "obj_feats: bad anchor count or row capacity";
+    const unsigned blocks = (unsigned)(((long)a.B * a.cap + 3) / 4);
+    if (a.half) hipLaunchKernelGGL(obj_feats_kernel<true>, dim3(blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(obj_feats_kernel<false>, dim3(blocks), dim3(256), 0, st, a);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
 }  // namespace mi355

@@ -8,6 +8,10 @@
 // as in the reference -- but as compiled code behind the C ABI instead of 0.3 ms of numpy per frame, which made the tracker, not
 // the detector, the bottleneck of the reference's frame loop.
 //
+// BoT-SORT's appearance half (with_reid: True, model: auto; BOTrack.update_features, BOTSORT.get_dists, embedding_distance) runs
+// on the features the detector hands over (mi355_tracker_create_ex / mi355_tracker_update_feats); its checker is
+// tests/_botsort_reid_numpy.py, the oracle below plus the feature bookkeeping in the same stated arithmetic orders.
+//
 // The checker is oracle/tracker_oracle.py (numpy, the round-2/3 implementation with a pure-Python statement of the same
 // assignment algorithm); tests compare ids exactly and boxes to float32 rounding.  PARITY UNPINNED against a real Ultralytics /
 // lap run (neither is installable here); the published algorithms are restated: ByteTrack (Zhang et al., ECCV 2022), BoT-SORT
@@ -303,9 +307,10 @@ struct Kalman {
 };
 
 // ------------------------------------------------------------------------------------------------ tracker
-struct Det { double xywh[4]; double score, cls, idx; };
+struct Det { double xywh[4]; double score, cls, idx; const float* feat = nullptr; };      // feat: this detection's curr_feat (unit length), or null
 struct Track {
     int id; double mean[8]; double cov[64]; double score, cls, idx; int state; bool confirmed; int born, seen;
+    std::vector<float> smooth;               // BOTrack.smooth_feat; empty until the track has absorbed a detection that carried a feature
 };
 typedef std::shared_ptr<Track> TP;
 
@@ -322,9 +327,37 @@ inline float iou_cost(const float* a, const float* b) {
     return 1.0f - inter / (((area_a + area_b) - inter) + 1e-7f);
 }
 
+// ---- appearance (BOTrack.update_features, matching.py:embedding_distance).  The reductions are fixed here, as the IoU's operation
+// order is above: ascending index, the fp32 values widened to float64 (every product is then exact), a float64 accumulator.
+constexpr float kAlpha = 0.9f, kOneMinusAlpha = (float)(1.0 - 0.9);      // BOTrack.alpha; numpy multiplies a float32 array by them as float32
+
+inline double sum_sq(const float* f, int dim) {
+    double acc = 0.0;
+    for (int i = 0; i < dim; ++i) acc += (double)f[i] * (double)f[i];
+    return acc;
+}
+// f / ||f|| in fp32, the norm rounded to fp32 once; a zero-norm vector stays zeros (numpy would produce NaN: the stated deviation)
+inline void unit_length(const float* f, int dim, float* out) {
+    const float norm = (float)std::sqrt(sum_sq(f, dim));
+    for (int i = 0; i < dim; ++i) out[i] = norm > 0.0f ? f[i] / norm : f[i];
+}
+// max(0, cosine distance) / 2 in float64, na / nb = sum_sq of the two vectors (taken once per track and per detection: the same
+// values whichever pair asks); 1 when either vector is missing or has no length
+inline double embedding_cost(const float* a, double na, const float* b, double nb, int dim) {
+    if (!a || !b || na == 0.0 || nb == 0.0) return 1.0;
+    double dot = 0.0;
+    for (int i = 0; i < dim; ++i) dot += (double)a[i] * (double)b[i];
+    const double d = 1.0 - dot / (std::sqrt(na) * std::sqrt(nb));
+    return std::max(0.0, d) / 2.0;
+}
+
 }  // namespace
 
 struct mi355_tracker {
+    // BoT-SORT's appearance half (botsort.yaml with_reid / proximity_thresh / appearance_thresh); off: everything below is never read
+    bool with_reid = false; int feat_dim = 0; double proximity = 0.5, appearance = 0.8;
+    std::vector<float> curr;                 // this frame's curr_feat per det row [n][feat_dim]
+    bool reid_now = false;                   // this update was handed features
     int frame_id = 0, max_time_lost = kTrackBuffer, ids_issued = 0;
     std::vector<TP> live, lost;
     std::vector<int> retired_ids;            // ids retired on EARLIER frames (sorted)
@@ -334,6 +367,8 @@ struct mi355_tracker {
     bool retired(int id) const { return std::binary_search(retired_ids.begin(), retired_ids.end(), id); }
 
     // cost matrix [tracks][dets] (double): IoU cost in fp32, fused with the detection score when asked (matching.py:fuse_score)
+    // With features (BOTSORT.get_dists, the stages that fuse): the gate mask is taken on the plain IoU cost before the fusion, the
+    // embedding cost is 1 beyond either gate, and the smaller of the two costs is kept.
     void costs(const std::vector<TP>& tr, const std::vector<Det>& dets, bool fuse) {
         cost.assign(tr.size() * dets.size(), 0.0);
         std::vector<float> db(dets.size() * 4);
@@ -342,12 +377,24 @@ struct mi355_tracker {
             const double m[4] = {z[0], z[1], z[2], z[3]};
             xyxy_of(m, &db[j * 4]);
         }
+        const bool reid = fuse && reid_now;
+        std::vector<double> det_ss(reid ? dets.size() : 0);
+        for (size_t j = 0; j < det_ss.size(); ++j) det_ss[j] = dets[j].feat ? sum_sq(dets[j].feat, feat_dim) : 0.0;
         for (size_t i = 0; i < tr.size(); ++i) {
             float tb[4];
             xyxy_of(tr[i]->mean, tb);
+            const float* sm = reid && !tr[i]->smooth.empty() ? tr[i]->smooth.data() : nullptr;
+            const double sm_ss = sm ? sum_sq(sm, feat_dim) : 0.0;
             for (size_t j = 0; j < dets.size(); ++j) {
                 const float c = iou_cost(tb, &db[j * 4]);
-                cost[i * dets.size() + j] = fuse ? 1.0 - (double)(1.0f - c) * dets[j].score : (double)c;
+                double d = fuse ? 1.0 - (double)(1.0f - c) * dets[j].score : (double)c;
+                if (reid) {
+                    // beyond the proximity gate the embedding cost is 1 whatever the vectors say: the dot product is not taken
+                    double emb = c > (float)(1.0 - proximity) ? 1.0 : embedding_cost(sm, sm_ss, dets[j].feat, det_ss[j], feat_dim);
+                    if (emb > 1.0 - appearance) emb = 1.0;
+                    d = std::min(d, emb);
+                }
+                cost[i * dets.size() + j] = d;
             }
         }
     }
@@ -359,9 +406,22 @@ struct mi355_tracker {
         for (size_t j = 0; j < nc; ++j) if (y[j] < 0) free_c->push_back((int)j);
     }
 
-    int update(const float* det, int n, const double* H, float* out, int cap) {
+    // BOTrack.update_features: smooth_feat = the first curr_feat, then 0.9 * smooth + 0.1 * curr in fp32, brought back to unit length
+    void absorb_feature(Track& t, const Det& d) const {
+        if (!d.feat) return;
+        if (t.smooth.empty()) { t.smooth.assign(d.feat, d.feat + feat_dim); return; }
+        for (int i = 0; i < feat_dim; ++i) t.smooth[i] = kAlpha * t.smooth[i] + kOneMinusAlpha * d.feat[i];
+        unit_length(t.smooth.data(), feat_dim, t.smooth.data());
+    }
+
+    int update(const float* det, int n, const double* H, float* out, int cap, const float* feats = nullptr) {
         ++frame_id;
         const int frame = frame_id;
+        reid_now = with_reid && feats != nullptr;
+        if (reid_now) {
+            curr.resize((size_t)n * feat_dim);
+            for (int i = 0; i < n; ++i) unit_length(feats + (size_t)i * feat_dim, feat_dim, &curr[(size_t)i * feat_dim]);
+        }
         std::vector<Det> strong, weak;
         for (int i = 0; i < n; ++i) {
             const float* r = det + (size_t)i * 6;
@@ -374,6 +434,7 @@ struct mi355_tracker {
             d.xywh[0] = (double)(float)((x1 + x2) / 2); d.xywh[1] = (double)(float)((y1 + y2) / 2);
             d.xywh[2] = (double)(float)(x2 - x1); d.xywh[3] = (double)(float)(y2 - y1);
             d.score = s; d.cls = (double)r[5]; d.idx = (double)i;
+            if (reid_now) d.feat = &curr[(size_t)i * feat_dim];
             (hi ? strong : weak).push_back(d);
         }
         std::vector<TP> confirmed, tentative, pool;
@@ -398,6 +459,7 @@ struct mi355_tracker {
         std::vector<TP> touched, revived, newly_lost, retired_now;
         auto absorb = [&](const TP& t, const Det& d) {
             Kalman::update(t->mean, t->cov, d.xywh);
+            absorb_feature(*t, d);
             t->score = d.score; t->cls = d.cls; t->idx = d.idx;
             t->state = TRACKED; t->confirmed = true; t->seen = frame;
         };
@@ -434,6 +496,7 @@ struct mi355_tracker {
             TP t = std::make_shared<Track>();
             t->id = ++ids_issued;
             Kalman::initiate(d.xywh, t->mean, t->cov);
+            absorb_feature(*t, d);
             t->score = d.score; t->cls = d.cls; t->idx = d.idx; t->state = TRACKED; t->confirmed = frame == 1; t->born = t->seen = frame;
             touched.push_back(t);
         }
@@ -511,6 +574,46 @@ void mi355_tracker_destroy(mi355_tracker* t) { delete t; }
 int mi355_tracker_update(mi355_tracker* t, const float* det, int n, const double* warp, float* out_rows, int cap) {
     if (!t || n < 0 || (n > 0 && !det) || cap < 0 || (cap > 0 && !out_rows)) return -1;
     return t->update(det, n, warp, out_rows, cap);
+}
+
+int mi355_tracker_create_ex(int frame_rate, const mi355_tracker_cfg* cfg, mi355_tracker** out) {
+    if (!out) return -1;
+    *out = nullptr;
+    if (cfg && cfg->struct_size < (int)sizeof(mi355_tracker_cfg)) return -1;
+    if (cfg && (cfg->feat_dim < 0 || cfg->proximity_thresh < 0.0 || cfg->proximity_thresh > 1.0 || cfg->appearance_thresh < 0.0 ||
+                cfg->appearance_thresh > 1.0)) return -1;
+    mi355_tracker* t = nullptr;
+    if (mi355_tracker_create(frame_rate, &t) != 0) return -1;
+    if (cfg) {
+        t->with_reid = cfg->with_reid != 0; t->feat_dim = cfg->feat_dim;
+        if (cfg->proximity_thresh > 0.0) t->proximity = cfg->proximity_thresh;
+        if (cfg->appearance_thresh > 0.0) t->appearance = cfg->appearance_thresh;
+    }
+    *out = t;
+    return 0;
+}
+
+int mi355_tracker_update_feats(mi355_tracker* t, const float* det, int n, const float* feats, int dim, const double* warp, float* out_rows,
+                               int cap) {
+    if (!t || n < 0 || (n > 0 && !det) || cap < 0 || (cap > 0 && !out_rows)) return -1;
+    if (feats && t->with_reid) {
+        if (dim <= 0 || (t->feat_dim > 0 && dim != t->feat_dim)) return -1;
+        t->feat_dim = dim;                   // feat_dim 0 at creation: the first call with features fixes it
+    }
+    return t->update(det, n, warp, out_rows, cap, feats);
+}
+
+int mi355_tracker_track_feat(const mi355_tracker* t, int track_id, float* smooth_out, int dim) {
+    if (!t || dim < 0 || (dim > 0 && !smooth_out)) return -1;
+    for (const std::vector<TP>* v : {&t->live, &t->lost})
+        for (const TP& p : *v)
+            if (p->id == track_id) {
+                const int m = (int)p->smooth.size();
+                if (m > dim) return -1;
+                if (m) std::memcpy(smooth_out, p->smooth.data(), (size_t)m * sizeof(float));
+                return m;
+            }
+    return -1;
 }
 
 int mi355_tracker_last_rows(const mi355_tracker* t, float* out_rows, int cap) {

@@ -49,13 +49,19 @@ class YOLO:
 
     def __init__(self, model: Union[str, bytes, os.PathLike], task: Optional[str] = None, device: int = 0,
                  batch_chunk: int = 0, verbose: bool = False, half: bool = False, fast_act: bool = False, autotune: int = 0,
-                 streams: int = 0, flags: int = 0, plan_dir: Optional[str] = None, plan_cache_dir: Optional[str] = None):
+                 streams: int = 0, flags: int = 0, plan_dir: Optional[str] = None, plan_cache_dir: Optional[str] = None,
+                 feats: bool = False):
         """Engine options are ``mi355_opts`` (include/mi355_yolo.h): ``fast_act`` = the v_exp / v_rcp SiLU on the fp32 path (tolerance
         mode; the default is the canonical, bit-reproducible arithmetic), ``autotune`` / ``streams`` / ``flags`` (``_lib.OPT_*``) as the
         header documents them, ``plan_dir`` = directory of shipped launch-plan files (default: the package's ``plans/``; "" = none),
-        ``plan_cache_dir`` = where freshly timed choices are kept (default ~/.cache/mi355yolo; "" = not persisted)."""
+        ``plan_cache_dir`` = where freshly timed choices are kept (default ~/.cache/mi355yolo; "" = not persisted).
+        ``feats`` = ``mi355_opts.obj_feats``: every predict also returns ``Results.feats``, one appearance embedding per box read from
+        the Detect head's own input maps (what Ultralytics' BoT-SORT uses under ``with_reid: True``, ``model: auto``).  Like ``half`` it
+        is a property of the engine: ``predict(feats=...)`` with the other value runs on a second engine, created on first use."""
         lib = _lib.lib()
-        self._lock = threading.Lock()          # Ultralytics serialises predict() with a per-predictor lock
+        self._lock = threading.RLock()         # Ultralytics serialises predict() with a per-predictor lock
+        self.feats = bool(feats)
+        self._h_feats = {}                     # half -> engine with the other value of `feats`, created on first use
         self._h = C.c_void_p()
         self._h_other = C.c_void_p()           # engine of the other precision, created by the first predict(half=...) that needs it
         self.half = bool(half)                 # precision of the primary engine (predict(half=None) uses it)
@@ -66,7 +72,7 @@ class YOLO:
         self._opt_kw = dict(batch_chunk=int(batch_chunk), fast_act=int(self.fast_act), autotune=int(autotune), streams=int(streams), flags=int(flags),
                             plan_dir=os.fsencode(pd) if pd else None,
                             plan_cache_dir=None if plan_cache_dir is None else os.fsencode(plan_cache_dir))
-        opts = _lib.Opts(struct_size=C.sizeof(_lib.Opts), half=int(self.half), **self._opt_kw)
+        opts = _lib.Opts(struct_size=C.sizeof(_lib.Opts), half=int(self.half), obj_feats=int(self.feats), **self._opt_kw)
         if isinstance(model, (bytes, bytearray, memoryview)):
             blob = bytes(model)
             self.ckpt_path = None
@@ -102,25 +108,38 @@ class YOLO:
         """Build from an unfused Ultralytics-named state dict (what a ``.pt`` holds) for model ``name``."""
         return cls(build_from_state_dict(name, state_dict, nc=nc), **kw)
 
-    def __del__(self):
-        for name in ("_h", "_h_other"):
-            h = getattr(self, name, None)
-            if h is not None and h.value:
-                try:
-                    _lib.lib().mi355_yolo_destroy(h)
-                except Exception:
-                    pass
-                setattr(self, name, C.c_void_p())
+    def _all_handles(self):
+        return [h for h in (getattr(self, "_h", None), getattr(self, "_h_other", None), *getattr(self, "_h_feats", {}).values())
+                if h is not None and h.value]
 
-    def _handle(self, half: Optional[bool]):
-        """Engine handle for the requested precision (``half=True`` = Ultralytics' predictor argument: fp16 storage)."""
-        if half is None or bool(half) == self.half:
+    def __del__(self):
+        for h in self._all_handles():
+            try:
+                _lib.lib().mi355_yolo_destroy(h)
+            except Exception:
+                pass
+        self._h, self._h_other, self._h_feats = C.c_void_p(), C.c_void_p(), {}
+
+    def _handle(self, half: Optional[bool], feats: Optional[bool] = None):
+        """Engine handle for the requested precision (``half=True`` = Ultralytics' predictor argument: fp16 storage) and feature
+        output (``feats``); None = what the model was constructed with."""
+        half = self.half if half is None else bool(half)
+        feats = self.feats if feats is None else bool(feats)
+        if half == self.half and feats == self.feats:
             return self._h
-        if not self._h_other.value:
-            opts = _lib.Opts(struct_size=C.sizeof(_lib.Opts), half=int(bool(half)), **self._opt_kw)
-            _lib.check(_lib.lib().mi355_yolo_create_from_memory(self._blob, len(self._blob), self.device, C.byref(opts),
-                                                                C.byref(self._h_other)))
-        return self._h_other
+        if feats == self.feats:
+            if not self._h_other.value:
+                self._h_other = self._create(half, feats)
+            return self._h_other
+        if half not in self._h_feats:
+            self._h_feats[half] = self._create(half, feats)
+        return self._h_feats[half]
+
+    def _create(self, half: bool, feats: bool):
+        hnd = C.c_void_p()
+        opts = _lib.Opts(struct_size=C.sizeof(_lib.Opts), half=int(half), obj_feats=int(feats), **self._opt_kw)
+        _lib.check(_lib.lib().mi355_yolo_create_from_memory(self._blob, len(self._blob), self.device, C.byref(opts), C.byref(hnd)))
+        return hnd
 
     def info(self, detailed: bool = False, verbose: bool = False):
         i = self.info_struct
@@ -232,9 +251,25 @@ class YOLO:
         def __init__(self, ptr: int, n: int, h: int, w: int):
             self.ptr, self.shape = int(ptr), (int(n), int(h), int(w), 3)
 
-    def _infer_rows(self, batch, conf, iou, classes, max_det, imgsz, half=None):
+    def _infer_rows(self, batch, conf, iou, classes, max_det, imgsz, half=None, feats=None, feats_out: Optional[list] = None):
+        """-> (rows [n, max_det, 58 words], counts [n], (h, w) or the list of them).  An engine with feature output appends
+        float32 [n, max_det, s] to ``feats_out``, parallel to ``rows``."""
+        if feats_out is None or not (self.feats if feats is None else feats):
+            return self._infer_rows_locked(batch, conf, iou, classes, max_det, imgsz, half, feats)      # the call as it always was
+        with self._lock:                       # re-entered by the call below: the features are fetched before another thread's call replaces them
+            out = self._infer_rows_locked(batch, conf, iou, classes, max_det, imgsz, half, feats)
+            hnd = self._last_handle
+            dim = C.c_int()
+            _lib.check(_lib.lib().mi355_yolo_feat_dim(hnd, C.byref(dim)))
+            if dim.value:
+                f = np.empty((len(out[1]), max_det, dim.value), np.float32)      # only f[i, :counts[i]] are written / meaningful
+                _lib.check(_lib.lib().mi355_yolo_last_feats(hnd, f.ctypes.data, max_det, len(out[1])))
+                feats_out.append(f)
+        return out
+
+    def _infer_rows_locked(self, batch, conf, iou, classes, max_det, imgsz, half, feats):
         lib = _lib.lib()
-        hnd = self._handle(half)
+        hnd = self._handle(half, feats)
         self._last_handle = hnd
         n = int(batch.shape[0])
         h, w = (0, 0) if isinstance(batch, (YOLO._Ragged, YOLO._YuvBatch)) else (int(batch.shape[1]), int(batch.shape[2]))
@@ -334,21 +369,22 @@ class YOLO:
 
     def sync(self) -> None:
         """Wait for every asynchronous call enqueued so far (both engines, when a ``half=`` override created the second)."""
-        for hnd in (self._h, self._h_other):
-            if hnd.value:
-                _lib.check(_lib.lib().mi355_yolo_sync(hnd))
+        for hnd in self._all_handles():
+            _lib.check(_lib.lib().mi355_yolo_sync(hnd))
 
     def predict(self, source=None, conf: Optional[float] = None, iou: float = 0.7, classes=None, max_det: int = 300,
-                imgsz: int = 640, half: Optional[bool] = None, verbose: bool = False, stream: bool = False, **kwargs
-                ) -> List[Results]:
+                imgsz: int = 640, half: Optional[bool] = None, verbose: bool = False, stream: bool = False,
+                feats: Optional[bool] = None, **kwargs) -> List[Results]:
         """``model.predict`` / ``model(...)``: ultralytics/engine/model.py:Model.predict.
         ``half=True`` runs the fp16-storage engine (fp32 accumulate; results differ from fp32 by fp16 rounding);
-        ``None`` = the precision the model was constructed with (fp32 unless ``YOLO(..., half=True)``)."""
+        ``None`` = the precision the model was constructed with (fp32 unless ``YOLO(..., half=True)``).
+        ``feats=True`` also fills ``Results.feats`` (float32 [M, s]: the detector's own appearance embedding of every box);
+        ``None`` = as constructed.  Boxes and keypoints are bit for bit the same either way."""
         if isinstance(imgsz, (list, tuple)):
             imgsz = int(max(imgsz))
         conf = 0.25 if conf is None else float(conf)
         batch, originals = self._as_batch(source)
-        return self._predict_batch(batch, originals, conf, iou, classes, max_det, imgsz, half)
+        return self._predict_batch(batch, originals, conf, iou, classes, max_det, imgsz, half, feats)
 
     def detect_rows(self, batch, conf: float = 0.25, iou: float = 0.7, classes=None, max_det: int = 300, imgsz: int = 640, half=None):
         """``Results.boxes.data`` of every frame of ``batch`` -- float32 [M, 6] rows x1, y1, x2, y2, conf, cls -- and the frames' (h, w),
@@ -365,8 +401,9 @@ class YOLO:
             out.append(d)
         return out, shape
 
-    def _predict_batch(self, batch, originals, conf, iou, classes, max_det, imgsz, half) -> List[Results]:
-        rows, counts, shape = self._infer_rows(batch, conf, float(iou), classes, int(max_det), int(imgsz), half)
+    def _predict_batch(self, batch, originals, conf, iou, classes, max_det, imgsz, half, feats=None) -> List[Results]:
+        fout = []
+        rows, counts, shape = self._infer_rows(batch, conf, float(iou), classes, int(max_det), int(imgsz), half, feats, fout)
         t = _lib.Timing()
         _lib.lib().mi355_yolo_last_timing(self._last_handle, C.byref(t))
         per_img_ms = t.total_ms / max(1, int(batch.shape[0]))
@@ -383,7 +420,7 @@ class YOLO:
                           boxes=torch.from_numpy(data), keypoints=kp.clone() if kp is not None else None,
                           orig_shape=shape[i] if isinstance(shape, list) else shape,
                           speed={"preprocess": 0.0, "inference": per_img_ms, "postprocess": 0.0},
-                          anchor_idx=ints[:, 1].copy())
+                          anchor_idx=ints[:, 1].copy(), feats=fout[0][i, :counts[i]].copy() if fout else None)
             if kp is not None:
                 res.keypoints_raw = kp.numpy()          # before Keypoints() zeroes x,y of joints with conf < 0.5
             out.append(res)
@@ -391,16 +428,24 @@ class YOLO:
 
     __call__ = predict
 
-    def track(self, source=None, persist: bool = False, show: bool = False, conf: Optional[float] = None, **kwargs
+    def track(self, source=None, persist: bool = False, show: bool = False, conf: Optional[float] = None, tracker=None, **kwargs
               ) -> List[Results]:
         """``model.track`` (``/root/reference/model.py:38``): predict at conf 0.1, then the tracker callback adds
-        ids.  ultralytics/engine/model.py:Model.track forces batch 1; frames are handled one at a time, in order."""
+        ids.  ultralytics/engine/model.py:Model.track forces batch 1; frames are handled one at a time, in order.
+        ``tracker``: a ``botsort.yaml``-style file path or dict (``tracker.tracker_config`` says which keys are honoured and refuses the
+        rest); it configures the tracker this call creates.  A ``persist=True`` call that continues a tracker may repeat the argument
+        (it is not parsed again) or omit it; settings that differ from the continued tracker's are a ``ValueError``, not ignored.
+        With ``with_reid: True`` the detector pass also produces its per-box embeddings and the tracker matches on them."""
         from .tracker import BYTETracker
         kwargs.pop("batch", None)
         conf = 0.1 if conf is None else conf
-        if self._tracker is None or not persist:
+        cfg = self._tracker_settings("track", tracker, continuing=self._tracker is not None and persist)
+        if cfg is not None:
             # the frame preparation and the optical flow of its motion compensation run on the engine's GPU (csrc/gmc_kernels.hip)
-            self._tracker = BYTETracker(gmc_device=getattr(self, "device", None))
+            self._tracker = BYTETracker(gmc_device=getattr(self, "device", None), **cfg)
+        reid = self._tracker.with_reid
+        if reid:
+            kwargs["feats"] = True
         yuv = as_frames(source)
         if yuv is not None:
             # the convenience form: the motion compensation takes a host BGR frame, so a YUV frame is converted on the GPU and its BGR
@@ -423,7 +468,8 @@ class YOLO:
             if dev is not None and dev[1:] == tuple(frame.shape[:2]) and not kwargs.get("stream"):
                 imgsz = kwargs.get("imgsz", 640)
                 res = self._predict_batch(YOLO._DeviceFrames(dev[0], 1, dev[1], dev[2]), None, float(conf), kwargs.get("iou", 0.7), kwargs.get("classes"),
-                                          kwargs.get("max_det", 300), int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"))[0]
+                                          kwargs.get("max_det", 300), int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"),
+                                          kwargs.get("feats"))[0]
             else:
                 res = self.predict(batch[i:i + 1], conf=conf, **kwargs)[0]
             if originals is not None:
@@ -431,9 +477,28 @@ class YOLO:
             # trackers/track.py:on_predict_postprocess_end: the tracker steps on EVERY frame (an empty frame still advances
             # frame_id, ages lost tracks against track_buffer and runs the Kalman predict); only the rewrite of the
             # result is skipped when no track comes back
-            tracks = self._tracker.update(res.boxes.data.numpy(), frame)   # trackers/track.py: tracker.update(det, im0)
+            tracks = self._tracker.update(res.boxes.data.numpy(), frame, feats=res.feats if reid else None)   # trackers/track.py: tracker.update(det, im0, feats)
             results.append(self._with_tracks(res, tracks))
         return results
+
+    def _tracker_settings(self, which: str, tracker, continuing: bool) -> Optional[dict]:
+        """``tracker=`` of :meth:`track` / :meth:`track_cameras` -> the ``BYTETracker`` keywords of the tracker(s) to create, or None when
+        the call continues existing ones.  The argument is parsed where a tracker is created; a continuing call that brings the argument
+        it was created with (or none) parses nothing, and one that brings other settings is refused."""
+        from .tracker import tracker_config
+        made = self.__dict__.setdefault("_tracker_made", {})
+        if not continuing:
+            cfg = tracker_config(tracker)
+            made[which] = (dict(tracker) if isinstance(tracker, dict) else tracker, cfg)
+            return cfg
+        arg0, cfg0 = made.get(which, (None, {}))
+        if tracker is not None and not (type(tracker) is type(arg0) and tracker == arg0):
+            full = lambda c: {"with_reid": False, "proximity_thresh": 0.5, "appearance_thresh": 0.8, **c}
+            if full(tracker_config(tracker)) != full(cfg0):
+                raise ValueError("tracker: these settings differ from those of the tracker this call continues (persist=True); "
+                                 "start a new tracker with persist=False")
+            made[which] = (dict(tracker) if isinstance(tracker, dict) else tracker, cfg0)
+        return None
 
     @staticmethod
     def _with_tracks(res: Results, tracks: np.ndarray) -> Results:
@@ -453,11 +518,12 @@ class YOLO:
         ONE detector pass over all present frames (the mixed-shape path of :meth:`predict`) and ONE motion-compensation step
         (``gmc.MultiGMC``), whose uploaded frames the detector reads in place.  ``persist=True`` continues the cameras' tracks (the list
         length is the number of cameras and must not change); otherwise every camera starts afresh.  Keyword arguments: ``iou``,
-        ``classes``, ``max_det``, ``imgsz``, ``half`` as in :meth:`predict`; ``show`` / ``verbose`` are accepted and ignored; anything
-        else is a ``TypeError``."""
+        ``classes``, ``max_det``, ``imgsz``, ``half``, ``feats`` as in :meth:`predict`, ``tracker`` as in :meth:`track` (every camera's
+        tracker gets the same settings); ``show`` / ``verbose`` are accepted and ignored; anything else is a ``TypeError``."""
         from .gmc import MultiGMC
         from .tracker import BYTETracker
-        unknown = set(kwargs) - {"iou", "classes", "max_det", "imgsz", "half", "show", "verbose"}
+        tracker = kwargs.pop("tracker", None)
+        unknown = set(kwargs) - {"iou", "classes", "max_det", "imgsz", "half", "feats", "show", "verbose"}
         if unknown:                                              # show / verbose are accepted and ignored, as in track()
             raise TypeError(f"track_cameras: unsupported argument(s) {sorted(unknown)} (iou, classes, max_det, imgsz, half pass through)")
         conf = 0.1 if conf is None else float(conf)
@@ -476,10 +542,12 @@ class YOLO:
         cams = getattr(self, "_cameras", None)
         if persist and cams is not None and len(cams[0]) != n:
             raise ValueError(f"{n} frames for {len(cams[0])} tracked cameras: the list length is the number of cameras (None = absent)")
-        if cams is None or not persist:
+        cfg = self._tracker_settings("cameras", tracker, continuing=cams is not None and persist)
+        if cfg is not None:
             # one BoT-SORT core per camera, stepped with the warp of the shared motion-compensation object (on the engine's GPU)
-            cams = self._cameras = ([BYTETracker(gmc_method=None) for _ in range(n)], MultiGMC(n, device=self.device))
+            cams = self._cameras = ([BYTETracker(gmc_method=None, **cfg) for _ in range(n)], MultiGMC(n, device=self.device))
         trackers, gmc = cams
+        reid = trackers[0].with_reid
         present = [i for i, f in enumerate(frames) if f is not None]
         out: List[Optional[Results]] = [None] * n
         if not present:
@@ -503,13 +571,14 @@ class YOLO:
         imgsz = kwargs.get("imgsz", 640)
         try:
             res = self._predict_batch(batch, originals, conf, kwargs.get("iou", 0.7), kwargs.get("classes"), kwargs.get("max_det", 300),
-                                      int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"))
+                                      int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"),
+                                      True if reid else kwargs.get("feats"))
         except BaseException:
             gmc.reset()                                          # the enqueued tick must not be taken for the next call's frames
             raise
         warps = gmc.apply(frames)
         for r, i in zip(res, present):
-            out[i] = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i]))    # an empty frame still steps
+            out[i] = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i], feats=r.feats if reid else None))    # an empty frame still steps
         return out
 
     # ------------------------------------------------------------------------------------------ test hooks
@@ -561,9 +630,8 @@ class YOLO:
                 "candidates": [int(v[6]), int(v[7]), int(v[8])], "last_overflow": bool(v[9])}
 
     def set_profiling(self, on: bool = True) -> None:
-        _lib.check(_lib.lib().mi355_yolo_set_profiling(self._h, int(on)))
-        if self._h_other.value:
-            _lib.check(_lib.lib().mi355_yolo_set_profiling(self._h_other, int(on)))
+        for hnd in self._all_handles():
+            _lib.check(_lib.lib().mi355_yolo_set_profiling(hnd, int(on)))
 
     def last_timing(self) -> dict:
         t = _lib.Timing()

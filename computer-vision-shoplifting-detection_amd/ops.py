@@ -157,6 +157,37 @@ def decode(levels, nc: int, nkpt: int = 0, kdim: int = 0, mode: str = "full", ga
     return (pred, best, count.value) if mode == "split" else (pred, best)
 
 
+def obj_feats(levels, anchor_idx, counts, half: bool = False, device: int = 0) -> np.ndarray:
+    """The object-feature gather alone (csrc/post_kernels.hip).  ``levels``: 1 to 4 tuples ``(buf [n,h,w,cs], c_off, C)``,
+    the level's channels at ``c_off .. c_off + C - 1`` of ``buf``; fp32 arrays, or with ``half`` float16 arrays (all levels alike).
+    ``anchor_idx`` int32 [n, cap] (P3 row-major first), ``counts`` [n].  -> float32 [n, cap, s], s = min(C): row r of frame i =
+    the group means of its anchor's channels for r < counts[i]; the rest keeps SENTINEL, which fills the output before the launch."""
+    levels = list(levels)
+    if not 1 <= len(levels) <= 4:
+        raise ValueError("obj_feats takes 1 to 4 levels")
+    want = np.float16 if half else np.float32
+    bufs, geom, n = [], [], None
+    for buf, c_off, c in levels:
+        b = np.ascontiguousarray(buf)
+        if b.dtype != want or b.ndim != 4 or (n is not None and b.shape[0] != n):
+            raise ValueError(f"every level is a {np.dtype(want).name} array [n, h, w, cs] with the same n")
+        n = b.shape[0]
+        bufs.append(b)
+        geom += [b.shape[3], int(c_off), int(c), b.shape[1], b.shape[2]]
+    idx = np.ascontiguousarray(anchor_idx, dtype=np.int32)
+    cnt = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    if idx.ndim != 2 or idx.shape[0] != n or len(cnt) != n:
+        raise ValueError("anchor_idx is [n, cap] and counts [n]")
+    dim = min(int(c) for _, _, c in levels)
+    out = _sentinel((n, idx.shape[1], dim))
+    ptrs = (C.c_void_p * len(bufs))(*[b.ctypes.data for b in bufs])
+    g = (C.c_int * len(geom))(*[int(v) for v in geom])
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    _lib.check(_lib.lib().mi355_op_obj_feats(device, ptrs, g, len(bufs), n, int(bool(half)), i32(idx), i32(cnt), idx.shape[1], dim,
+                                             out.ctypes.data))
+    return out
+
+
 def pose_array(poses):
     """-> (poses as a C-contiguous [P, V_src, 2] array, its MI355_POSE_* code); anything but float32 / float64 is refused, because the
     window arithmetic runs in the poses' own type"""
@@ -561,6 +592,20 @@ def memory_plan(blob: bytes, n: int, height: int, width: int, imgsz: int = 640, 
                                             C.byref(arena), C.byref(plain)))
     k = nb.value
     return np.array(off[:k], dtype=np.int64), np.array(sz[:k], dtype=np.int64), arena.value, plain.value
+
+
+def memory_plan_ex(blob: bytes, n: int, height: int, width: int, imgsz: int = 640, half: bool = False, reuse: bool = True,
+                   obj_feats: bool = False):
+    """:func:`memory_plan` for an engine with ``mi355_opts.obj_feats``: -> (offsets, sizes, arena_bytes, unshared_bytes, detect_bufs),
+    ``detect_bufs`` = the program buffers that hold the Detect head's input maps, one per level (what the option keeps alive)."""
+    cap = 4096
+    off, sz = (C.c_longlong * cap)(), (C.c_longlong * cap)()
+    nb, arena, plain = C.c_int(0), C.c_longlong(0), C.c_longlong(0)
+    det = (C.c_int * 4)(-1, -1, -1, -1)
+    _lib.check(_lib.lib().mi355_memory_plan_ex(blob, len(blob), n, height, width, imgsz, int(half), int(reuse), int(obj_feats), off, sz, cap,
+                                               C.byref(nb), C.byref(arena), C.byref(plain), det))
+    k = nb.value
+    return np.array(off[:k], dtype=np.int64), np.array(sz[:k], dtype=np.int64), arena.value, plain.value, [d for d in det if d >= 0]
 
 
 def conv2d_group(x_nhwc: np.ndarray, wa: np.ndarray, ba: np.ndarray, wb: np.ndarray, bb: np.ndarray, stride_a: int = 1, stride_b: int = 1,

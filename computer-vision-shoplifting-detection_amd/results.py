@@ -162,7 +162,7 @@ class Results:
     """One image's predictions (``list[Results]`` is what ``model(frame)`` / ``model.track(frame)`` return)."""
 
     def __init__(self, orig_img: Optional[np.ndarray], path: str, names: Dict[int, str], boxes=None, keypoints=None,
-                 orig_shape: Optional[Tuple[int, int]] = None, speed: Optional[dict] = None, anchor_idx=None):
+                 orig_shape: Optional[Tuple[int, int]] = None, speed: Optional[dict] = None, anchor_idx=None, feats=None):
         self.orig_img = orig_img
         self.orig_shape = tuple(orig_shape) if orig_shape is not None else tuple(orig_img.shape[:2])
         self.boxes = Boxes(boxes, self.orig_shape) if boxes is not None else None
@@ -172,6 +172,9 @@ class Results:
         self.names = names
         self.path = path
         self.anchor_idx = anchor_idx      # engine extra: source anchor of every row (index-identity checks)
+        # predict(feats=True): float32 [M, s], row i the appearance embedding of box i, read from the Detect head's input maps
+        # (Ultralytics' Results.feats under with_reid / model: auto); None otherwise
+        self.feats = feats
 
     def __len__(self):
         return len(self.boxes) if self.boxes is not None else 0
@@ -182,6 +185,9 @@ class Results:
             r.boxes = self.boxes[idx]
         if self.keypoints is not None:
             r.keypoints = self.keypoints[idx]
+        if self.feats is not None:
+            ix = idx.numpy() if isinstance(idx, torch.Tensor) else idx
+            r.feats = self.feats[[ix]] if isinstance(ix, (int, np.integer)) else self.feats[ix]       # an integer keeps one row, as Boxes does
         return r
 
     def update(self, boxes=None):
@@ -198,4 +204,5 @@ class Results:
         r = Results(self.orig_img, self.path, self.names, orig_shape=self.orig_shape, speed=self.speed)
         r.boxes = self.boxes.numpy() if self.boxes is not None else None
         r.keypoints = self.keypoints.numpy() if self.keypoints is not None else None
+        r.feats = self.feats
         return r

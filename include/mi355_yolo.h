@@ -69,7 +69,9 @@ typedef struct mi355_opts {
                            * (the planner's static guess), n > 0 = n */
     int streams;          /* HIP streams the ops of a pass of >= 6 frames are dealt to along the dependency DAG: 0 = default (4), 1 = one */
     int flags;            /* MI355_OPT_* */
-    int reserved;
+    int obj_feats;        /* 1 = every blocking infer call also produces one appearance embedding per kept row, read from the Detect head's
+                           * own input maps (Ultralytics' with_reid / model: auto; mi355_yolo_last_feats below).  0 (default): nothing of it
+                           * exists -- launches, arena offsets and rows are those of an engine that never heard of it.  Was `reserved`. */
     const char* plan_dir;        /* read-only directory of SHIPPED launch-plan files (cvsd_amd/plans): looked up first, so that every process
                                   * on the same GPU model runs the same launch sequence without timing anything.  NULL = none */
     const char* plan_cache_dir;  /* writable directory where freshly timed choices are kept (and found again): NULL = ~/.cache/mi355yolo,
@@ -227,6 +229,23 @@ int  mi355_yolo_raw_head_multi(mi355_yolo* h, const uint8_t* const* frames, cons
                                const int* row_strides, int frames_on_device, int n, int imgsz, float* out, int* out_channels,
                                int* out_anchors);
 
+/* ---- object features: the detector's own appearance embedding per kept row -----------------------------------------
+ * DetectionPredictor.get_obj_feats (ultralytics/engine/predictor.py, fed by a forward pre-hook on Detect; botsort.yaml with_reid: True,
+ * model: auto): with C_l the channels of the three Detect inputs and s = min(C_l), a row whose anchor a lies on level l (g = C_l / s) gets
+ *     e[j] = mean(x_l[a, j*g .. j*g + g - 1]),  j = 0 .. s-1
+ * in fp32: acc = x[0]; acc += x[r] for ascending r; e = acc / (float)g, IEEE division (g = 1 copies the bits); with half = 1 the stored
+ * fp16 values are widened to fp32 first.  An engine created with mi355_opts.obj_feats = 1 keeps the three maps alive until the chunk's
+ * NMS has run (they share arena bytes with no other buffer) and enqueues ONE gather launch per chunk behind NMS.  Creation fails with
+ * MI355_EFORMAT when the program's three Detect-input slices cannot be found, or their channel counts are not multiples of the smallest.
+ *   mi355_yolo_feat_dim     *dim = s, or 0 when the option is off
+ *   mi355_yolo_last_feats   out[n][capacity_per_image][dim] float32, parallel to out_rows of the LAST blocking infer call on the handle
+ *                           (mi355_yolo_infer, _infer_device, _infer_multi, _infer_yuv): row r of image i belongs to out_rows row r of image i;
+ *                           rows at or beyond that call's out_counts[i] are not written.  n must be that call's n.  MI355_EINVAL when the
+ *                           last call produced none: the option is off, no call yet, the call failed, or it was one of the *_device_async
+ *                           forms -- those run unchanged and produce no features. */
+int  mi355_yolo_feat_dim(const mi355_yolo* h, int* dim);
+int  mi355_yolo_last_feats(const mi355_yolo* h, float* out, int capacity_per_image, int n);
+
 /* Launch plans of the shape last run: plan_hash identifies the candidate lists AND the choice per conv (two runs with the same
  * hash launch the same kernels with the same grids); source 0 = static guess (autotune off), 1 = this process's memory,
  * 2 = this machine's plan cache, 3 = timed now, 4 = shipped plan file (opts.plan_dir); launches = kernel launches of one pass (stem .. last conv; decode and NMS follow);
@@ -240,6 +259,11 @@ int  mi355_yolo_plan_info(const mi355_yolo* h, unsigned long long* plan_hash, in
 int  mi355_memory_plan(const void* blob, size_t nbytes, int n, int height, int width, int imgsz, int half, int reuse,
                        long long* offsets, long long* sizes, int cap, int* n_buffers, long long* arena_bytes,
                        long long* unshared_bytes);
+/* The same with the option mi355_opts.obj_feats: 1 places the three Detect-input buffers on bytes of their own; detect_bufs (or NULL)
+ * receives their program buffer indices, one per head level.  obj_feats = 0 gives exactly mi355_memory_plan's results. */
+int  mi355_memory_plan_ex(const void* blob, size_t nbytes, int n, int height, int width, int imgsz, int half, int reuse, int obj_feats,
+                          long long* offsets, long long* sizes, int cap, int* n_buffers, long long* arena_bytes,
+                          long long* unshared_bytes, int* detect_bufs);
 /* Per-kernel-kind timing costs two HIP events per launch; off by default (total_ms is always measured). */
 int  mi355_yolo_set_profiling(mi355_yolo* h, int on);
 int  mi355_yolo_last_timing(const mi355_yolo* h, mi355_timing* t);
@@ -392,6 +416,34 @@ int  mi355_tracker_state(const mi355_tracker* t, int* frame_id, int* ids_issued,
 /* which = 0: tracked (confirmed or awaiting confirmation), 1: lost.  Rows of 16 doubles: id, state (1 tracked, 2 lost, 3 removed),
  * confirmed, frame of birth, last matched frame, score, cls, idx, mean[8] = cx cy w h + velocities.  Returns the count. */
 int  mi355_tracker_tracks(const mi355_tracker* t, int which, double* out, int cap);
+/* BoT-SORT's appearance half (botsort.yaml with_reid: True, model: auto; trackers/bot_sort.py:BOTrack, BOTSORT.get_dists,
+ * matching.py:embedding_distance).  The embeddings come from the detector itself (mi355_opts.obj_feats, mi355_yolo_last_feats).
+ *   a detection handed a feature f holds curr_feat = f / ||f||; a track's smooth_feat is the first curr_feat it absorbs and after every
+ *   later match (any of the three stages, re-activation included) 0.9 * smooth + 0.1 * curr in fp32, brought back to unit length
+ *   stages 1 and 3 (the ones that fuse the score): d = IoU cost; mask = d > 1 - proximity_thresh (before the fusion); d = fuse_score(d);
+ *   emb = max(0, cosine distance(smooth_feat, curr_feat)) / 2; emb[emb > 1 - appearance_thresh] = 1; emb[mask] = 1; d = min(d, emb).
+ *   Stage 2 stays plain IoU.
+ * Reductions (norm, dot) run in ascending index over the fp32 values widened to float64, in a float64 accumulator; the norm is rounded
+ * to fp32 once before the division, the cosine distance stays float64.  Deviations from Ultralytics: a zero-norm feature stays zeros and
+ * its embedding cost is 1 (numpy: NaN), as is that of a track that has absorbed no feature yet; the 50-entry `features` deque, which
+ * Ultralytics writes and never reads, is not kept.
+ *   cfg       struct_size = sizeof(mi355_tracker_cfg); NULL = mi355_tracker_create.  feat_dim 0 = fixed by the first update that brings
+ *             features; a threshold of 0 = its botsort.yaml default (0.5 / 0.8)
+ *   feats     NULL, or [n][dim] float32, row i belonging to det row i.  NULL on a with_reid tracker is Ultralytics' `encoder is None`:
+ *             that frame associates on IoU alone and no smooth_feat changes.  On a tracker without with_reid feats is not read.
+ * mi355_tracker_track_feat (tests): the smooth_feat of live or lost track `track_id` -> the number of floats written (0: the track has
+ * absorbed no feature), -1: no such track or dim too small.  mi355_tracker_create / mi355_tracker_update behave exactly as before. */
+typedef struct mi355_tracker_cfg {
+    int struct_size;
+    int with_reid;
+    int feat_dim;
+    int reserved;
+    double proximity_thresh, appearance_thresh;
+} mi355_tracker_cfg;
+int  mi355_tracker_create_ex(int frame_rate, const mi355_tracker_cfg* cfg, mi355_tracker** out);
+int  mi355_tracker_update_feats(mi355_tracker* t, const float* det, int n, const float* feats, int dim, const double* warp, float* out_rows,
+                                int cap);
+int  mi355_tracker_track_feat(const mi355_tracker* t, int track_id, float* smooth_out, int dim);
 /* The pieces, for known-answer tests: the filter on (mean[8], cov[8][8] row-major) in place, and the assignment solver --
  * lap.lapjv(cost [n_rows][n_cols], extend_cost=True, cost_limit): x_out[i] = column of row i or -1, y_out[j] = row of column j or -1. */
 int  mi355_kalman_initiate(const double* z_xywh, double* mean, double* cov);
@@ -465,6 +517,13 @@ int  mi355_op_psa_attention(int device_id, const float* qkv, int n, int hw, int 
  * (cs and box_off multiples of 4) come back as MI355_EHIP with its message. */
 int  mi355_op_decode(int device_id, const float* const* bufs, const int* geom, int n_levels, int n, int nc, int nkpt, int kdim,
                      int mode, int gate, float* pred, float* best, int* fallback_count);
+/* The object-feature gather alone (csrc/post_kernels.hip: one wave per row slot), on maps of the caller: bufs[l] = [n][h][w][cs] and
+ * geom[l] = {cs, c_off, C, h, w} for each of n_levels (1 .. 4) levels, the level's channels at c_off .. c_off + C - 1; half = 0: fp32
+ * elements, 1: fp16 bit patterns (all levels alike).  dim must be min(C_l) and divide every C_l; cs and c_off are multiples of 4
+ * (fp32) or 8 (fp16) elements.  anchor_idx[n][cap] in [0, A), A = sum h*w, P3 row-major first; counts[n] in [0, cap].
+ * feats[n][cap][dim] is read in and handed back, so rows at or beyond counts[i] keep the caller's bits. */
+int  mi355_op_obj_feats(int device_id, const void* const* bufs, const int* geom, int n_levels, int n, int half, const int* anchor_idx,
+                        const int* counts, int cap, int dim, float* feats);
 /* The sparse box branch alone (csrc/conv_f32_sparse.hip), enqueued as a pass enqueues its sparse tail minus the dense launches:
  * the 12 state ints zeroed, the lists kernel, then cv2.i.0 at the dilated and cv2.i.1 -> cv2.i.2 -> DFL -> box at the candidate
  * positions.  n_levels 1 .. 3; per level l
