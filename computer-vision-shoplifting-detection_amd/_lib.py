@@ -55,6 +55,14 @@ class YuvFrame(C.Structure):
                 ("y_stride", C.c_int), ("uv_stride", C.c_int), ("format", C.c_int), ("reserved", C.c_int)]
 
 
+class TileOpts(C.Structure):
+    """mi355_tile_opts: the tile grid (pixels) and the merge of a tiled predict call"""
+    _fields_ = [("struct_size", C.c_int), ("tile_h", C.c_int), ("tile_w", C.c_int), ("overlap_y_px", C.c_int), ("overlap_x_px", C.c_int),
+                ("full_frame", C.c_int), ("metric", C.c_int), ("thr", C.c_float)]
+
+
+TILE_IOS, TILE_IOU = 0, 1               # MI355_TILE_IOS / MI355_TILE_IOU
+TILE_MAX_ENTRIES, TILE_MAX_CANDIDATES = 64, 65536
 PIX_NV12, PIX_I420 = 1, 2               # MI355_PIX_*
 DET_WORDS = C.sizeof(Det) // 4          # 58 32-bit words per row
 POSE_F32, POSE_F64 = 0, 1               # MI355_POSE_F32 / MI355_POSE_F64: the element type of a pose array
@@ -83,6 +91,13 @@ SIGNATURES = {
     "mi355_yolo_infer_yuv_device_async": (C.c_int, [C.c_void_p, _P(YuvFrame), C.c_int, C.c_float, C.c_float, _i32p, C.c_int, C.c_int, C.c_int,
                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi355_op_yuv_to_bgr": (C.c_int, [C.c_int, _P(YuvFrame), C.c_int, _P(C.c_void_p)]),
+    "mi355_tile_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
+    "mi355_yolo_infer_tiled": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, C.c_int, C.c_int, _P(TileOpts), C.c_float, C.c_float,
+                                         _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p, C.c_void_p]),
+    "mi355_yolo_infer_tiled_yuv": (C.c_int, [C.c_void_p, _P(YuvFrame), C.c_int, C.c_int, _P(TileOpts), C.c_float, C.c_float, _i32p, C.c_int,
+                                             C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p, C.c_void_p]),
+    "mi355_op_tile_merge": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi355_yolo_stream": (C.c_void_p, [C.c_void_p]),
     "mi355_yolo_sync": (C.c_int, [C.c_void_p]),
     "mi355_yolo_raw_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -265,6 +265,11 @@ struct mi355_yolo {
     // NMS and the gather behind it have run.  d_feats [n][max_det][dim] follows d_rows, d_feats_packed d_packed, h_feats h_rows.
     bool obj_feats = false; int feat_levels = 0, feat_src[4] = {-1, -1, -1, -1}, feat_dim = 0;
     Buf d_feats, d_feats_packed, h_feats{true};
+    // Tiled predict (engine_tiled.hip): the call's host (or converted YUV) frames, uploaded once each; the per-frame entry
+    // ranges and origins of the merge [entry_off (n + 1) | origins (2 per entry)] with their pinned image, uploaded when the bytes change;
+    // the merge kernel's key scratch (frames with more than 4096 candidates); its counts and entry indices [counts n | idx slots | idx packed]
+    Buf d_tile_frames, d_tile, h_tile{true}, d_tile_keys, d_tile_out, h_tile_out{true}; size_t tile_bytes = 0;
+    bool tile_direct = false;           // the last tiled call's merged rows went straight to the pinned host blocks (slot layout)
     // what mi355_yolo_last_feats hands out: the last blocking call's n and max_det, and whether h_feats holds its rows packed in frame
     // order (counts in h_counts) or at slot i * max_det (the direct-rows path); last_feat_n = 0: the last call produced none
     int last_feat_n = 0, last_feat_max_det = 0; bool last_feat_packed = false;
@@ -371,9 +376,23 @@ int yuv_upload(mi355_yolo* h, const mi355_yuv_frame* frames, bool on_device, int
 int yuv_stage_chunk(mi355_yolo* h, const mi355_yuv_frame* frames, const YuvCall& yc, int s0, int m, int slot);
 int yuv_convert_chunk(mi355_yolo* h, Prof& pf, const YuvCall& yc, int s0, int m);
 
+// engine_tiled.hip: a tiled call.  The frames of the InferCall are the ENTRIES (every source frame's tiles, then the frame itself), on the
+// device; frame f owns entries [entry_off[f], entry_off[f + 1]).  The entry rows stay on the device, one merge launch follows the last
+// chunk's NMS and only the merged rows travel to out_rows [n_frames][cap] / out_counts / out_tile_idx (may be NULL).
+struct TileCall {
+    int n_frames = 0, max_entries = 0;
+    std::vector<int> entry_off, origins;                      // [n_frames + 1]; [entries][2] = ox, oy
+    int metric = 0; float thr = 0.5f;
+    mi355_det* out_rows = nullptr; int cap = 1; int* out_counts = nullptr; int* out_tile_idx = nullptr;
+};
+struct InferCall;
+int tile_merge_enqueue(mi355_yolo* h, const InferCall& c, Prof& pf, bool direct_rows_on);
+int tile_merge_fetch(mi355_yolo* h, const InferCall& c);
+
 // engine_run.hip: one infer call.  An entry point fills what it uses: the frames (one dense block of one shape, `multi`, or `yuv`), the
 // filter, and one of the two output forms.
 struct InferCall {
+    const TileCall* tile = nullptr;                           // set by the tiled entry points only (with `multi` = the entry list)
     const uint8_t* src = nullptr; bool on_device = false;
     int n = 0, height = 0, width = 0, row_stride = 0;         // row_stride 0 = width * 3; host frames only
     const MultiFrames* multi = nullptr;                       // frames of different sizes: src, on_device and the sizes above are not read

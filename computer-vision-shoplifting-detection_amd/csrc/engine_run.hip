@@ -654,7 +654,7 @@ int infer_impl(mi355_yolo* h, const InferCall& call) {
         h->async_pending = false;
     }
     h->last_feat_n = 0;                 // until this call has produced its features
-    s.feats = h->obj_feats && !s.async_out;
+    s.feats = h->obj_feats && !s.async_out && !c.tile;      // a tiled call's rows are merged across entries: no features for it
     rc = call_shape(h, s); if (rc) return rc;
     if (!c.on_device || c.yuv) GROW(h->d_in, 2 * s.slot_bytes);     // host frames / converted YUV frames: a double-buffered staging area of two chunks
     if (c.yuv) { rc = yuv_upload(h, c.yuv, c.on_device, c.n, s.nb, s.slot_bytes, s.yc); if (rc) return rc; }
@@ -670,7 +670,7 @@ int infer_impl(mi355_yolo* h, const InferCall& call) {
     // counts straight into the pinned host buffers -- no compaction kernels, no copy-engine hand-overs (five stream operations,
     // ~45 us of a 425-us frame at batch 1), one stream synchronisation.  MI355_DIRECT_ROWS=0 keeps the copy path.
     const bool direct_rows_on = getenv("MI355_DIRECT_ROWS") ? atoi(getenv("MI355_DIRECT_ROWS")) != 0 : !(h->opt_flags & MI355_OPT_NO_DIRECT_ROWS);
-    s.direct_host = !s.async_out && s.single_chunk && c.n <= 16 && direct_rows_on;
+    s.direct_host = !s.async_out && s.single_chunk && c.n <= 16 && direct_rows_on && !c.tile;   // tiled: the entry rows stay on the device
     if (s.direct_host) {                // taken after the growth: the device view of the pinned blocks as they are now
         HIPCHK(hipHostGetDevicePointer((void**)&s.host_rows_dev, h->h_rows.p, 0));
         HIPCHK(hipHostGetDevicePointer((void**)&s.host_counts_dev, h->h_counts.p, 0));
@@ -680,7 +680,12 @@ int infer_impl(mi355_yolo* h, const InferCall& call) {
     Prof pf{h};
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     rc = run_chunks(h, s, pf); if (rc) return rc;
+    if (c.tile) { rc = tile_merge_enqueue(h, c, pf, direct_rows_on); if (rc) return rc; }      // one launch behind the last chunk's NMS
     HIPCHK(hipEventRecord(h->ev1, h->stream));
+    if (c.tile) {                       // only the merged rows travel (engine_tiled.hip)
+        rc = tile_merge_fetch(h, c); if (rc) return rc;
+        return sparse_feedback_after(h, s, pf);
+    }
     const int n = c.n, det_words = (int)(sizeof(mi355_det) / 4);
     if (s.async_out) {
         // packed rows (frame order), counts and their sum go to the caller's device buffers; no host copy, no sync

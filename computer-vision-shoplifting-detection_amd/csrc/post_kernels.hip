@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #pragma clang fp contract(off)
+#include "tile_merge.h"
 
 namespace mi355 {
 
@@ -684,6 +685,135 @@ const char* launch_obj_feats(const ObjFeatArgs& a, hipStream_t st) {
     const unsigned blocks = (unsigned)(((long)a.B * a.cap + 3) / 4);
     if (a.half) hipLaunchKernelGGL(obj_feats_kernel<true>, dim3(blocks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(obj_feats_kernel<false>, dim3(blocks), dim3(256), 0, st, a);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------------------- tile merge
+// The per-entry rows of a tiled predict call (include/mi355_yolo.h) -> one row list per source frame.  ONE BLOCK PER
+// FRAME, 16 waves, the NMS kernels' structure on rows instead of anchors:
+//   gather   wave w takes entries w, w + 16, ...: the entry's count, its first candidate and its origin are wave-uniform, lane r builds
+//            the key (~conf bits << 32) | (e * max_det + r) of row r -- keys are unique, so the sort below is the stable order
+//   sort     bitonic_sort in LDS up to 4096 keys (7 entries x 300 rows), bitonic_sort_hybrid on the frame's global key scratch beyond
+//   greedy   nms_greedy_body's wave-ballot pass: chunks of 64 candidates in key order, the test against the kept rows split over the
+//            waves, the pass inside the chunk run by every wave alike; a candidate dies iff an earlier kept row of the SAME class
+//            overlaps it by more than thr (tile_overlap_gt: IoS or IoU on the shifted boxes)
+//   rows     one 32-bit word per thread step, consecutive lanes on consecutive words of a row (plain vector stores, coalesced whether
+//            out_rows is HBM or pinned host memory): box and keypoint x / y get one fp32 add of the origin, every other word its bits
+// LDS: 32 KB of keys + 28 KB of kept rows (5 floats, class, slot per row; max_det <= 1024) + 1 KB of per-entry values = 61 KB of the
+// 64 KB a block may declare; one block per frame, so occupancy is not a consideration.  A frame's offsets fit 32 bits: the launcher
+// refuses more than MI355_TILE_MAX_CANDIDATES candidates per frame; the frame's bases are 64-bit.
+constexpr int TM_WAVES = NMS_SORT_THREADS / 64;
+
+__global__ __launch_bounds__(NMS_SORT_THREADS) void tile_merge_kernel(TileMergeArgs a) {
+    __shared__ unsigned long long skeys[NMS_LDS_KEYS];
+    __shared__ float kx1[NMS_MAX_DET], ky1[NMS_MAX_DET], kx2[NMS_MAX_DET], ky2[NMS_MAX_DET], kar[NMS_MAX_DET];
+    __shared__ int kcl[NMS_MAX_DET], ksl[NMS_MAX_DET];
+    __shared__ unsigned long long survive[2][TM_WAVES];
+    __shared__ int spre[MI355_TILE_MAX_ENTRIES + 1];
+    __shared__ float sox[MI355_TILE_MAX_ENTRIES], soy[MI355_TILE_MAX_ENTRIES];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int e0 = a.entry_off ? a.entry_off[f] : f * a.entries;
+    int E = a.entry_off ? a.entry_off[f + 1] - e0 : a.entries;
+    E = E < 0 ? 0 : (E > a.entries ? a.entries : E);                  // never more than the launcher sized the frame for
+    const int* counts = a.counts + e0;
+    const unsigned* rows = a.rows + (size_t)e0 * a.max_det * TILE_ROW_WORDS;
+    if (tid == 0) {
+        int at = 0;
+        for (int e = 0; e < E; ++e) { spre[e] = at; const int c = counts[e]; at += c < 0 ? 0 : (c > a.max_det ? a.max_det : c); }
+        spre[E] = at;
+    }
+    if (tid < E) { sox[tid] = (float)a.origins[2 * (e0 + tid)]; soy[tid] = (float)a.origins[2 * (e0 + tid) + 1]; }
+    __syncthreads();
+    const int n = spre[E];
+    int n2 = 1;
+    while (n2 < n) n2 <<= 1;
+    const bool in_lds = n2 <= NMS_LDS_KEYS;
+    // (a frame beyond the LDS form without scratch cannot get here: the launcher sizes key_stride from entries * max_det)
+    unsigned long long* keys = in_lds ? skeys : a.keys + (size_t)f * a.key_stride;
+    for (int e = wave; e < E; e += TM_WAVES) {                        // e, its count and its first candidate: the same in every lane
+        const int first = spre[e], cnt = spre[e + 1] - first;
+        const unsigned* er = rows + (size_t)e * a.max_det * TILE_ROW_WORDS;
+        for (int r = lane; r < cnt; r += 64)
+            keys[first + r] = ((unsigned long long)(~er[r * TILE_ROW_WORDS + 4]) << 32) | (unsigned)(e * a.max_det + r);
+    }
+    for (int i = n + tid; i < n2; i += NMS_SORT_THREADS) keys[i] = ~0ull;
+    __syncthreads();
+    if (n2 > 1) {
+        if (in_lds) bitonic_sort(skeys, n2, tid, NMS_SORT_THREADS);
+        else bitonic_sort_hybrid(keys, skeys, n2, tid);
+    }
+    __syncthreads();
+    // ---- greedy suppression in key order
+    int nk = 0, it = 0;
+    for (int base = 0; base < n && nk < a.max_det; base += 64, ++it) {
+        const int j = base + lane;
+        const bool valid = j < n;
+        int slot = 0, cls = 0;
+        TileBox me = {0.f, 0.f, 0.f, 0.f, 0.f};
+        if (valid) {
+            slot = (int)(keys[j] & 0xffffffffull);
+            const int e = slot / a.max_det;
+            const unsigned* p = rows + (size_t)slot * TILE_ROW_WORDS;
+            const float ox = sox[e], oy = soy[e];
+            me.x1 = __uint_as_float(p[0]) + ox; me.y1 = __uint_as_float(p[1]) + oy;
+            me.x2 = __uint_as_float(p[2]) + ox; me.y2 = __uint_as_float(p[3]) + oy;
+            me.area = (me.x2 - me.x1) * (me.y2 - me.y1);
+            cls = (int)p[5];
+        }
+        bool alive = valid;
+        for (int k = wave; k < nk; k += TM_WAVES) {                   // this wave's share of the kept rows
+            const TileBox kb = {kx1[k], ky1[k], kx2[k], ky2[k], kar[k]};
+            if (alive && kcl[k] == cls && tile_overlap_gt(kb, me, a.metric, a.thr)) alive = false;
+        }
+        const unsigned long long mine = __ballot(alive);
+        if (lane == 0) survive[it & 1][wave] = mine;
+        __syncthreads();
+        unsigned long long all = ~0ull;
+#pragma unroll
+        for (int w = 0; w < TM_WAVES; ++w) all &= survive[it & 1][w];
+        alive = (all >> lane) & 1ull;
+        unsigned long long mask = all;
+        while (mask) {                                                // greedy pass inside the chunk (every wave, identically)
+            const int jj = __ffsll((long long)mask) - 1;
+            TileBox kb;
+            kb.x1 = __shfl(me.x1, jj); kb.y1 = __shfl(me.y1, jj); kb.x2 = __shfl(me.x2, jj); kb.y2 = __shfl(me.y2, jj);
+            kb.area = __shfl(me.area, jj);
+            const int kc = __shfl(cls, jj);
+            if (wave == 0 && lane == jj) { kx1[nk] = me.x1; ky1[nk] = me.y1; kx2[nk] = me.x2; ky2[nk] = me.y2; kar[nk] = me.area; kcl[nk] = cls; ksl[nk] = slot; }
+            ++nk;
+            if (nk >= a.max_det) break;
+            if (alive && lane > jj && kc == cls && tile_overlap_gt(kb, me, a.metric, a.thr)) alive = false;
+            mask = __ballot(alive && lane > jj);
+        }
+        __syncthreads();                                              // the kept arrays are complete before the next chunk reads them
+    }
+    __syncthreads();
+    if (tid == 0) a.out_counts[f] = nk;
+    unsigned* out = a.out_rows + (size_t)f * a.max_det * TILE_ROW_WORDS;
+    for (int idx = tid; idx < nk * TILE_ROW_WORDS; idx += NMS_SORT_THREADS) {
+        const int k = idx / TILE_ROW_WORDS, q = idx - k * TILE_ROW_WORDS;
+        const int slot = ksl[k], e = slot / a.max_det;
+        out[idx] = tile_shift_word(rows[(size_t)slot * TILE_ROW_WORDS + q], q, sox[e], soy[e], a.nk, a.kdim);
+    }
+    if (a.out_tile_idx)
+        for (int k = tid; k < nk; k += NMS_SORT_THREADS) a.out_tile_idx[(size_t)f * a.max_det + k] = ksl[k] / a.max_det;
+}
+
+const char* launch_tile_merge(const TileMergeArgs& a, hipStream_t st) {
+    if (a.n_frames < 1 || a.entries < 1 || a.entries > MI355_TILE_MAX_ENTRIES) return "tile_merge: entries per frame must be in [1, 64]";
+    if (a.max_det < 1 || a.max_det > NMS_MAX_DET) return "tile_merge: max_det must be in [1, 1024]";
+    const long cand = (long)a.entries * a.max_det;
+    if (cand > MI355_TILE_MAX_CANDIDATES) return "tile_merge: more candidates per frame than the kernel's capacity";
+    if (cand > NMS_LDS_KEYS) {
+        long p2 = 1; while (p2 < cand) p2 <<= 1;
+        if (!a.keys || a.key_stride < p2 || (a.key_stride & (a.key_stride - 1))) return "tile_merge: key scratch missing or too small";
+    }
+    if (a.nk < 0 || a.nk > MI355_MAX_KPT_FLOATS || !(a.kdim == 0 || a.kdim == 2 || a.kdim == 3)) return "tile_merge: bad keypoint shape";
+    if (a.metric != MI355_TILE_IOS && a.metric != MI355_TILE_IOU) return "tile_merge: unknown metric";
+    if (!a.rows || !a.counts || !a.origins || !a.out_rows || !a.out_counts) return "tile_merge: null argument";
+    hipLaunchKernelGGL(tile_merge_kernel, dim3(a.n_frames), dim3(NMS_SORT_THREADS), 0, st, a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }

@@ -374,15 +374,24 @@ class YOLO:
 
     def predict(self, source=None, conf: Optional[float] = None, iou: float = 0.7, classes=None, max_det: int = 300,
                 imgsz: int = 640, half: Optional[bool] = None, verbose: bool = False, stream: bool = False,
-                feats: Optional[bool] = None, **kwargs) -> List[Results]:
+                feats: Optional[bool] = None, tile=None, overlap: float = 0.2, full_frame: bool = True, tile_iou: float = 0.5,
+                tile_metric: str = "ios", **kwargs) -> List[Results]:
         """``model.predict`` / ``model(...)``: ultralytics/engine/model.py:Model.predict.
         ``half=True`` runs the fp16-storage engine (fp32 accumulate; results differ from fp32 by fp16 rounding);
         ``None`` = the precision the model was constructed with (fp32 unless ``YOLO(..., half=True)``).
         ``feats=True`` also fills ``Results.feats`` (float32 [M, s]: the detector's own appearance embedding of every box);
-        ``None`` = as constructed.  Boxes and keypoints are bit for bit the same either way."""
+        ``None`` = as constructed.  Boxes and keypoints are bit for bit the same either way.
+        ``tile`` (int or (tile_h, tile_w)): tiled inference for high-resolution frames -- every frame is cut into tiles overlapping by
+        ``overlap`` (a fraction of the tile), the tiles (and with ``full_frame`` the frame itself) run through ONE detector pass at
+        ``imgsz`` each, and their rows are merged per frame on the GPU: a row dies when an earlier row of its class overlaps it by more
+        than ``tile_iou`` under ``tile_metric`` ("ios": intersection over the smaller box, "iou").  ``Results.tile_idx`` / ``.tiles``
+        say which entry every row came from.  ``None`` (default): the call as it always was."""
         if isinstance(imgsz, (list, tuple)):
             imgsz = int(max(imgsz))
         conf = 0.25 if conf is None else float(conf)
+        if tile is not None:
+            batch, originals = self._as_tile_batch(source)
+            return self._predict_tiled(batch, originals, conf, iou, classes, max_det, imgsz, half, feats, tile, overlap, full_frame, tile_iou, tile_metric)
         batch, originals = self._as_batch(source)
         return self._predict_batch(batch, originals, conf, iou, classes, max_det, imgsz, half, feats)
 
@@ -404,9 +413,14 @@ class YOLO:
     def _predict_batch(self, batch, originals, conf, iou, classes, max_det, imgsz, half, feats=None) -> List[Results]:
         fout = []
         rows, counts, shape = self._infer_rows(batch, conf, float(iou), classes, int(max_det), int(imgsz), half, feats, fout)
+        return self._build_results(rows, counts, shape, originals, fout)
+
+    def _build_results(self, rows, counts, shape, originals, fout, tile_idx=None, tiles=None) -> List[Results]:
+        """rows [n, max_det, 58 words] and counts [n] of a call -> its ``Results``; a tiled call adds every frame's entry indices
+        ``tile_idx`` [n, max_det] and entry list ``tiles`` (one int32 [E, 4] array per frame)"""
         t = _lib.Timing()
         _lib.lib().mi355_yolo_last_timing(self._last_handle, C.byref(t))
-        per_img_ms = t.total_ms / max(1, int(batch.shape[0]))
+        per_img_ms = t.total_ms / max(1, len(counts))
         out = []
         for i in range(len(counts)):
             r = rows[i, :counts[i]]
@@ -420,13 +434,102 @@ class YOLO:
                           boxes=torch.from_numpy(data), keypoints=kp.clone() if kp is not None else None,
                           orig_shape=shape[i] if isinstance(shape, list) else shape,
                           speed={"preprocess": 0.0, "inference": per_img_ms, "postprocess": 0.0},
-                          anchor_idx=ints[:, 1].copy(), feats=fout[0][i, :counts[i]].copy() if fout else None)
+                          anchor_idx=ints[:, 1].copy(), feats=fout[0][i, :counts[i]].copy() if fout else None,
+                          tile_idx=tile_idx[i, :counts[i]].copy() if tile_idx is not None else None,
+                          tiles=tiles[i] if tiles is not None else None)
             if kp is not None:
                 res.keypoints_raw = kp.numpy()          # before Keypoints() zeroes x,y of joints with conf < 0.5
             out.append(res)
         return out
 
     __call__ = predict
+
+    # ---- tiled predict -----------------------------------------------------------------------------------------
+    @staticmethod
+    def _as_tile_batch(source):
+        """The frames of a tiled call, each passed by pointer with its own row stride: -> (_Ragged or _YuvBatch, originals or None).
+        Takes what :meth:`predict` takes; `_as_batch` is not involved, so calls without ``tile`` see no change."""
+        yuv = as_frames(source)
+        if yuv is not None:
+            return YOLO._YuvBatch(yuv), None
+        if isinstance(source, torch.Tensor):
+            if source.dtype != torch.uint8 or source.ndim not in (3, 4) or source.shape[-1] != 3:
+                raise ValueError("tensor sources must be uint8 [N,H,W,3] BGR frames")
+            source = [source] if source.ndim == 3 else list(source)
+        elif isinstance(source, np.ndarray):
+            if source.dtype != np.uint8 or source.ndim not in (3, 4) or source.shape[-1] != 3:
+                raise ValueError("frames must be uint8 arrays of shape [H,W,3] (BGR, as cv2 delivers them)")
+            source = [source] if source.ndim == 3 else list(source)
+        if not isinstance(source, (list, tuple)):
+            raise TypeError(f"unsupported source type {type(source).__name__}: pass decoded BGR uint8 frames")
+        if not source:
+            raise ValueError("empty source")
+        on_dev = [isinstance(f, torch.Tensor) and f.is_cuda for f in source]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("a list of frames must be all host arrays or all CUDA tensors")
+        if not any(on_dev):
+            source = [f.numpy() if isinstance(f, torch.Tensor) else f for f in source]
+        return YOLO._Ragged(source, all(on_dev)), (None if all(on_dev) else list(source))
+
+    def _predict_tiled(self, batch, originals, conf, iou, classes, max_det, imgsz, half, feats, tile, overlap=0.2, full_frame=True,
+                       tile_iou=0.5, tile_metric="ios") -> List[Results]:
+        """One tiled call (``mi355_yolo_infer_tiled`` / ``_tiled_yuv``): every argument is checked here, before any launch."""
+        from . import ops
+        if self.feats if feats is None else feats:
+            raise ValueError("feats=True cannot be combined with tile: a merged row's anchor index no longer identifies its map position")
+        th, tw, oy, ox = ops.tile_overlap_px(tile, overlap)
+        if tile_metric not in ops.TILE_METRICS:
+            raise ValueError(f"tile_metric must be 'ios' or 'iou', got {tile_metric!r}")
+        if isinstance(tile_iou, bool) or not isinstance(tile_iou, (int, float, np.integer, np.floating)):
+            raise TypeError(f"tile_iou must be a number in [0, 1], got {tile_iou!r}")
+        if not 0 <= float(tile_iou) <= 1:
+            raise ValueError(f"tile_iou must be in [0, 1], got {tile_iou!r}")
+        max_det, imgsz = int(max_det), int(imgsz)
+        tiles = []
+        for h, w in batch.shapes:
+            g = self._grid_px(h, w, th, tw, oy, ox)
+            if full_frame:
+                g = np.concatenate([g, np.array([[0, 0, w, h]], np.int32)])
+            if len(g) > _lib.TILE_MAX_ENTRIES or len(g) * max(1, max_det) > _lib.TILE_MAX_CANDIDATES:
+                raise ValueError(f"tile={tile!r} cuts a {h}x{w} frame into {len(g)} entries: at most {_lib.TILE_MAX_ENTRIES} entries and "
+                                 f"{_lib.TILE_MAX_CANDIDATES} entries x max_det candidates per frame are merged")
+            tiles.append(g)
+        opts = _lib.TileOpts(struct_size=C.sizeof(_lib.TileOpts), tile_h=th, tile_w=tw, overlap_y_px=oy, overlap_x_px=ox,
+                             full_frame=int(bool(full_frame)), metric=ops.TILE_METRICS[tile_metric], thr=float(tile_iou))
+        lib = _lib.lib()
+        hnd = self._handle(half, False)
+        n = int(batch.shape[0])
+        rows = np.empty((n, max_det, _lib.DET_WORDS), dtype=np.float32)    # only rows[i, :counts[i]] are written / meaningful
+        counts = np.zeros(n, dtype=np.int32)
+        tile_idx = np.full((n, max_det), -1, np.int32)
+        cls_arr, ncls = None, 0
+        if classes is not None:
+            cl = [int(classes)] if np.isscalar(classes) else [int(c) for c in classes]
+            cls_arr, ncls = (C.c_int * len(cl))(*cl), len(cl)
+        cp = counts.ctypes.data_as(C.POINTER(C.c_int))
+        with self._lock:
+            self._last_handle = hnd
+            if isinstance(batch, YOLO._YuvBatch):
+                batch.check_device(self.device)
+                _lib.check(lib.mi355_yolo_infer_tiled_yuv(hnd, batch.structs, int(batch.on_device), n, C.byref(opts), float(conf), float(iou), cls_arr,
+                                                          ncls, max_det, imgsz, rows.ctypes.data, max_det, cp, tile_idx.ctypes.data))
+            else:
+                if batch.on_device and batch.frames is not None:
+                    if any(f.device.index != self.device for f in batch.frames):
+                        raise ValueError("frames live on a different GPU than the engine")
+                    torch.cuda.current_stream(batch.frames[0].device).synchronize()   # engine runs on its own stream
+                _lib.check(lib.mi355_yolo_infer_tiled(hnd, *batch.args(), C.byref(opts), float(conf), float(iou), cls_arr, ncls, max_det, imgsz,
+                                                      rows.ctypes.data, max_det, cp, tile_idx.ctypes.data))
+            return self._build_results(rows, counts, list(batch.shapes), originals, [], tile_idx, tiles)
+
+    @staticmethod
+    def _grid_px(h, w, th, tw, oy, ox) -> np.ndarray:
+        """``mi355_tile_grid`` with the overlaps already in pixels"""
+        cnt = C.c_int()
+        _lib.check(_lib.lib().mi355_tile_grid(int(h), int(w), th, tw, oy, ox, None, 0, C.byref(cnt)))
+        g = np.zeros((cnt.value, 4), np.int32)
+        _lib.check(_lib.lib().mi355_tile_grid(int(h), int(w), th, tw, oy, ox, g.ctypes.data, cnt.value, C.byref(cnt)))
+        return g
 
     def track(self, source=None, persist: bool = False, show: bool = False, conf: Optional[float] = None, tracker=None, **kwargs
               ) -> List[Results]:
@@ -435,7 +538,9 @@ class YOLO:
         ``tracker``: a ``botsort.yaml``-style file path or dict (``tracker.tracker_config`` says which keys are honoured and refuses the
         rest); it configures the tracker this call creates.  A ``persist=True`` call that continues a tracker may repeat the argument
         (it is not parsed again) or omit it; settings that differ from the continued tracker's are a ``ValueError``, not ignored.
-        With ``with_reid: True`` the detector pass also produces its per-box embeddings and the tracker matches on them."""
+        With ``with_reid: True`` the detector pass also produces its per-box embeddings and the tracker matches on them.
+        ``tile=...`` (with ``overlap``, ``full_frame``, ``tile_iou``, ``tile_metric``) is passed on to :meth:`predict`: the tracker consumes
+        the merged rows of the tiled call (not together with ``with_reid``: a tiled call has no features)."""
         from .tracker import BYTETracker
         kwargs.pop("batch", None)
         conf = 0.1 if conf is None else conf
@@ -465,7 +570,14 @@ class YOLO:
             # the other, tools/track_timeline.py)
             share = os.environ.get("MI355_TRACK_SHARED_FRAME", "1") != "0"            # A/B and tests only
             dev = self._tracker.gmc.pending_device_frame() if share and isinstance(frame, np.ndarray) and frame.ndim == 3 else None
-            if dev is not None and dev[1:] == tuple(frame.shape[:2]) and not kwargs.get("stream"):
+            if dev is not None and dev[1:] == tuple(frame.shape[:2]) and not kwargs.get("stream") and kwargs.get("tile") is not None:
+                # tiled: the tiles are cut from the same uploaded copy, and the tracker consumes the merged rows
+                imgsz = kwargs.get("imgsz", 640)
+                res = self._predict_tiled(YOLO._RaggedDevice([dev[0]], [dev[1:]]), None, float(conf), kwargs.get("iou", 0.7), kwargs.get("classes"),
+                                          kwargs.get("max_det", 300), int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"),
+                                          kwargs.get("feats"), kwargs["tile"],
+                                          **{k: kwargs[k] for k in ("overlap", "full_frame", "tile_iou", "tile_metric") if k in kwargs})[0]
+            elif dev is not None and dev[1:] == tuple(frame.shape[:2]) and not kwargs.get("stream"):
                 imgsz = kwargs.get("imgsz", 640)
                 res = self._predict_batch(YOLO._DeviceFrames(dev[0], 1, dev[1], dev[2]), None, float(conf), kwargs.get("iou", 0.7), kwargs.get("classes"),
                                           kwargs.get("max_det", 300), int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"),

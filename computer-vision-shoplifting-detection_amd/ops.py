@@ -213,6 +213,58 @@ def pose_windows(poses: np.ndarray, starts, seq_len: int, num_keypoints: int, ne
     return out
 
 
+def tile_overlap_px(tile, overlap: float):
+    """``tile`` (int or (tile_h, tile_w)) and the fractional ``overlap`` of ``predict(tile=...)`` -> (tile_h, tile_w, overlap_y_px,
+    overlap_x_px): the overlap is turned into pixels once, here, as ``int(overlap * tile)`` per axis; the C ABI takes pixels.  Refuses
+    (TypeError / ValueError naming the argument) a tile that is no int or pair of ints or is below 32, and an overlap outside [0, 1)."""
+    if isinstance(tile, (bool, float)) or (not isinstance(tile, (int, np.integer)) and not (
+            isinstance(tile, (tuple, list)) and len(tile) == 2 and all(isinstance(t, (int, np.integer)) and not isinstance(t, bool) for t in tile))):
+        raise TypeError(f"tile must be an int or (tile_h, tile_w), got {tile!r}")
+    th, tw = (int(tile), int(tile)) if isinstance(tile, (int, np.integer)) else (int(tile[0]), int(tile[1]))
+    if th < 32 or tw < 32:
+        raise ValueError(f"tile must be >= 32, got {tile!r}")
+    if isinstance(overlap, bool) or not isinstance(overlap, (int, float, np.integer, np.floating)):
+        raise TypeError(f"overlap must be a number in [0, 1), got {overlap!r}")
+    if not 0 <= float(overlap) < 1:
+        raise ValueError(f"overlap must be in [0, 1), got {overlap!r}")
+    return th, tw, int(float(overlap) * th), int(float(overlap) * tw)
+
+
+def tile_grid(height: int, width: int, tile, overlap: float = 0.2) -> np.ndarray:
+    """The tile grid of ``predict(tile=..., overlap=...)`` for a ``height`` x ``width`` frame (``mi355_tile_grid``, host arithmetic
+    only): int32 [T, 4] rows x, y, w, h, row-major (y outer, x inner)."""
+    th, tw, oy, ox = tile_overlap_px(tile, overlap)
+    cnt = C.c_int()
+    _lib.check(_lib.lib().mi355_tile_grid(int(height), int(width), th, tw, oy, ox, None, 0, C.byref(cnt)))
+    out = np.zeros((cnt.value, 4), np.int32)
+    _lib.check(_lib.lib().mi355_tile_grid(int(height), int(width), th, tw, oy, ox, out.ctypes.data, cnt.value, C.byref(cnt)))
+    return out
+
+
+TILE_METRICS = {"ios": _lib.TILE_IOS, "iou": _lib.TILE_IOU}
+
+
+def tile_merge(rows: np.ndarray, counts, origins, kdim: int = 0, metric: str = "ios", thr: float = 0.5, device: int = 0):
+    """The merge kernel of a tiled predict alone (csrc/post_kernels.hip: one block per source frame): ``rows`` float32
+    [F, E, max_det, 58] (the words of ``mi355_det``; cls and anchor_idx are int32 bits), ``counts`` [F, E], ``origins`` [F, E, 2] = x, y
+    of every entry -> (merged rows [F, max_det, 58], counts [F], tile_idx int32 [F, max_det]).  Slots at or beyond a frame's count come
+    back as SENTINEL_BITS (tile_idx: -1).  ``device=-1`` runs the same per-frame routine on the host (no GPU is touched)."""
+    r = np.ascontiguousarray(rows, dtype=np.float32)
+    if r.ndim != 4 or r.shape[3] != _lib.DET_WORDS:
+        raise ValueError(f"rows must be [F, E, max_det, {_lib.DET_WORDS}], got {tuple(r.shape)}")
+    F, E, md = r.shape[:3]
+    cnt = np.ascontiguousarray(counts, dtype=np.int32).reshape(F, E)
+    org = np.ascontiguousarray(origins, dtype=np.int32).reshape(F, E, 2)
+    if metric not in TILE_METRICS:
+        raise ValueError(f"tile_metric must be 'ios' or 'iou', got {metric!r}")
+    out = _sentinel((F, md, _lib.DET_WORDS))
+    oc = np.zeros(F, np.int32)
+    idx = np.full((F, md), -1, np.int32)
+    _lib.check(_lib.lib().mi355_op_tile_merge(int(device), r.ctypes.data, cnt.ctypes.data, org.ctypes.data, F, E, md, int(kdim),
+                                              TILE_METRICS[metric], float(thr), out.ctypes.data, oc.ctypes.data, idx.ctypes.data))
+    return out, oc, idx
+
+
 class SparseBoxResult:
     """What :func:`sparse_box` hands back: ``pred`` [n, A, no]; per level ``mid`` [n, h, w, mid_cs], ``dil`` / ``cand`` (the first
     min(count, cap) list entries, int32, in the kernel's order), ``n_dil`` / ``n_cand`` (the counts the device holds, also beyond

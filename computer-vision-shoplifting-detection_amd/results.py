@@ -162,7 +162,8 @@ class Results:
     """One image's predictions (``list[Results]`` is what ``model(frame)`` / ``model.track(frame)`` return)."""
 
     def __init__(self, orig_img: Optional[np.ndarray], path: str, names: Dict[int, str], boxes=None, keypoints=None,
-                 orig_shape: Optional[Tuple[int, int]] = None, speed: Optional[dict] = None, anchor_idx=None, feats=None):
+                 orig_shape: Optional[Tuple[int, int]] = None, speed: Optional[dict] = None, anchor_idx=None, feats=None,
+                 tile_idx=None, tiles=None):
         self.orig_img = orig_img
         self.orig_shape = tuple(orig_shape) if orig_shape is not None else tuple(orig_img.shape[:2])
         self.boxes = Boxes(boxes, self.orig_shape) if boxes is not None else None
@@ -175,6 +176,11 @@ class Results:
         # predict(feats=True): float32 [M, s], row i the appearance embedding of box i, read from the Detect head's input maps
         # (Ultralytics' Results.feats under with_reid / model: auto); None otherwise
         self.feats = feats
+        # predict(tile=...): tiles = int32 [E, 4] rows x, y, w, h of the frame's entries (its tiles, row-major, then the frame itself when
+        # full_frame is set); tile_idx = int32 [M], the entry every row came from (anchor_idx is then the anchor within that entry's
+        # own canvas).  None for an untiled call.
+        self.tile_idx = tile_idx
+        self.tiles = tiles
 
     def __len__(self):
         return len(self.boxes) if self.boxes is not None else 0
@@ -188,6 +194,10 @@ class Results:
         if self.feats is not None:
             ix = idx.numpy() if isinstance(idx, torch.Tensor) else idx
             r.feats = self.feats[[ix]] if isinstance(ix, (int, np.integer)) else self.feats[ix]       # an integer keeps one row, as Boxes does
+        if self.tile_idx is not None:
+            ix = idx.numpy() if isinstance(idx, torch.Tensor) else idx
+            r.tile_idx = self.tile_idx[[ix]] if isinstance(ix, (int, np.integer)) else self.tile_idx[ix]
+        r.tiles = self.tiles
         return r
 
     def update(self, boxes=None):
@@ -205,4 +215,5 @@ class Results:
         r.boxes = self.boxes.numpy() if self.boxes is not None else None
         r.keypoints = self.keypoints.numpy() if self.keypoints is not None else None
         r.feats = self.feats
+        r.tile_idx, r.tiles = self.tile_idx, self.tiles
         return r

@@ -217,6 +217,67 @@ int  mi355_yolo_infer_yuv_device_async(mi355_yolo* h, const mi355_yuv_frame* fra
  * the launch changed one.  device_id = -1 runs the same per-block routine in a host loop and touches no GPU. */
 int  mi355_op_yuv_to_bgr(int device_id, const mi355_yuv_frame* frames, int n, uint8_t* const* bgr_out);
 
+/* ---- tiled predict for high-resolution frames --------------------------------------------------------------------
+ * A frame is cut into overlapping tiles, every tile (and, with full_frame, the frame itself) runs through ONE detector pass as an entry
+ * of the mixed-shape call above, and the per-entry rows are merged per frame on the GPU; only the merged rows come back.
+ *
+ * Tile grid, pure integer arithmetic.  Along an axis of length L with tile t and overlap o pixels (0 <= o < t): positions start at
+ * p_0 = 0 and advance by t - o; a position is kept while p + t < L; the first position with p + t >= L is the last one and is replaced
+ * by max(0, L - t); every tile's extent on that axis is min(t, L).  Tiles are listed row-major (y outer, x inner).
+ *   mi355_tile_grid   host only.  out_xywh[4 * i ..] = x, y, w, h of tile i (out_xywh may be NULL to query *count); cap counts tiles;
+ *                     MI355_EINVAL: a non-positive size, an overlap outside [0, tile), more tiles than cap.
+ *
+ * Entry list of a call: for each frame in order its tiles, then the frame itself when full_frame is set: E = T + 1 (or T) entries per
+ * frame.  The concatenated list is treated exactly as mi355_yolo_infer_multi treats n frames: all entries of one shape -> the rect
+ * canvas, otherwise the square one; every entry has its own NMS (conf, iou, classes, max_det) and is scaled back to its own pixels.
+ *
+ * Merge, per source frame, fp32 (FP contraction off).  Candidates: every kept row of the frame's entries.  Row r of entry e with origin
+ * (ox, oy) (the full frame: (0, 0)) is shifted: x1 + (float)ox, y1 + (float)oy, x2 + (float)ox, y2 + (float)oy, and with kdim >= 2 each
+ * keypoint's x and y likewise (one fp32 add each); keypoint confidence, conf, cls and anchor_idx pass through as bits.  Order: ascending
+ * key (~conf_bits << 32) | (e * max_det + r), i.e. descending conf, ties by ascending slot.  Greedy in that order: a candidate dies iff
+ * an earlier KEPT candidate of the same cls has metric > thr, with w = max(0, min(x2) - max(x1)), h likewise, inter = w * h (rounded to
+ * fp32), area = (x2 - x1) * (y2 - y1) on the shifted coordinates,
+ *   MI355_TILE_IOS   inter / min(area_i, area_j)        (min(a, b) = a < b ? a : b)
+ *   MI355_TILE_IOU   inter / (area_i + area_j - inter)
+ * 0 / 0 is NaN and NaN > thr is false: a zero-area box neither suppresses nor is suppressed.  The merge stops after max_det kept rows.
+ * Capacity of the merge kernel: E <= MI355_TILE_MAX_ENTRIES entries per frame and E * max_det <= MI355_TILE_MAX_CANDIDATES candidates
+ * per frame; beyond either the calls below refuse with MI355_EINVAL before any launch.
+ *
+ *   mi355_yolo_infer_tiled   frames / heights / widths / row_strides / frames_on_device / n and conf .. imgsz as mi355_yolo_infer_multi.
+ *        HOST frames are uploaded ONCE each, ahead of the first chunk, into a device buffer of the engine (rows width * 3 apart); the
+ *        entries are descriptors into that copy -- or into the caller's device frames -- (pointer offset + the parent's row stride),
+ *        nothing else is copied.  The entry rows stay on the device; ONE merge launch behind the last chunk's NMS.
+ *        out_rows [n][cap] merged rows in frame pixels, kept order; anchor_idx = the anchor within the entry's own canvas;
+ *        out_counts [n]; out_tile_idx [n][cap] (or NULL) = entry index of every row within its frame (T = the full frame).
+ *        An engine with obj_feats runs the call unchanged and produces no features for it.
+ *   mi355_yolo_infer_tiled_yuv   the same on NV12 / I420 frames: all n frames are converted first (one launch) into the engine's dense
+ *        BGR buffer, which the tiles are then cut from.
+ *   mi355_op_tile_merge   the merge alone (parity tests): rows [n_frames][entries][max_det] (58 words each), counts [n_frames][entries],
+ *        origins [n_frames][entries][2] = ox, oy; kdim 0, 2 or 3: floats j < (51 / kdim) * kdim of kpt[] are keypoints.  out_rows
+ *        [n_frames][max_det], out_counts [n_frames], out_tile_idx [n_frames][max_det]; slots at or beyond the count keep the caller's
+ *        bits.  Host memory in and out.  device = -1 runs the same per-frame routine on the host and touches no GPU. */
+#define MI355_TILE_IOS 0
+#define MI355_TILE_IOU 1
+#define MI355_TILE_MAX_ENTRIES 64
+#define MI355_TILE_MAX_CANDIDATES 65536
+typedef struct mi355_tile_opts {
+    int struct_size;                    /* sizeof(mi355_tile_opts) */
+    int tile_h, tile_w;                 /* >= 32 */
+    int overlap_y_px, overlap_x_px;     /* 0 <= overlap < tile */
+    int full_frame;                     /* 1: the frame itself is the last entry of its list */
+    int metric;                         /* MI355_TILE_IOS / MI355_TILE_IOU */
+    float thr;                          /* in [0, 1] */
+} mi355_tile_opts;
+int  mi355_tile_grid(int height, int width, int tile_h, int tile_w, int overlap_y_px, int overlap_x_px, int* out_xywh, int cap, int* count);
+int  mi355_yolo_infer_tiled(mi355_yolo* h, const uint8_t* const* frames, const int* heights, const int* widths, const int* row_strides,
+                            int frames_on_device, int n, const mi355_tile_opts* tile, float conf, float iou, const int* classes,
+                            int n_classes, int max_det, int imgsz, mi355_det* out_rows, int cap, int* out_counts, int* out_tile_idx);
+int  mi355_yolo_infer_tiled_yuv(mi355_yolo* h, const mi355_yuv_frame* frames, int frames_on_device, int n, const mi355_tile_opts* tile,
+                                float conf, float iou, const int* classes, int n_classes, int max_det, int imgsz, mi355_det* out_rows,
+                                int cap, int* out_counts, int* out_tile_idx);
+int  mi355_op_tile_merge(int device, const mi355_det* rows, const int* counts, const int* origins, int n_frames, int entries, int max_det,
+                         int kdim, int metric, float thr, mi355_det* out_rows, int* out_counts, int* out_tile_idx);
+
 /* The decoded pre-NMS head tensor, exactly the layout Detect/Pose.forward returns: out[n][4+nc+nk][A] fp32
  * (xywh in letterboxed pixels, sigmoid class scores, decoded keypoints).  For parity tests.
  * out may be NULL to query *out_channels / *out_anchors for the given frame size. */
