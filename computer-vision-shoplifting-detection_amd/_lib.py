@@ -61,6 +61,17 @@ class TileOpts(C.Structure):
                 ("full_frame", C.c_int), ("metric", C.c_int), ("thr", C.c_float)]
 
 
+class MotionOpts(C.Structure):
+    """mi355_motion_opts: the block grid and the thresholds of a motion gate"""
+    _fields_ = [("struct_size", C.c_int), ("block", C.c_int), ("level", C.c_float), ("min_blocks", C.c_int), ("max_skip", C.c_int)]
+
+
+class MotionFrame(C.Structure):
+    """mi355_motion_frame: one camera's frame of a tick (bytes_per_pixel 3: BGR, 1: a Y plane)"""
+    _fields_ = [("data", C.c_void_p), ("height", C.c_int), ("width", C.c_int), ("row_stride", C.c_int), ("bytes_per_pixel", C.c_int)]
+
+
+MOTION_MAX_CAMERAS = 64                 # MI355_MOTION_MAX_CAMERAS
 TILE_IOS, TILE_IOU = 0, 1               # MI355_TILE_IOS / MI355_TILE_IOU
 TILE_MAX_ENTRIES, TILE_MAX_CANDIDATES = 64, 65536
 PIX_NV12, PIX_I420 = 1, 2               # MI355_PIX_*
@@ -212,6 +223,12 @@ SIGNATURES = {
     "mi355_shopformer_decoder_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mi355_pose_windows": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mi355_shopformer_score_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "mi355_motion_gate_create": (C.c_int, [C.c_int, C.c_int, _P(MotionOpts), _P(C.c_void_p)]),
+    "mi355_motion_gate_destroy": (None, [C.c_void_p]),
+    "mi355_motion_gate_update": (C.c_int, [C.c_void_p, _P(_P(MotionFrame)), C.c_int, _i32p, _i32p]),
+    "mi355_motion_gate_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _i32p, _i32p]),
+    "mi355_motion_gate_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "mi355_op_motion_grid": (C.c_int, [C.c_int, _P(MotionFrame), C.c_int, C.c_int, _P(C.c_void_p)]),
     "mi355_op_nms": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,
                                C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
     "mi355_op_nms_ex": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,

@@ -631,10 +631,20 @@ class YOLO:
         (``gmc.MultiGMC``), whose uploaded frames the detector reads in place.  ``persist=True`` continues the cameras' tracks (the list
         length is the number of cameras and must not change); otherwise every camera starts afresh.  Keyword arguments: ``iou``,
         ``classes``, ``max_det``, ``imgsz``, ``half``, ``feats`` as in :meth:`predict`, ``tracker`` as in :meth:`track` (every camera's
-        tracker gets the same settings); ``show`` / ``verbose`` are accepted and ignored; anything else is a ``TypeError``."""
+        tracker gets the same settings); ``show`` / ``verbose`` are accepted and ignored; anything else is a ``TypeError``.
+
+        ``motion_gate``: None (default) -- the call as it always was; True, a dict of ``MotionGate`` options (``block``,
+        ``level``, ``min_blocks``, ``max_skip``) or a :class:`MotionGate` for exactly this many cameras -- the detector runs only on the
+        present cameras the gate calls moving (not at all when there are none), and a static camera's tracker steps, with this tick's warp,
+        on the rows the detector last produced for that camera: it ages, predicts and keeps its ids as if the detector had returned the
+        same rows again.  The gate reads the frames the motion compensation uploaded.  Every returned ``Results`` then carries
+        ``motion = {"moving", "changed", "skipped"}`` and, for a static camera, this tick's frame as ``orig_img``.  The letterbox geometry
+        follows the list handed to the detector, as with absent cameras: moving frames of one shape take the rect path, of mixed shapes
+        the square canvas.  ``persist=False`` resets the gate along with the trackers."""
         from .gmc import MultiGMC
         from .tracker import BYTETracker
         tracker = kwargs.pop("tracker", None)
+        motion_gate = kwargs.pop("motion_gate", None)
         unknown = set(kwargs) - {"iou", "classes", "max_det", "imgsz", "half", "feats", "show", "verbose"}
         if unknown:                                              # show / verbose are accepted and ignored, as in track()
             raise TypeError(f"track_cameras: unsupported argument(s) {sorted(unknown)} (iou, classes, max_det, imgsz, half pass through)")
@@ -651,6 +661,7 @@ class YOLO:
                 raise ValueError("frames must be uint8 arrays of shape [H,W,3] (BGR, as cv2 delivers them), or None for an absent camera")
             if not f.flags.c_contiguous:
                 frames[i] = np.ascontiguousarray(f)
+        spec = self._motion_gate_spec(motion_gate, n)
         cams = getattr(self, "_cameras", None)
         if persist and cams is not None and len(cams[0]) != n:
             raise ValueError(f"{n} frames for {len(cams[0])} tracked cameras: the list length is the number of cameras (None = absent)")
@@ -660,6 +671,7 @@ class YOLO:
             cams = self._cameras = ([BYTETracker(gmc_method=None, **cfg) for _ in range(n)], MultiGMC(n, device=self.device))
         trackers, gmc = cams
         reid = trackers[0].with_reid
+        gate = self._camera_gate_for(spec, n, restart=cfg is not None)
         present = [i for i, f in enumerate(frames) if f is not None]
         out: List[Optional[Results]] = [None] * n
         if not present:
@@ -668,30 +680,110 @@ class YOLO:
         # enqueued before the detector pass, which reads the frames that step has just uploaded; RANSAC runs on host threads meanwhile
         gmc.begin(frames)
         share = os.environ.get("MI355_TRACK_SHARED_FRAME", "1") != "0"                # A/B and tests only
-        originals = [frames[i] for i in present]
+        run = present                                            # the cameras the detector sees
         try:
             dev = gmc.pending_device_frames() if share else None
             if dev is not None and any(dev[i] is None for i in present):
                 raise RuntimeError("track_cameras: the motion compensation's pending tick is not this call's")
+            if gate is not None:
+                # the gate's launch reads the frames that step uploaded: their pointers came back behind the event wait for that upload
+                # (mi355_gmc_multi_frames), which is what orders the detector pass behind it as well
+                g, cache = gate
+                if dev is not None and g.device == self.device:
+                    moving, changed = g._update_device_bgr(dev, [None if f is None else f.shape[:2] for f in frames])
+                else:
+                    moving, changed = g.update(frames)
+                run = [i for i in present if moving[i] or cache[i] is None]
         except BaseException:
             gmc.reset()
             raise
-        if dev is not None:
-            batch = YOLO._RaggedDevice([dev[i] for i in present], [f.shape[:2] for f in originals])
-        else:
-            batch = YOLO._Ragged(originals, False)
-        imgsz = kwargs.get("imgsz", 640)
-        try:
-            res = self._predict_batch(batch, originals, conf, kwargs.get("iou", 0.7), kwargs.get("classes"), kwargs.get("max_det", 300),
-                                      int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"),
-                                      True if reid else kwargs.get("feats"))
-        except BaseException:
-            gmc.reset()                                          # the enqueued tick must not be taken for the next call's frames
-            raise
+        originals = [frames[i] for i in run]
+        res = []
+        if run:
+            if dev is not None:
+                batch = YOLO._RaggedDevice([dev[i] for i in run], [f.shape[:2] for f in originals])
+            else:
+                batch = YOLO._Ragged(originals, False)
+            imgsz = kwargs.get("imgsz", 640)
+            try:
+                res = self._predict_batch(batch, originals, conf, kwargs.get("iou", 0.7), kwargs.get("classes"), kwargs.get("max_det", 300),
+                                          int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"),
+                                          True if reid else kwargs.get("feats"))
+            except BaseException:
+                gmc.reset()                                      # the enqueued tick must not be taken for the next call's frames
+                if gate is not None:
+                    gate[0].reset()                              # its references are this tick's grids, for which no rows exist
+                raise
         warps = gmc.apply(frames)
-        for r, i in zip(res, present):
-            out[i] = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i], feats=r.feats if reid else None))    # an empty frame still steps
+        if gate is None:
+            for r, i in zip(res, present):
+                out[i] = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i], feats=r.feats if reid else None))    # an empty frame still steps
+            return out
+        fresh = dict(zip(run, res))
+        for i in present:
+            r = fresh.get(i)
+            if r is not None:
+                cache[i] = self._result_snapshot(r)
+            else:
+                r = self._result_from_snapshot(cache[i], frames[i])    # the rows the detector last produced for this camera, on this tick's frame
+            r = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i], feats=r.feats if reid else None))
+            r.motion = {"moving": bool(moving[i]), "changed": int(changed[i]), "skipped": i not in fresh}
+            out[i] = r
         return out
+
+    # ---- motion gate of track_cameras --------------------------------------------------------------------------
+    @staticmethod
+    def _motion_gate_spec(arg, n: int):
+        """``motion_gate=`` of :meth:`track_cameras` -> None, the validated options of the gate to create, or the caller's MotionGate"""
+        if arg is None or arg is False:
+            return None
+        from .motion import OPTIONS, MotionGate, check_options
+        if arg is True:
+            return check_options()
+        if isinstance(arg, MotionGate):
+            if arg.n != n:
+                raise ValueError(f"motion_gate: a MotionGate for {arg.n} cameras given to a call with {n} cameras")
+            return arg
+        if isinstance(arg, dict):
+            unknown = sorted(set(arg) - set(OPTIONS))
+            if unknown:
+                raise ValueError(f"motion_gate: unknown option(s) {unknown} (the options are {list(OPTIONS)})")
+            return check_options(**arg)
+        raise TypeError(f"motion_gate must be None, True, a dict of MotionGate options or a MotionGate, not {type(arg).__name__}")
+
+    def _camera_gate_for(self, spec, n: int, restart: bool):
+        """-> (gate, per-camera cache of the last detector result) of a gated call, None for an ungated one.  The gate is kept between
+        ``persist=True`` calls that bring the same argument; new trackers, another argument or an ungated call in between start it afresh."""
+        from .motion import MotionGate
+        held = self.__dict__.get("_camera_gate")
+        if spec is None:
+            if held is not None:
+                self._camera_gate = None                         # a later gated call must not step trackers on rows older than this call's
+            return None
+        if held is not None and not restart and (held[0] is spec if isinstance(spec, MotionGate) else (held[1] == spec and held[0].n == n)):
+            return held[0], held[2]
+        g = spec if isinstance(spec, MotionGate) else MotionGate(n, device=self.device, **spec)
+        g.reset()
+        self._camera_gate = (g, None if isinstance(spec, MotionGate) else spec, [None] * n)
+        return g, self._camera_gate[2]
+
+    @staticmethod
+    def _result_snapshot(r: Results) -> dict:
+        """private copies of a pre-tracker result: what a static camera's tracker steps on until the detector sees that camera again"""
+        return {"boxes": r.boxes.data.clone(), "keypoints": None if r.keypoints is None else r.keypoints.data.clone(),
+                "keypoints_raw": None if getattr(r, "keypoints_raw", None) is None else r.keypoints_raw.copy(),
+                "anchor_idx": None if r.anchor_idx is None else r.anchor_idx.copy(), "feats": None if r.feats is None else r.feats.copy(),
+                "orig_shape": r.orig_shape, "path": r.path, "names": r.names}
+
+    @staticmethod
+    def _result_from_snapshot(c: dict, frame) -> Results:
+        kp = c["keypoints"]
+        r = Results(frame, c["path"], c["names"], boxes=c["boxes"].clone(), keypoints=kp.clone() if kp is not None else None,
+                    orig_shape=c["orig_shape"], speed={"preprocess": 0.0, "inference": 0.0, "postprocess": 0.0},
+                    anchor_idx=None if c["anchor_idx"] is None else c["anchor_idx"].copy(), feats=None if c["feats"] is None else c["feats"].copy())
+        if c["keypoints_raw"] is not None:
+            r.keypoints_raw = c["keypoints_raw"].copy()
+        return r
 
     # ------------------------------------------------------------------------------------------ test hooks
     def raw_head(self, source, imgsz: int = 640, half: Optional[bool] = None) -> np.ndarray:

@@ -503,6 +503,27 @@ def yuv_to_bgr(frames, device: int = 0, out: Optional[Sequence[np.ndarray]] = No
     return out
 
 
+def motion_grid(frames, block: int = 16, device: int = 0):
+    """The block-luma sums of a motion gate alone (csrc/motion_kernels.hip): ``frames`` -- BGR arrays [H, W, 3] of any row pitch or
+    ``cvsd_amd.YUVFrame``s (their Y plane), up to 64, any sizes -> a list of uint32 [ceil(H / block), ceil(W / block)] grids.  One launch
+    for all frames; ``device=-1`` runs the same routine on the host and touches no GPU.  Frames on a GPU are brought to the host first:
+    the hook takes host memory and uploads it with the caller's pitch and base alignment."""
+    import torch
+    from .motion import _descriptor
+    from .yuv import YUVFrame
+    if isinstance(frames, (np.ndarray, YUVFrame, torch.Tensor)):
+        frames = [frames]
+    keep, descs = [], []
+    for f in frames:
+        f = f.host() if isinstance(f, YUVFrame) else (f.cpu() if isinstance(f, torch.Tensor) else f)
+        descs.append(_descriptor(f, keep)[0])
+    b = int(block)
+    out = [np.zeros((-(-d.height // b), -(-d.width // b)) if b > 0 else (0, 0), np.uint32) for d in descs]
+    ptrs = (C.c_void_p * len(out))(*[o.ctypes.data or 1 for o in out])
+    _lib.check(_lib.lib().mi355_op_motion_grid(int(device), (_lib.MotionFrame * len(descs))(*descs), len(descs), b, ptrs))
+    return out
+
+
 def nms(pred: np.ndarray, nc: int, conf: float = 0.25, iou: float = 0.7, classes: Optional[Sequence[int]] = None,
         max_det: int = 300, device: int = 0):
     """non_max_suppression on pred [N, 4+nc+extra, A] -> list of (rows [n,6+extra], anchor_idx [n])."""

@@ -181,6 +181,8 @@ class Results:
         # own canvas).  None for an untiled call.
         self.tile_idx = tile_idx
         self.tiles = tiles
+        # track_cameras(motion_gate=...): {"moving", "changed", "skipped"} of this camera's tick; None for any other call
+        self.motion = None
 
     def __len__(self):
         return len(self.boxes) if self.boxes is not None else 0
@@ -198,6 +200,7 @@ class Results:
             ix = idx.numpy() if isinstance(idx, torch.Tensor) else idx
             r.tile_idx = self.tile_idx[[ix]] if isinstance(ix, (int, np.integer)) else self.tile_idx[ix]
         r.tiles = self.tiles
+        r.motion = self.motion
         return r
 
     def update(self, boxes=None):
@@ -216,4 +219,5 @@ class Results:
         r.keypoints = self.keypoints.numpy() if self.keypoints is not None else None
         r.feats = self.feats
         r.tile_idx, r.tiles = self.tile_idx, self.tiles
+        r.motion = self.motion
         return r

@@ -556,6 +556,54 @@ int  mi355_gmc_multi_finish(mi355_gmc_multi* g, double* H_out);
 int  mi355_gmc_multi_frames(mi355_gmc_multi* g, const uint8_t** dev_frames);
 int  mi355_gmc_multi_reset(mi355_gmc_multi* g, int camera);
 int  mi355_gmc_multi_state(const mi355_gmc_multi* g, int camera, int* oh, int* ow, int* n_pts, uint8_t* gray_out, float* pts_out, int pts_cap);
+
+/* ---- motion gate: which cameras of a tick changed since their last detector pass ------------------------------------
+ * Integer arithmetic only (csrc/motion_grid.h; the kernel of csrc/motion_kernels.hip and its host twin give the same numbers).
+ *   luma      of a BGR pixel (bytes_per_pixel 3): (1868 B + 9617 G + 4899 R + 8192) >> 14, the luma of the motion compensation;
+ *             of a Y-plane pixel (bytes_per_pixel 1): its byte.
+ *   grid      gh = ceil(height / block) by gw = ceil(width / block) blocks of block x block pixels (edge blocks are partial);
+ *             S[b] = uint32 sum of the luma of block b's pixels, P[b] = their number.
+ *   changed   block b is flagged when 16 |S_cur[b] - S_ref[b]| > level_q P[b], level_q = floor(16 level + 0.5); a camera without a
+ *             reference has every block flagged.  A camera's `changed` is its number of flagged blocks.
+ *   moving    a present camera moves when it has no reference (first frame, after a reset, height / width / bytes_per_pixel differ from
+ *             its previous frame's), when changed >= min_blocks, or when it has been static for max_skip consecutive present ticks.
+ *             A moving camera's current grid becomes its reference (two buffers per camera swap roles) and its static run restarts; a
+ *             static camera keeps its reference -- slow drift adds up until it trips -- and its run grows by one.
+ *   absent    a NULL frame descriptor: the camera's state is untouched; moving = 0, changed = -1.
+ * Options: block 8, 16 or 32; level in [0, 255]; min_blocks >= 0 (0: every present camera moves); max_skip < 0: never forced.  A NULL
+ * options pointer means block 16, level 2, min_blocks 4, max_skip 30.  At most MI355_MOTION_MAX_CAMERAS cameras.
+ *   create   device >= 0: a stream of its own on that GPU; -1: the host twin, which touches no GPU.
+ *   update   frames[i] = camera i's descriptor or NULL.  frames_on_device = 0: host memory, staged with the caller's row pitch and base
+ *            alignment (modulo 16) and uploaded once per call on the gate's stream, in front of the launch.  frames_on_device = 1: memory
+ *            of the gate's GPU, read in place -- the caller orders the call behind whatever wrote the frames (the pointers of
+ *            mi355_gmc_multi_frames come back behind an event wait for that upload).  ONE launch for all present cameras, one copy of the
+ *            per-strip counts into pinned memory, one stream wait.  Rows whose address is 16-byte aligned are read with 16-byte loads,
+ *            4-byte aligned ones with 4-byte loads, others by bytes.  moving[n_cameras], changed[n_cameras] are written for every camera.
+ *   mask     camera's flag grid of its last present tick: flags_out [gh][gw] (may be NULL to query gh, gw; both 0 before its first frame).
+ *   reset    forgets camera's reference and static run (-1: every camera's).
+ *   mi355_op_motion_grid   the sums alone (parity tests): n host frames -> sums_out[i] = uint32 [gh_i][gw_i].
+ * MI355_EINVAL before any launch: a block, level or min_blocks outside the above, n_cameras outside [1, 64], a non-positive height or
+ * width, bytes_per_pixel other than 1 or 3, a row_stride smaller than a row, a frame of 2 GiB or more, device frames for a host gate. */
+#define MI355_MOTION_MAX_CAMERAS 64
+typedef struct mi355_motion_opts {
+    int struct_size;                    /* sizeof(mi355_motion_opts) */
+    int block;                          /* 8, 16 or 32 */
+    float level;                        /* mean luma change of a block that counts, in [0, 255] */
+    int min_blocks;                     /* changed blocks that make a camera move */
+    int max_skip;                       /* static present ticks after which the detector is forced; < 0: never */
+} mi355_motion_opts;
+typedef struct mi355_motion_frame {
+    const uint8_t* data;                /* first pixel */
+    int height, width, row_stride;      /* row_stride in bytes, >= width * bytes_per_pixel */
+    int bytes_per_pixel;                /* 3: BGR, 1: the Y plane of an NV12 / I420 frame */
+} mi355_motion_frame;
+typedef struct mi355_motion_gate mi355_motion_gate;
+int  mi355_motion_gate_create(int device, int n_cameras, const mi355_motion_opts* opts, mi355_motion_gate** out);
+void mi355_motion_gate_destroy(mi355_motion_gate* g);
+int  mi355_motion_gate_update(mi355_motion_gate* g, const mi355_motion_frame* const* frames, int frames_on_device, int* moving, int* changed);
+int  mi355_motion_gate_mask(mi355_motion_gate* g, int camera, uint8_t* flags_out, int cap, int* gh, int* gw);
+int  mi355_motion_gate_reset(mi355_motion_gate* g, int camera);
+int  mi355_op_motion_grid(int device, const mi355_motion_frame* frames, int n, int block, uint32_t* const* sums_out);
 /* Depthwise 3x3 conv (stride 1, pad 1) + bias (+SiLU) (+residual) on channel views, fp32, as the engine runs YOLO11's
  * DWConv and Attention.pe (ultralytics nn/modules/conv.py:DWConv, Conv with groups = c).  x[n][h][w][x_cs] holds the input view at
  * channels x_off .. x_off+c-1; residual (or NULL) [n][h][w][res_cs] at res_off; y[n][h][w][y_cs] is read in, its view y_off ..
