@@ -71,6 +71,17 @@ class MotionFrame(C.Structure):
     _fields_ = [("data", C.c_void_p), ("height", C.c_int), ("width", C.c_int), ("row_stride", C.c_int), ("bytes_per_pixel", C.c_int)]
 
 
+class RenderFrame(C.Structure):
+    """mi355_render_frame: one BGR source frame of a render call (host memory, or memory of the call's GPU)"""
+    _fields_ = [("data", C.c_void_p), ("height", C.c_int), ("width", C.c_int), ("row_stride", C.c_int), ("on_device", C.c_int)]
+
+
+class RenderOut(C.Structure):
+    """mi355_render_out: where the rendered copy of a frame goes"""
+    _fields_ = [("data", C.c_void_p), ("row_stride", C.c_int), ("on_device", C.c_int)]
+
+
+RENDER_WORDS, RENDER_MAX_PRIMS, RENDER_MAX_FRAMES = 8, 16384, 256      # MI355_RENDER_*
 MOTION_MAX_CAMERAS = 64                 # MI355_MOTION_MAX_CAMERAS
 TILE_IOS, TILE_IOU = 0, 1               # MI355_TILE_IOS / MI355_TILE_IOU
 TILE_MAX_ENTRIES, TILE_MAX_CANDIDATES = 64, 65536
@@ -229,6 +240,9 @@ SIGNATURES = {
     "mi355_motion_gate_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _i32p, _i32p]),
     "mi355_motion_gate_reset": (C.c_int, [C.c_void_p, C.c_int]),
     "mi355_op_motion_grid": (C.c_int, [C.c_int, _P(MotionFrame), C.c_int, C.c_int, _P(C.c_void_p)]),
+    "mi355_render": (C.c_int, [C.c_int, _P(RenderFrame), C.c_int, _P(C.c_void_p), _i32p, _P(RenderOut), C.c_void_p, _f32p]),
+    "mi355_yolo_render": (C.c_int, [C.c_void_p, _P(RenderFrame), C.c_int, _P(C.c_void_p), _i32p, _P(RenderOut), _f32p]),
+    "mi355_yolo_last_frames": (C.c_int, [C.c_void_p, _P(RenderFrame), C.c_int, _i32p]),
     "mi355_op_nms": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,
                                C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
     "mi355_op_nms_ex": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,

@@ -51,6 +51,15 @@ inline int grow_or_fail(Buf& b, size_t need, const char* name) {
 }
 #define GROW(buf, need) do { if (grow_or_fail(buf, need, #buf) < 0) return MI355_EHIP; } while (0)
 
+// render_kernels.hip: the grow-only scratch of render calls -- one device buffer [descriptors | primitives | bins |
+// staged host frames], the pinned image of its first two parts and the pinned landing area of host outputs -- and one call: checks, staging, the two launches, the copy back.
+// device = -1 runs the host twin.  The call returns behind `st`; launch_ms (or NULL) receives the time from the bins' memset to the end
+// of the draw launch.
+struct RenderCtx { Buf d_work; Buf h_img{true}, h_out{true}; hipEvent_t ev0 = nullptr, ev1 = nullptr; };
+int render_run(RenderCtx& ctx, int device, const mi355_render_frame* frames, int n, const int32_t* const* prims, const int* n_prims,
+               const mi355_render_out* outs, hipStream_t st, float* launch_ms);
+void render_ctx_free(RenderCtx& ctx);
+
 // OP_DWCONV / OP_ATTN (YOLO11, file version 2): FileOp.r0 = groups (== channels) / heads; for OP_ATTN k = key_dim, s = head_dim
 enum { OP_STEM = 0, OP_CONV = 1, OP_UPSAMPLE = 2, OP_SPPF_POOL = 3, OP_DWCONV = 4, OP_ATTN = 5 };
 
@@ -273,6 +282,13 @@ struct mi355_yolo {
     // what mi355_yolo_last_feats hands out: the last blocking call's n and max_det, and whether h_feats holds its rows packed in frame
     // order (counts in h_counts) or at slot i * max_det (the direct-rows path); last_feat_n = 0: the last call produced none
     int last_feat_n = 0, last_feat_max_det = 0; bool last_feat_packed = false;
+    // Evidence frames (render_kernels.hip): where the BGR frames of the last blocking infer call lie on the device, so that
+    // mi355_yolo_render draws them without a second upload -- the d_in slot a host or YUV frame was staged / converted into, the one
+    // copy of a tiled call (d_tile_frames), or the caller's own device memory.  p = nullptr: the slot has since been reused (host
+    // frames of a call of more than two chunks, except its last two).  Cleared by every infer call before it touches a buffer.
+    struct LastFrame { const uint8_t* p; int h, w, pitch; };
+    std::vector<LastFrame> last_frames;
+    RenderCtx render;
     unsigned long long plan_hash = 0;   // fingerprint of the candidate lists + the chosen indices of the current shape
     int plan_source = 0, plan_launches = 0;   // 0 static guess (autotune off), 1 memory, 2 this machine's plan cache, 3 tuned now, 4 shipped plan file; launches of one pass (stem..last conv)
     bool async_pending = false;         // mi355_yolo_infer_device_async work may still be in flight on `stream`

@@ -644,8 +644,29 @@ static void copy_out(const mi355_yolo* h, const InferCall& c, bool packed) {
     }
 }
 
+// where the call's BGR frames lie on the device now that its chunks are enqueued (mi355_yolo_render reads them until the next call): the
+// caller's own memory, or the d_in slot of the frame's chunk -- which only the call's last two chunks still own
+static void record_frames(mi355_yolo* h, const CallState& s) {
+    const InferCall& c = s.c;
+    const int nchunks = (c.n + s.nb - 1) / s.nb;
+    h->last_frames.resize((size_t)c.n);
+    for (int i = 0; i < c.n; ++i) {
+        mi355_yolo::LastFrame& f = h->last_frames[i];
+        f.h = c.multi ? c.multi->heights[i] : c.height; f.w = c.multi ? c.multi->widths[i] : c.width; f.pitch = f.w * 3;
+        if (c.on_device && !c.yuv) {
+            if (c.multi) { f.p = c.multi->frames[i]; if (c.multi->row_strides && c.multi->row_strides[i]) f.pitch = c.multi->row_strides[i]; }
+            else f.p = c.src + (size_t)i * s.frame_bytes;
+            continue;
+        }
+        const int ci = i / s.nb;
+        const size_t off = c.multi ? s.mc.stage_off[i] : (size_t)(i % s.nb) * s.frame_bytes;
+        f.p = ci >= nchunks - 2 ? h->d_in.p + (size_t)(ci & 1) * s.slot_bytes + off : nullptr;
+    }
+}
+
 int infer_impl(mi355_yolo* h, const InferCall& call) {
     CallState s; s.c = call;
+    h->last_frames.clear();
     int rc = check_call(h, s); if (rc) return rc;
     const InferCall& c = s.c;
     HIPCHK(hipSetDevice(h->device));
@@ -680,6 +701,7 @@ int infer_impl(mi355_yolo* h, const InferCall& call) {
     Prof pf{h};
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     rc = run_chunks(h, s, pf); if (rc) return rc;
+    if (!c.tile && !s.async_out) record_frames(h, s);         // (a tiled call's frames are the entries' sources: engine_tiled.hip records them)
     if (c.tile) { rc = tile_merge_enqueue(h, c, pf, direct_rows_on); if (rc) return rc; }      // one launch behind the last chunk's NMS
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     if (c.tile) {                       // only the merged rows travel (engine_tiled.hip)
@@ -751,6 +773,7 @@ static int raw_head_upload_multi(mi355_yolo* h, const RawHeadCall& c, int nb, Mu
 // What the two entry points share: imgsz, the anchor count and the shape query, the transposed head's buffer, and the chunk loop (net
 // with the full decode, transpose, copy out, synchronise).  Profiling is off inside and back on every way out.
 int raw_head_impl(mi355_yolo* h, const RawHeadCall& c) {
+    h->last_frames.clear();             // d_in is about to hold this call's frames
     int imgsz = c.imgsz;
     if (imgsz <= 0) imgsz = 640;
     if (imgsz % 32) return fail(MI355_EINVAL, "imgsz must be a multiple of 32");

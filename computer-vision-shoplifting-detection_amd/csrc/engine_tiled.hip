@@ -202,7 +202,10 @@ static int tiled_run(mi355_yolo* h, const uint8_t* const* dev, const int* height
     c.multi = &mf; c.n = (int)eptr.size(); c.tile = &t;
     c.conf = conf; c.iou = iou; c.classes = classes; c.n_classes = n_classes; c.max_det = md; c.imgsz = imgsz;
     c.out_rows = out.rows; c.cap = out.cap; c.out_counts = out.counts;
-    return infer_impl(h, c);
+    const int rc = infer_impl(h, c); if (rc) return rc;
+    h->last_frames.resize((size_t)n);                         // the one device copy of every source frame (d_tile_frames, or the caller's)
+    for (int i = 0; i < n; ++i) h->last_frames[i] = mi355_yolo::LastFrame{dev[i], heights[i], widths[i], strides[i]};
+    return MI355_OK;
 }
 
 // what both entry points check and do first

@@ -375,7 +375,7 @@ class YOLO:
     def predict(self, source=None, conf: Optional[float] = None, iou: float = 0.7, classes=None, max_det: int = 300,
                 imgsz: int = 640, half: Optional[bool] = None, verbose: bool = False, stream: bool = False,
                 feats: Optional[bool] = None, tile=None, overlap: float = 0.2, full_frame: bool = True, tile_iou: float = 0.5,
-                tile_metric: str = "ios", **kwargs) -> List[Results]:
+                tile_metric: str = "ios", render=None, **kwargs) -> List[Results]:
         """``model.predict`` / ``model(...)``: ultralytics/engine/model.py:Model.predict.
         ``half=True`` runs the fp16-storage engine (fp32 accumulate; results differ from fp32 by fp16 rounding);
         ``None`` = the precision the model was constructed with (fp32 unless ``YOLO(..., half=True)``).
@@ -385,15 +385,63 @@ class YOLO:
         ``overlap`` (a fraction of the tile), the tiles (and with ``full_frame`` the frame itself) run through ONE detector pass at
         ``imgsz`` each, and their rows are merged per frame on the GPU: a row dies when an earlier row of its class overlaps it by more
         than ``tile_iou`` under ``tile_metric`` ("ios": intersection over the smaller box, "iou").  ``Results.tile_idx`` / ``.tiles``
-        say which entry every row came from.  ``None`` (default): the call as it always was."""
+        say which entry every row came from.  ``None`` (default): the call as it always was.
+        ``render``: True or a :class:`cvsd_amd.render.RenderSpec` (or a dict of its fields) -- every ``Results`` also
+        carries ``rendered``, uint8 [H, W, 3]: a COPY of its frame with its boxes, labels and skeletons drawn in (and people pixelated,
+        ``anonymize=``), rendered on the GPU from the copy of the frame this call already put there.  The source frames, the rows and
+        the keypoints are what they are without it.  ``None`` (default): the call as it always was."""
+        from .render import as_spec
         if isinstance(imgsz, (list, tuple)):
             imgsz = int(max(imgsz))
         conf = 0.25 if conf is None else float(conf)
-        if tile is not None:
-            batch, originals = self._as_tile_batch(source)
-            return self._predict_tiled(batch, originals, conf, iou, classes, max_det, imgsz, half, feats, tile, overlap, full_frame, tile_iou, tile_metric)
-        batch, originals = self._as_batch(source)
-        return self._predict_batch(batch, originals, conf, iou, classes, max_det, imgsz, half, feats)
+        spec = as_spec(render)
+        if spec is None:
+            if tile is not None:
+                batch, originals = self._as_tile_batch(source)
+                return self._predict_tiled(batch, originals, conf, iou, classes, max_det, imgsz, half, feats, tile, overlap, full_frame, tile_iou, tile_metric)
+            batch, originals = self._as_batch(source)
+            return self._predict_batch(batch, originals, conf, iou, classes, max_det, imgsz, half, feats)
+        with self._lock:                       # the picture is drawn from the frames this call leaves on the GPU: no other call in between
+            if tile is not None:
+                batch, originals = self._as_tile_batch(source)
+                res = self._predict_tiled(batch, originals, conf, iou, classes, max_det, imgsz, half, feats, tile, overlap, full_frame, tile_iou, tile_metric)
+            else:
+                batch, originals = self._as_batch(source)
+                res = self._predict_batch(batch, originals, conf, iou, classes, max_det, imgsz, half, feats)
+            return self._render_into(res, spec, None, lambda: self._batch_frames(batch))
+
+    @staticmethod
+    def _batch_frames(batch) -> list:
+        """the frames of a call as ``ops.render`` takes them (the fallback of ``_render_into``: a copy that has left the GPU)"""
+        if isinstance(batch, (YOLO._Ragged, YOLO._YuvBatch)):
+            if batch.frames is None:
+                from .ops import DeviceFrame
+                return [DeviceFrame(p, h, w) for p, (h, w) in zip(batch.ptrs, batch.shapes)]
+            return list(batch.frames)
+        return list(batch)
+
+    def _render_into(self, results, spec, sources, fallback=None):
+        """Fills ``Results.rendered`` of every non-None result with ONE render call on the engine that ran the detector.  ``sources``
+        None: the frames of that engine's last call, from where the call left them on the GPU (``fallback()`` -> the frames to pass again
+        when a copy has been overwritten: host calls of more than two chunks); else one frame per result as ``ops.render`` takes them."""
+        from . import ops
+        from .render import primitives
+        idx = [i for i, r in enumerate(results) if r is not None]
+        if not idx:
+            return results
+        prims = [primitives(results[i], spec) for i in idx]
+        hnd = getattr(self, "_last_handle", None) or self._h
+        with self._lock:
+            if sources is None:
+                try:
+                    pics = ops.render(None, prims, device=self.device, handle=hnd)
+                except LookupError:
+                    pics = ops.render(fallback(), prims, device=self.device, handle=hnd)
+            else:
+                pics = ops.render([sources[i] for i in idx], prims, device=self.device, handle=hnd)
+        for i, pic in zip(idx, pics):
+            results[i].rendered = pic
+        return results
 
     def detect_rows(self, batch, conf: float = 0.25, iou: float = 0.7, classes=None, max_det: int = 300, imgsz: int = 640, half=None):
         """``Results.boxes.data`` of every frame of ``batch`` -- float32 [M, 6] rows x1, y1, x2, y2, conf, cls -- and the frames' (h, w),
@@ -439,6 +487,7 @@ class YOLO:
                           tiles=tiles[i] if tiles is not None else None)
             if kp is not None:
                 res.keypoints_raw = kp.numpy()          # before Keypoints() zeroes x,y of joints with conf < 0.5
+            res._render_device = self.device            # Results.plot() renders where the engine lives
             out.append(res)
         return out
 
@@ -540,9 +589,14 @@ class YOLO:
         (it is not parsed again) or omit it; settings that differ from the continued tracker's are a ``ValueError``, not ignored.
         With ``with_reid: True`` the detector pass also produces its per-box embeddings and the tracker matches on them.
         ``tile=...`` (with ``overlap``, ``full_frame``, ``tile_iou``, ``tile_metric``) is passed on to :meth:`predict`: the tracker consumes
-        the merged rows of the tiled call (not together with ``with_reid``: a tiled call has no features)."""
+        the merged rows of the tiled call (not together with ``with_reid``: a tiled call has no features).
+        ``render=`` as in :meth:`predict`: drawn after the tracker step, so ``Results.rendered`` shows the tracker's boxes and ids; the
+        picture is rendered from the copy of the frame the motion compensation uploaded."""
+        from .ops import DeviceFrame
+        from .render import as_spec
         from .tracker import BYTETracker
         kwargs.pop("batch", None)
+        spec = as_spec(kwargs.pop("render", None))
         conf = 0.1 if conf is None else conf
         cfg = self._tracker_settings("track", tracker, continuing=self._tracker is not None and persist)
         if cfg is not None:
@@ -583,6 +637,7 @@ class YOLO:
                                           kwargs.get("max_det", 300), int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"),
                                           kwargs.get("feats"))[0]
             else:
+                dev = None
                 res = self.predict(batch[i:i + 1], conf=conf, **kwargs)[0]
             if originals is not None:
                 res.orig_img = originals[i]
@@ -590,7 +645,11 @@ class YOLO:
             # frame_id, ages lost tracks against track_buffer and runs the Kalman predict); only the rewrite of the
             # result is skipped when no track comes back
             tracks = self._tracker.update(res.boxes.data.numpy(), frame, feats=res.feats if reid else None)   # trackers/track.py: tracker.update(det, im0, feats)
-            results.append(self._with_tracks(res, tracks))
+            res = self._with_tracks(res, tracks)
+            if spec is not None:
+                # the motion compensation's copy stays where it is until its next step; without one, the detector call's own copy
+                self._render_into([res], spec, None if dev is None else [DeviceFrame(dev[0], dev[1], dev[2])], lambda: [frame])
+            results.append(res)
         return results
 
     def _tracker_settings(self, which: str, tracker, continuing: bool) -> Optional[dict]:
@@ -640,11 +699,17 @@ class YOLO:
         same rows again.  The gate reads the frames the motion compensation uploaded.  Every returned ``Results`` then carries
         ``motion = {"moving", "changed", "skipped"}`` and, for a static camera, this tick's frame as ``orig_img``.  The letterbox geometry
         follows the list handed to the detector, as with absent cameras: moving frames of one shape take the rect path, of mixed shapes
-        the square canvas.  ``persist=False`` resets the gate along with the trackers."""
+        the square canvas.  ``persist=False`` resets the gate along with the trackers.
+
+        ``render``: as in :meth:`predict` -- every present camera's ``Results.rendered`` is its frame with the tracker's
+        boxes and ids drawn in, all cameras in ONE render call reading the frames the motion compensation uploaded; an absent camera has
+        no picture, and a camera the motion gate skipped is drawn with the rows its tracker stepped on."""
         from .gmc import MultiGMC
+        from .render import as_spec
         from .tracker import BYTETracker
         tracker = kwargs.pop("tracker", None)
         motion_gate = kwargs.pop("motion_gate", None)
+        rspec = as_spec(kwargs.pop("render", None))
         unknown = set(kwargs) - {"iou", "classes", "max_det", "imgsz", "half", "feats", "show", "verbose"}
         if unknown:                                              # show / verbose are accepted and ignored, as in track()
             raise TypeError(f"track_cameras: unsupported argument(s) {sorted(unknown)} (iou, classes, max_det, imgsz, half pass through)")
@@ -718,7 +783,7 @@ class YOLO:
         if gate is None:
             for r, i in zip(res, present):
                 out[i] = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i], feats=r.feats if reid else None))    # an empty frame still steps
-            return out
+            return out if rspec is None else self._render_cameras(out, rspec, frames, dev)
         fresh = dict(zip(run, res))
         for i in present:
             r = fresh.get(i)
@@ -726,10 +791,18 @@ class YOLO:
                 cache[i] = self._result_snapshot(r)
             else:
                 r = self._result_from_snapshot(cache[i], frames[i])    # the rows the detector last produced for this camera, on this tick's frame
+                r._render_device = self.device
             r = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i], feats=r.feats if reid else None))
             r.motion = {"moving": bool(moving[i]), "changed": int(changed[i]), "skipped": i not in fresh}
             out[i] = r
-        return out
+        return out if rspec is None else self._render_cameras(out, rspec, frames, dev)
+
+    def _render_cameras(self, out, spec, frames, dev):
+        """``track_cameras(render=...)``: the present cameras' pictures from the tick's uploaded frames (valid until the next tick's
+        motion-compensation step), or from the host frames when that step shared none"""
+        from .ops import DeviceFrame
+        src = [None if f is None else (f if dev is None else DeviceFrame(dev[i], f.shape[0], f.shape[1])) for i, f in enumerate(frames)]
+        return self._render_into(out, spec, src)
 
     # ---- motion gate of track_cameras (DESIGN.md 3.18) --------------------------------------------------------------------------
     @staticmethod

@@ -524,6 +524,108 @@ def motion_grid(frames, block: int = 16, device: int = 0):
     return out
 
 
+class DeviceFrame:
+    """A dense-or-pitched BGR uint8 frame on a GPU known by raw pointer (``ops.render``): the copy a motion-compensation step uploaded"""
+    def __init__(self, ptr: int, h: int, w: int, pitch: Optional[int] = None):
+        self.ptr, self.shape, self.pitch = int(ptr), (int(h), int(w), 3), int(pitch) if pitch else 3 * int(w)
+
+
+def render(frames, prims, device: int = 0, out: str = "numpy", timing: Optional[list] = None, handle=None):
+    """Draw primitive lists into COPIES of frames (csrc/render_kernels.hip): ``frames`` -- a BGR array [H, W, 3] (any row
+    pitch), a uint8 CUDA tensor [H, W, 3] on ``device`` (any row pitch, read in place and left unchanged), a ``cvsd_amd.YUVFrame``
+    (rendered from the BGR the ingest conversion makes of it), or a list of them of any sizes; ``prims`` -- int32 [P, 8] records
+    (``cvsd_amd.render.primitives`` builds them), one array per frame.  One call, two launches, whatever the number of frames.
+    ``out="numpy"``: uint8 arrays; ``"cuda"``: tensors on ``device``, nothing comes back to the host.  A single frame gives a single
+    picture, a list a list.  ``device=-1`` runs the host twin and touches no GPU.  ``timing``: a list that receives the launches' ms.
+    ``handle``: an engine handle -- the call runs on its stream with its scratch (``mi355_yolo_render``), and ``frames=None`` then means
+    the frames of that handle's last call, read from where the call left them on the GPU."""
+    import torch
+    from .yuv import YUVFrame
+    if out not in ("numpy", "cuda"):
+        raise ValueError(f"out must be 'numpy' or 'cuda', got {out!r}")
+    device = int(device)
+    if out == "cuda" and device < 0:
+        raise ValueError("out='cuda' needs a GPU: the host twin (device=-1) returns numpy arrays")
+    lib = _lib.lib()
+    single = isinstance(frames, (np.ndarray, YUVFrame, torch.Tensor, DeviceFrame))
+    if single:
+        frames, prims = [frames], [prims]
+    prims = list(prims)
+    keep, fd = [], []
+    if frames is None:
+        if handle is None:
+            raise ValueError("frames=None needs an engine handle")
+        cnt = C.c_int()
+        _lib.check(lib.mi355_yolo_last_frames(handle, None, 0, C.byref(cnt)))
+        last = (_lib.RenderFrame * max(cnt.value, 1))()
+        _lib.check(lib.mi355_yolo_last_frames(handle, last, cnt.value, C.byref(cnt)))
+        fd = [last[i] for i in range(cnt.value)]
+        if not fd or any(not f.data for f in fd):
+            raise LookupError("a frame of the handle's last call is no longer on the GPU")
+        frames = None
+    else:
+        frames = list(frames)
+        if not frames:
+            raise ValueError("empty list of frames")
+        for f in frames:
+            if isinstance(f, YUVFrame):
+                f = yuv_to_bgr([f], device=-1)[0] if device < 0 else f.to_bgr(device)
+            if isinstance(f, DeviceFrame):
+                if device < 0:
+                    raise ValueError("a frame on a GPU cannot be rendered by the host twin")
+                fd.append(_lib.RenderFrame(f.ptr, f.shape[0], f.shape[1], f.pitch, 1))
+                continue
+            on_dev = isinstance(f, torch.Tensor) and f.is_cuda
+            if isinstance(f, torch.Tensor) and not on_dev:
+                f = f.numpy()
+            if f.dtype != (torch.uint8 if on_dev else np.uint8) or f.ndim != 3 or f.shape[-1] != 3:
+                raise ValueError("frames must be uint8 [H, W, 3] BGR arrays or CUDA tensors")
+            if on_dev:
+                if device < 0 or f.device.index != device:
+                    raise ValueError("a CUDA frame must live on the GPU the call runs on")
+                if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.shape[1]:
+                    f = f.contiguous()
+                torch.cuda.current_stream(f.device).synchronize()
+                ptr, pitch = f.data_ptr(), f.stride(0)
+            else:
+                f = np.asarray(f)
+                if f.size and (f.strides[2] != 1 or f.strides[1] != 3 or f.strides[0] < 3 * f.shape[1]):
+                    f = np.ascontiguousarray(f)
+                ptr, pitch = f.ctypes.data, f.strides[0]
+            h, w = int(f.shape[0]), int(f.shape[1])
+            keep.append(f)
+            fd.append(_lib.RenderFrame(ptr or 1, h, w, int(max(pitch, 3 * w)), int(on_dev)))
+    if len(fd) != len(prims):
+        raise ValueError("prims: one int32 [P, 8] array per frame")
+    od, outs, pp = [], [], []
+    for f in fd:
+        h, w = max(f.height, 0), max(f.width, 0)
+        if out == "cuda":
+            o = torch.empty((h, w, 3), dtype=torch.uint8, device=torch.device("cuda", device))
+            od.append(_lib.RenderOut(o.data_ptr() or 1, 3 * w, 1))
+        else:
+            o = np.empty((h, w, 3), np.uint8)
+            od.append(_lib.RenderOut(o.ctypes.data or 1, 3 * w, 0))
+        outs.append(o)
+    for p in prims:
+        p = np.ascontiguousarray(np.zeros((0, _lib.RENDER_WORDS), np.int32) if p is None else p)
+        if p.dtype != np.int32 or p.ndim != 2 or p.shape[1] != _lib.RENDER_WORDS:
+            raise ValueError(f"prims must be int32 arrays of shape [P, {_lib.RENDER_WORDS}]")
+        pp.append(p)
+    n = len(fd)
+    ptrs = (C.c_void_p * n)(*[p.ctypes.data if len(p) else None for p in pp])
+    counts = (C.c_int * n)(*[len(p) for p in pp])
+    ms = C.c_float(0.0)
+    msp = C.byref(ms) if timing is not None else None
+    if handle is not None:
+        _lib.check(lib.mi355_yolo_render(handle, None if frames is None else (_lib.RenderFrame * n)(*fd), n, ptrs, counts, (_lib.RenderOut * n)(*od), msp))
+    else:
+        _lib.check(lib.mi355_render(device, (_lib.RenderFrame * n)(*fd), n, ptrs, counts, (_lib.RenderOut * n)(*od), None, msp))
+    if timing is not None:
+        timing.append(float(ms.value))
+    return outs[0] if single else outs
+
+
 def nms(pred: np.ndarray, nc: int, conf: float = 0.25, iou: float = 0.7, classes: Optional[Sequence[int]] = None,
         max_det: int = 300, device: int = 0):
     """non_max_suppression on pred [N, 4+nc+extra, A] -> list of (rows [n,6+extra], anchor_idx [n])."""

@@ -183,6 +183,21 @@ class Results:
         self.tiles = tiles
         # track_cameras(motion_gate=...): {"moving", "changed", "skipped"} of this camera's tick; None for any other call
         self.motion = None
+        # predict / track / track_cameras(render=...): uint8 [H, W, 3], the frame with this result drawn in, rendered on the GPU from the
+        # call's device copy; None for any other call
+        self.rendered = None
+        self._render_device = 0
+
+    def plot(self, **spec) -> np.ndarray:
+        """``results[0].plot()``: this result drawn into a COPY of its frame -> uint8 [H, W, 3] BGR, rendered on the GPU
+        (``ops.render``).  Keywords are the fields of :class:`cvsd_amd.render.RenderSpec` (``boxes``, ``labels``, ``skeleton``,
+        ``anonymize``, ``mosaic``, ``line_width``, ``kpt_radius``, ``kpt_conf``, ``color_by``).  ``orig_img`` is left unchanged."""
+        from . import ops
+        from .render import RenderSpec, primitives
+        if self.orig_img is None:
+            raise ValueError("this Results holds no image (its frames were on the GPU, or YUV planes): ask for the picture at call time, "
+                             "predict / track / track_cameras(..., render=True), and read Results.rendered")
+        return ops.render(np.asarray(self.orig_img), primitives(self, RenderSpec(**spec)), device=self._render_device)
 
     def __len__(self):
         return len(self.boxes) if self.boxes is not None else 0
@@ -201,6 +216,7 @@ class Results:
             r.tile_idx = self.tile_idx[[ix]] if isinstance(ix, (int, np.integer)) else self.tile_idx[ix]
         r.tiles = self.tiles
         r.motion = self.motion
+        r.rendered, r._render_device = self.rendered, self._render_device
         return r
 
     def update(self, boxes=None):
@@ -220,4 +236,5 @@ class Results:
         r.feats = self.feats
         r.tile_idx, r.tiles = self.tile_idx, self.tiles
         r.motion = self.motion
+        r.rendered, r._render_device = self.rendered, self._render_device
         return r

@@ -604,6 +604,65 @@ int  mi355_motion_gate_update(mi355_motion_gate* g, const mi355_motion_frame* co
 int  mi355_motion_gate_mask(mi355_motion_gate* g, int camera, uint8_t* flags_out, int cap, int* gh, int* gw);
 int  mi355_motion_gate_reset(mi355_motion_gate* g, int camera);
 int  mi355_op_motion_grid(int device, const mi355_motion_frame* frames, int n, int block, uint32_t* const* sums_out);
+
+/* ---- evidence frames: boxes, labels, skeletons and mosaics drawn into a COPY of a frame --------------------------------
+ * A small rasteriser in integer arithmetic (csrc/render_raster.h; the kernels of csrc/render_kernels.hip and their host twin give the
+ * same bytes).  Out of place: the source is only read.  BGR in, BGR out, solid colours, no blending.
+ * A primitive is MI355_RENDER_WORDS int32: {type, a, b, c, d, size, colour, 0}, colour = B | G << 8 | R << 16.  Pixel (px, py) is a
+ * point; a rectangle a, b, c, d = x0, y0, x1, y1 holds x0 <= px <= x1 and y0 <= py <= y1 (x1 < x0 or y1 < y0: empty).
+ *   MOSAIC  rectangle, size B in {4, 8, 16, 32}: a covered pixel takes, per channel, (2 S + N) / (2 N) (integer division) of the SOURCE
+ *           frame's B x B block holding it -- blocks aligned to the frame's origin, S the sum and N the number of the block's pixels
+ *           inside the frame (the whole block, not the rectangle's part of it).
+ *   RECT    rectangle, size t: the rectangle without the rectangle shrunk by t on every side.
+ *   FILL    rectangle.
+ *   LINE    A = (a, b), B = (c, d), size t: pixels within t / 2 of the segment.  With u = (p - A) . (B - A): u <= 0 -> 4 |p - A|^2 <= t^2;
+ *           u >= |B - A|^2 -> 4 |p - B|^2 <= t^2; else 4 cross(B - A, p - A)^2 <= t^2 |B - A|^2.  A = B is a disc of diameter t.
+ *   DISC    centre (a, b), size r: (px - a)^2 + (py - b)^2 <= r^2.
+ *   GLYPH   top-left (a, b), c = character (0-9 # . : % - space), size = scale: a 5 x 7 bitmap, each bit a scale x scale square.
+ * Order: the mosaics first, in ascending index, every one reading the source; then the others in ascending index, the last writer wins.
+ * Everything is clipped to the frame; primitives partly or wholly outside it are legal.
+ * Ranges: |coordinate| <= 2^20, height and width <= 16384, t in 1 .. 255, r in 0 .. 2^20, scale in 1 .. 64, at most
+ * MI355_RENDER_MAX_PRIMS primitives per frame (300 boxes x (mosaic + box + 11 of a label + 19 limbs + 17 joints) fit) and
+ * MI355_RENDER_MAX_FRAMES frames per call.  Anything else -- one primitive too many included -- is MI355_EINVAL with a message naming
+ * the limit, before a byte of any output is written: nothing is ever dropped silently.
+ *   mi355_render   device >= 0: that GPU; -1: the host twin (host memory only), which touches no GPU.  frames[i] / outs[i]: host memory
+ *            (staged with the caller's pitch and address modulo 16, one upload per frame) or memory of that GPU (on_device = 1, read /
+ *            written in place; the caller orders the call behind whatever wrote the frames).  prims[i] = n_prims[i] host records.  All
+ *            frames of a call, whatever their sizes and pitches, take one memset of the bins and two launches on `stream` (NULL: the
+ *            null stream); the call returns when they and the copies have finished.  Of an output only the height x width x 3 pixel bytes
+ *            are written.  launch_ms (or NULL) receives the device time from the memset to the end of the draw launch. */
+#define MI355_RENDER_WORDS      8
+#define MI355_RENDER_MAX_PRIMS  16384
+#define MI355_RENDER_MAX_FRAMES 256
+#define MI355_RENDER_MOSAIC 1
+#define MI355_RENDER_RECT   2
+#define MI355_RENDER_FILL   3
+#define MI355_RENDER_LINE   4
+#define MI355_RENDER_DISC   5
+#define MI355_RENDER_GLYPH  6
+typedef struct mi355_render_frame {
+    const uint8_t* data;                /* first pixel of a BGR frame */
+    int height, width, row_stride;      /* row_stride in bytes, >= 3 * width */
+    int on_device;                      /* 1: memory of the call's GPU */
+} mi355_render_frame;
+typedef struct mi355_render_out {
+    uint8_t* data;                      /* height x width BGR pixels of the frame it answers */
+    int row_stride;
+    int on_device;
+} mi355_render_out;
+int  mi355_render(int device, const mi355_render_frame* frames, int n, const int32_t* const* prims, const int* n_prims,
+                  const mi355_render_out* outs, void* stream, float* launch_ms);
+/* The same call on an engine handle: its stream, and scratch that is kept between calls.  frames = NULL renders THE FRAMES OF THE
+ * HANDLE'S LAST BLOCKING INFER CALL from where that call left them on the device, so a host or YUV frame is not uploaded (or converted)
+ * twice: the staging slot of mi355_yolo_infer / _multi / _yuv, the one copy of a tiled call, or the caller's own device memory (which
+ * the caller keeps alive and unchanged).  They stay there until the handle's next infer or raw_head call.  The staging area holds two
+ * chunks (mi355_opts.batch_chunk frames each), so of a host or YUV call of more than two chunks only the last two chunks' frames
+ * remain; mi355_yolo_last_frames says which (data = NULL: gone) and the call refuses a NULL `frames` when one is gone -- the
+ * caller then passes descriptors of the frames again.  The asynchronous device-output calls record nothing.  n must be the last call's
+ * number of frames (a tiled call: of its source frames). */
+int  mi355_yolo_render(mi355_yolo* h, const mi355_render_frame* frames, int n, const int32_t* const* prims, const int* n_prims,
+                       const mi355_render_out* outs, float* launch_ms);
+int  mi355_yolo_last_frames(mi355_yolo* h, mi355_render_frame* frames_out, int cap, int* n);
 /* Depthwise 3x3 conv (stride 1, pad 1) + bias (+SiLU) (+residual) on channel views, fp32, as the engine runs YOLO11's
  * DWConv and Attention.pe (ultralytics nn/modules/conv.py:DWConv, Conv with groups = c).  x[n][h][w][x_cs] holds the input view at
  * channels x_off .. x_off+c-1; residual (or NULL) [n][h][w][res_cs] at res_off; y[n][h][w][y_cs] is read in, its view y_off ..
