@@ -81,7 +81,13 @@ class RenderOut(C.Structure):
     _fields_ = [("data", C.c_void_p), ("row_stride", C.c_int), ("on_device", C.c_int)]
 
 
+class JpegOut(C.Structure):
+    """mi355_jpeg_out: host memory for one JPEG stream, and the length the call reports"""
+    _fields_ = [("data", C.c_void_p), ("capacity", C.c_int64), ("length", C.c_int64)]
+
+
 RENDER_WORDS, RENDER_MAX_PRIMS, RENDER_MAX_FRAMES = 8, 16384, 256      # MI355_RENDER_*
+JPEG_420, JPEG_444 = 420, 444           # MI355_JPEG_*
 MOTION_MAX_CAMERAS = 64                 # MI355_MOTION_MAX_CAMERAS
 TILE_IOS, TILE_IOU = 0, 1               # MI355_TILE_IOS / MI355_TILE_IOU
 TILE_MAX_ENTRIES, TILE_MAX_CANDIDATES = 64, 65536
@@ -243,6 +249,10 @@ SIGNATURES = {
     "mi355_render": (C.c_int, [C.c_int, _P(RenderFrame), C.c_int, _P(C.c_void_p), _i32p, _P(RenderOut), C.c_void_p, _f32p]),
     "mi355_yolo_render": (C.c_int, [C.c_void_p, _P(RenderFrame), C.c_int, _P(C.c_void_p), _i32p, _P(RenderOut), _f32p]),
     "mi355_yolo_last_frames": (C.c_int, [C.c_void_p, _P(RenderFrame), C.c_int, _i32p]),
+    "mi355_jpeg_bound": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mi355_jpeg_encode": (C.c_int, [C.c_int, _P(RenderFrame), C.c_int, C.c_int, C.c_int, _P(JpegOut), C.c_void_p, _f32p]),
+    "mi355_yolo_encode": (C.c_int, [C.c_void_p, _P(RenderFrame), C.c_int, C.c_int, C.c_int, _P(JpegOut), _f32p]),
+    "mi355_op_jpeg_coefficients": (C.c_int, [C.c_int, _P(RenderFrame), C.c_int, C.c_int, C.c_int, _P(C.c_void_p)]),
     "mi355_op_nms": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,
                                C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
     "mi355_op_nms_ex": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,

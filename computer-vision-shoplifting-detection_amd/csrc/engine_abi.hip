@@ -1,5 +1,6 @@
 // The C ABI of include/mi355_yolo.h: engine handle entry points (create / infer / raw_head / plan_info / memory_plan ...).
 #include "engine_internal.h"
+#include "jpeg_codec.h"
 
 namespace mi355 { thread_local std::string g_err; }
 using namespace mi355;
@@ -186,6 +187,43 @@ int mi355_letterbox_shape(int height, int width, int imgsz, int* out_h, int* out
     const Geometry g = make_geometry(height, width, imgsz);
     *out_h = g.Hl; *out_w = g.Wl;
     return MI355_OK;
+}
+
+// ------------------------------------------------------------------------------------- JPEG evidence frames (jpeg_kernels.hip)
+int64_t mi355_jpeg_bound(int height, int width, int subsampling) {
+    if (height < 1 || width < 1 || height > kJpegMaxSide || width > kJpegMaxSide || (subsampling != kJpeg420 && subsampling != kJpeg444)) return 0;
+    return jpeg_bound(height, width, subsampling);
+}
+
+int mi355_jpeg_encode(int device, const mi355_render_frame* frames, int n, int quality, int subsampling, mi355_jpeg_out* outs, void* stream,
+                      float* launch_ms) {
+    if (!outs) return fail(MI355_EINVAL, "jpeg: null output");
+    JpegCtx ctx;
+    const int rc = jpeg_run(ctx, device, frames, n, quality, subsampling, outs, nullptr, (hipStream_t)stream, launch_ms);
+    if (device >= 0) jpeg_ctx_free(ctx);
+    return rc;
+}
+
+int mi355_yolo_encode(mi355_yolo* h, const mi355_render_frame* frames, int n, int quality, int subsampling, mi355_jpeg_out* outs, float* launch_ms) {
+    if (!h) return fail(MI355_EINVAL, "jpeg: null handle");
+    if (!outs) return fail(MI355_EINVAL, "jpeg: null output");
+    std::vector<mi355_render_frame> last;
+    if (!frames) {                                             // the frames of the handle's last call, where that call left them on the device
+        if (h->last_frames.empty()) return fail(MI355_EINVAL, "jpeg: the handle has no frames of a last blocking infer call");
+        if (n != (int)h->last_frames.size())
+            return fail(MI355_EINVAL, "jpeg: n = " + std::to_string(n) + ", but the last call had " + std::to_string(h->last_frames.size()) + " frames");
+        last.resize((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            const mi355_yolo::LastFrame& f = h->last_frames[i];
+            if (!f.p) return fail(MI355_EINVAL, "jpeg: frame " + std::to_string(i) + " of the last call is no longer on the device (a host call of more than two "
+                                                "chunks keeps its last two): pass the frames again");
+            last[i] = mi355_render_frame{f.p, f.h, f.w, f.pitch, 1};
+        }
+        frames = last.data();
+    }
+    HIPCHK(hipSetDevice(h->device));
+    if (h->async_pending) { HIPCHK(hipStreamSynchronize(h->stream)); h->async_pending = false; }
+    return jpeg_run(h->jpeg, h->device, frames, n, quality, subsampling, outs, nullptr, h->stream, launch_ms);
 }
 
 }  // extern "C"

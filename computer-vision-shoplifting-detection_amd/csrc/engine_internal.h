@@ -60,6 +60,16 @@ int render_run(RenderCtx& ctx, int device, const mi355_render_frame* frames, int
                const mi355_render_out* outs, hipStream_t st, float* launch_ms);
 void render_ctx_free(RenderCtx& ctx);
 
+// jpeg_kernels.hip: the grow-only scratch of JPEG calls -- one device buffer [descriptors | tables | lengths | headers |
+// per frame: coefficients, segment words, segment sizes, stream | staged host frames], the pinned image of its first part and the pinned
+// landing areas of the lengths and the streams -- and one call: checks, staging, the three launches (the transform launch alone when
+// `coefs` is given instead of `outs`), the copy back of the streams' bytes.  device = -1 runs the host twin.  launch_ms (or NULL) receives
+// the device time of the launches.
+struct JpegCtx { Buf d_work; Buf h_img{true}, h_out{true}, h_len{true}; hipEvent_t ev0 = nullptr, ev1 = nullptr; };
+int jpeg_run(JpegCtx& ctx, int device, const mi355_render_frame* frames, int n, int quality, int subsampling, mi355_jpeg_out* outs,
+             int16_t* const* coefs, hipStream_t st, float* launch_ms);
+void jpeg_ctx_free(JpegCtx& ctx);
+
 // OP_DWCONV / OP_ATTN (YOLO11, file version 2): FileOp.r0 = groups (== channels) / heads; for OP_ATTN k = key_dim, s = head_dim
 enum { OP_STEM = 0, OP_CONV = 1, OP_UPSAMPLE = 2, OP_SPPF_POOL = 3, OP_DWCONV = 4, OP_ATTN = 5 };
 
@@ -289,6 +299,7 @@ struct mi355_yolo {
     struct LastFrame { const uint8_t* p; int h, w, pitch; };
     std::vector<LastFrame> last_frames;
     RenderCtx render;
+    JpegCtx jpeg;                       // mi355_yolo_encode's scratch
     unsigned long long plan_hash = 0;   // fingerprint of the candidate lists + the chosen indices of the current shape
     int plan_source = 0, plan_launches = 0;   // 0 static guess (autotune off), 1 memory, 2 this machine's plan cache, 3 tuned now, 4 shipped plan file; launches of one pass (stem..last conv)
     bool async_pending = false;         // mi355_yolo_infer_device_async work may still be in flight on `stream`

@@ -31,6 +31,7 @@ mi355_yolo::~mi355_yolo() {
     for (Buf* b : {&sp_lists, &d_in, &d_rows, &d_counts, &d_packed, &d_offsets, &h_rows, &h_counts, &d_cmask, &h_cmask, &d_xtab, &d_ytab,
                    &d_rawhead, &h_stage, &d_multi, &h_multi, &d_yuv, &d_yuvdesc, &h_yuvdesc, &d_feats, &d_feats_packed, &h_feats}) buf_free(*b);
     render_ctx_free(render);
+    jpeg_ctx_free(jpeg);
     if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1);
     for (auto e : pev) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) { if (ev_copied[i]) (void)hipEventDestroy(ev_copied[i]); if (ev_consumed[i]) (void)hipEventDestroy(ev_consumed[i]); }

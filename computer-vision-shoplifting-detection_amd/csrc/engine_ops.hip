@@ -927,5 +927,13 @@ int mi355_op_nms_ex(int device_id, const float* pred, const float* best, int n, 
     return MI355_OK;
 }
 
-}  // extern "C"
+// the transform stage of the JPEG encoder alone (jpeg_kernels.hip): quantised coefficients in zigzag order, on the GPU or by the host twin
+int mi355_op_jpeg_coefficients(int device, const mi355_render_frame* frames, int n, int quality, int subsampling, int16_t* const* coefs) {
+    if (!coefs) return fail(MI355_EINVAL, "jpeg: null output");
+    JpegCtx ctx;
+    const int rc = jpeg_run(ctx, device, frames, n, quality, subsampling, nullptr, coefs, nullptr, nullptr);
+    if (device >= 0) jpeg_ctx_free(ctx);
+    return rc;
+}
 
+}  // extern "C"

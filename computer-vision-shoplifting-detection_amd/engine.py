@@ -375,7 +375,7 @@ class YOLO:
     def predict(self, source=None, conf: Optional[float] = None, iou: float = 0.7, classes=None, max_det: int = 300,
                 imgsz: int = 640, half: Optional[bool] = None, verbose: bool = False, stream: bool = False,
                 feats: Optional[bool] = None, tile=None, overlap: float = 0.2, full_frame: bool = True, tile_iou: float = 0.5,
-                tile_metric: str = "ios", render=None, **kwargs) -> List[Results]:
+                tile_metric: str = "ios", render=None, encode=None, **kwargs) -> List[Results]:
         """``model.predict`` / ``model(...)``: ultralytics/engine/model.py:Model.predict.
         ``half=True`` runs the fp16-storage engine (fp32 accumulate; results differ from fp32 by fp16 rounding);
         ``None`` = the precision the model was constructed with (fp32 unless ``YOLO(..., half=True)``).
@@ -389,13 +389,18 @@ class YOLO:
         ``render``: True or a :class:`cvsd_amd.render.RenderSpec` (or a dict of its fields) -- every ``Results`` also
         carries ``rendered``, uint8 [H, W, 3]: a COPY of its frame with its boxes, labels and skeletons drawn in (and people pixelated,
         ``anonymize=``), rendered on the GPU from the copy of the frame this call already put there.  The source frames, the rows and
-        the keypoints are what they are without it.  ``None`` (default): the call as it always was."""
+        the keypoints are what they are without it.  ``None`` (default): the call as it always was.
+        ``encode``: "jpeg" or a :class:`cvsd_amd.jpeg.JpegSpec` (or a dict of its fields) -- every ``Results`` carries
+        ``jpeg``, the bytes of a baseline JFIF stream encoded on the GPU: of the rendered picture with ``render=`` (the picture stays
+        on the GPU and ``Results.rendered`` stays None unless ``keep_pixels``), of the source frame itself without.  Only the bytes
+        come back.  ``None`` (default): the call as it always was."""
+        from .jpeg import as_spec as as_jpeg_spec
         from .render import as_spec
         if isinstance(imgsz, (list, tuple)):
             imgsz = int(max(imgsz))
         conf = 0.25 if conf is None else float(conf)
-        spec = as_spec(render)
-        if spec is None:
+        spec, jspec = as_spec(render), as_jpeg_spec(encode)
+        if spec is None and jspec is None:
             if tile is not None:
                 batch, originals = self._as_tile_batch(source)
                 return self._predict_tiled(batch, originals, conf, iou, classes, max_det, imgsz, half, feats, tile, overlap, full_frame, tile_iou, tile_metric)
@@ -408,7 +413,7 @@ class YOLO:
             else:
                 batch, originals = self._as_batch(source)
                 res = self._predict_batch(batch, originals, conf, iou, classes, max_det, imgsz, half, feats)
-            return self._render_into(res, spec, None, lambda: self._batch_frames(batch))
+            return self._render_into(res, spec, None, lambda: self._batch_frames(batch), jspec)
 
     @staticmethod
     def _batch_frames(batch) -> list:
@@ -420,27 +425,43 @@ class YOLO:
             return list(batch.frames)
         return list(batch)
 
-    def _render_into(self, results, spec, sources, fallback=None):
+    def _render_into(self, results, spec, sources, fallback=None, jspec=None):
         """Fills ``Results.rendered`` of every non-None result with ONE render call on the engine that ran the detector.  ``sources``
         None: the frames of that engine's last call, from where the call left them on the GPU (``fallback()`` -> the frames to pass again
-        when a copy has been overwritten: host calls of more than two chunks); else one frame per result as ``ops.render`` takes them."""
+        when a copy has been overwritten: host calls of more than two chunks); else one frame per result as ``ops.render`` takes them.
+        ``jspec`` (``encode=``): the pictures stay on the GPU and ONE encode call on the same stream fills ``Results.jpeg`` (the pixels
+        come back only with ``keep_pixels``); with ``spec`` None the source frames themselves are encoded."""
         from . import ops
         from .render import primitives
         idx = [i for i, r in enumerate(results) if r is not None]
         if not idx:
             return results
-        prims = [primitives(results[i], spec) for i in idx]
         hnd = getattr(self, "_last_handle", None) or self._h
+        where = "numpy" if jspec is None else "cuda"
+
+        def on_frames(call):
+            if sources is not None:
+                return call([sources[i] for i in idx])
+            try:
+                return call(None)
+            except LookupError:
+                return call(fallback())
+
         with self._lock:
-            if sources is None:
-                try:
-                    pics = ops.render(None, prims, device=self.device, handle=hnd)
-                except LookupError:
-                    pics = ops.render(fallback(), prims, device=self.device, handle=hnd)
-            else:
-                pics = ops.render([sources[i] for i in idx], prims, device=self.device, handle=hnd)
-        for i, pic in zip(idx, pics):
-            results[i].rendered = pic
+            pics = None
+            if spec is not None:
+                prims = [primitives(results[i], spec) for i in idx]
+                pics = on_frames(lambda fr: ops.render(fr, prims, device=self.device, handle=hnd, out=where))
+            if jspec is not None:
+                enc = lambda fr: ops.jpeg_encode(fr, jspec.quality, jspec.subsampling, device=self.device, handle=hnd)   # noqa: E731
+                streams = enc(pics) if pics is not None else on_frames(enc)
+                for i, b in zip(idx, streams):
+                    results[i].jpeg = b
+                if pics is not None:
+                    pics = [p.cpu().numpy() for p in pics] if jspec.keep_pixels else None
+        if pics is not None:
+            for i, pic in zip(idx, pics):
+                results[i].rendered = pic
         return results
 
     def detect_rows(self, batch, conf: float = 0.25, iou: float = 0.7, classes=None, max_det: int = 300, imgsz: int = 640, half=None):
@@ -591,12 +612,14 @@ class YOLO:
         ``tile=...`` (with ``overlap``, ``full_frame``, ``tile_iou``, ``tile_metric``) is passed on to :meth:`predict`: the tracker consumes
         the merged rows of the tiled call (not together with ``with_reid``: a tiled call has no features).
         ``render=`` as in :meth:`predict`: drawn after the tracker step, so ``Results.rendered`` shows the tracker's boxes and ids; the
-        picture is rendered from the copy of the frame the motion compensation uploaded."""
+        picture is rendered from the copy of the frame the motion compensation uploaded.  ``encode=`` as in :meth:`predict`."""
+        from .jpeg import as_spec as as_jpeg_spec
         from .ops import DeviceFrame
         from .render import as_spec
         from .tracker import BYTETracker
         kwargs.pop("batch", None)
         spec = as_spec(kwargs.pop("render", None))
+        jspec = as_jpeg_spec(kwargs.pop("encode", None))
         conf = 0.1 if conf is None else conf
         cfg = self._tracker_settings("track", tracker, continuing=self._tracker is not None and persist)
         if cfg is not None:
@@ -646,9 +669,9 @@ class YOLO:
             # result is skipped when no track comes back
             tracks = self._tracker.update(res.boxes.data.numpy(), frame, feats=res.feats if reid else None)   # trackers/track.py: tracker.update(det, im0, feats)
             res = self._with_tracks(res, tracks)
-            if spec is not None:
+            if spec is not None or jspec is not None:
                 # the motion compensation's copy stays where it is until its next step; without one, the detector call's own copy
-                self._render_into([res], spec, None if dev is None else [DeviceFrame(dev[0], dev[1], dev[2])], lambda: [frame])
+                self._render_into([res], spec, None if dev is None else [DeviceFrame(dev[0], dev[1], dev[2])], lambda: [frame], jspec)
             results.append(res)
         return results
 
@@ -703,13 +726,17 @@ class YOLO:
 
         ``render``: as in :meth:`predict` -- every present camera's ``Results.rendered`` is its frame with the tracker's
         boxes and ids drawn in, all cameras in ONE render call reading the frames the motion compensation uploaded; an absent camera has
-        no picture, and a camera the motion gate skipped is drawn with the rows its tracker stepped on."""
+        no picture, and a camera the motion gate skipped is drawn with the rows its tracker stepped on.
+        ``encode`` (DESIGN.md 3.20): as in :meth:`predict` -- ``Results.jpeg`` of every present camera, all cameras in ONE encode call;
+        an absent camera has no bytes."""
         from .gmc import MultiGMC
+        from .jpeg import as_spec as as_jpeg_spec
         from .render import as_spec
         from .tracker import BYTETracker
         tracker = kwargs.pop("tracker", None)
         motion_gate = kwargs.pop("motion_gate", None)
         rspec = as_spec(kwargs.pop("render", None))
+        jspec = as_jpeg_spec(kwargs.pop("encode", None))
         unknown = set(kwargs) - {"iou", "classes", "max_det", "imgsz", "half", "feats", "show", "verbose"}
         if unknown:                                              # show / verbose are accepted and ignored, as in track()
             raise TypeError(f"track_cameras: unsupported argument(s) {sorted(unknown)} (iou, classes, max_det, imgsz, half pass through)")
@@ -783,7 +810,7 @@ class YOLO:
         if gate is None:
             for r, i in zip(res, present):
                 out[i] = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i], feats=r.feats if reid else None))    # an empty frame still steps
-            return out if rspec is None else self._render_cameras(out, rspec, frames, dev)
+            return out if rspec is None and jspec is None else self._render_cameras(out, rspec, frames, dev, jspec)
         fresh = dict(zip(run, res))
         for i in present:
             r = fresh.get(i)
@@ -795,14 +822,14 @@ class YOLO:
             r = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i], feats=r.feats if reid else None))
             r.motion = {"moving": bool(moving[i]), "changed": int(changed[i]), "skipped": i not in fresh}
             out[i] = r
-        return out if rspec is None else self._render_cameras(out, rspec, frames, dev)
+        return out if rspec is None and jspec is None else self._render_cameras(out, rspec, frames, dev, jspec)
 
-    def _render_cameras(self, out, spec, frames, dev):
-        """``track_cameras(render=...)``: the present cameras' pictures from the tick's uploaded frames (valid until the next tick's
+    def _render_cameras(self, out, spec, frames, dev, jspec=None):
+        """``track_cameras(render=..., encode=...)``: the present cameras' pictures from the tick's uploaded frames (valid until the next tick's
         motion-compensation step), or from the host frames when that step shared none"""
         from .ops import DeviceFrame
         src = [None if f is None else (f if dev is None else DeviceFrame(dev[i], f.shape[0], f.shape[1])) for i, f in enumerate(frames)]
-        return self._render_into(out, spec, src)
+        return self._render_into(out, spec, src, None, jspec)
 
     # ---- motion gate of track_cameras (DESIGN.md 3.18) --------------------------------------------------------------------------
     @staticmethod

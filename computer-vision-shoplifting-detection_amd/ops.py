@@ -530,27 +530,12 @@ class DeviceFrame:
         self.ptr, self.shape, self.pitch = int(ptr), (int(h), int(w), 3), int(pitch) if pitch else 3 * int(w)
 
 
-def render(frames, prims, device: int = 0, out: str = "numpy", timing: Optional[list] = None, handle=None):
-    """Draw primitive lists into COPIES of frames (csrc/render_kernels.hip, DESIGN.md 3.19): ``frames`` -- a BGR array [H, W, 3] (any row
-    pitch), a uint8 CUDA tensor [H, W, 3] on ``device`` (any row pitch, read in place and left unchanged), a ``cvsd_amd.YUVFrame``
-    (rendered from the BGR the ingest conversion makes of it), or a list of them of any sizes; ``prims`` -- int32 [P, 8] records
-    (``cvsd_amd.render.primitives`` builds them), one array per frame.  One call, two launches, whatever the number of frames.
-    ``out="numpy"``: uint8 arrays; ``"cuda"``: tensors on ``device``, nothing comes back to the host.  A single frame gives a single
-    picture, a list a list.  ``device=-1`` runs the host twin and touches no GPU.  ``timing``: a list that receives the launches' ms.
-    ``handle``: an engine handle -- the call runs on its stream with its scratch (``mi355_yolo_render``), and ``frames=None`` then means
-    the frames of that handle's last call, read from where the call left them on the GPU."""
+def _frame_descriptors(frames, device: int, handle):
+    """The ``mi355_render_frame`` records of a render or JPEG call -> (records, what they point into, ``frames`` or None): a list of
+    arrays, CUDA tensors, ``YUVFrame`` and ``DeviceFrame``; or None with a handle -- the frames of the handle's last call."""
     import torch
     from .yuv import YUVFrame
-    if out not in ("numpy", "cuda"):
-        raise ValueError(f"out must be 'numpy' or 'cuda', got {out!r}")
-    device = int(device)
-    if out == "cuda" and device < 0:
-        raise ValueError("out='cuda' needs a GPU: the host twin (device=-1) returns numpy arrays")
     lib = _lib.lib()
-    single = isinstance(frames, (np.ndarray, YUVFrame, torch.Tensor, DeviceFrame))
-    if single:
-        frames, prims = [frames], [prims]
-    prims = list(prims)
     keep, fd = [], []
     if frames is None:
         if handle is None:
@@ -595,6 +580,31 @@ def render(frames, prims, device: int = 0, out: str = "numpy", timing: Optional[
             h, w = int(f.shape[0]), int(f.shape[1])
             keep.append(f)
             fd.append(_lib.RenderFrame(ptr or 1, h, w, int(max(pitch, 3 * w)), int(on_dev)))
+    return fd, keep, frames
+
+
+def render(frames, prims, device: int = 0, out: str = "numpy", timing: Optional[list] = None, handle=None):
+    """Draw primitive lists into COPIES of frames (csrc/render_kernels.hip, DESIGN.md 3.19): ``frames`` -- a BGR array [H, W, 3] (any row
+    pitch), a uint8 CUDA tensor [H, W, 3] on ``device`` (any row pitch, read in place and left unchanged), a ``cvsd_amd.YUVFrame``
+    (rendered from the BGR the ingest conversion makes of it), or a list of them of any sizes; ``prims`` -- int32 [P, 8] records
+    (``cvsd_amd.render.primitives`` builds them), one array per frame.  One call, two launches, whatever the number of frames.
+    ``out="numpy"``: uint8 arrays; ``"cuda"``: tensors on ``device``, nothing comes back to the host.  A single frame gives a single
+    picture, a list a list.  ``device=-1`` runs the host twin and touches no GPU.  ``timing``: a list that receives the launches' ms.
+    ``handle``: an engine handle -- the call runs on its stream with its scratch (``mi355_yolo_render``), and ``frames=None`` then means
+    the frames of that handle's last call, read from where the call left them on the GPU."""
+    import torch
+    from .yuv import YUVFrame
+    if out not in ("numpy", "cuda"):
+        raise ValueError(f"out must be 'numpy' or 'cuda', got {out!r}")
+    device = int(device)
+    if out == "cuda" and device < 0:
+        raise ValueError("out='cuda' needs a GPU: the host twin (device=-1) returns numpy arrays")
+    lib = _lib.lib()
+    single = isinstance(frames, (np.ndarray, YUVFrame, torch.Tensor, DeviceFrame))
+    if single:
+        frames, prims = [frames], [prims]
+    prims = list(prims)
+    fd, keep, frames = _frame_descriptors(frames, device, handle)
     if len(fd) != len(prims):
         raise ValueError("prims: one int32 [P, 8] array per frame")
     od, outs, pp = [], [], []
@@ -623,6 +633,66 @@ def render(frames, prims, device: int = 0, out: str = "numpy", timing: Optional[
         _lib.check(lib.mi355_render(device, (_lib.RenderFrame * n)(*fd), n, ptrs, counts, (_lib.RenderOut * n)(*od), None, msp))
     if timing is not None:
         timing.append(float(ms.value))
+    return outs[0] if single else outs
+
+
+def _jpeg_args(quality, subsampling):
+    ss = {"420": _lib.JPEG_420, "444": _lib.JPEG_444, 420: _lib.JPEG_420, 444: _lib.JPEG_444}.get(subsampling)
+    if ss is None:
+        raise ValueError(f"subsampling must be '420' or '444', got {subsampling!r}")
+    return int(quality), ss
+
+
+def jpeg_encode(frames, quality: int = 85, subsampling: str = "420", device: int = 0, handle=None, timing: Optional[list] = None):
+    """Encode BGR frames as baseline JFIF streams (csrc/jpeg_kernels.hip) -> ``bytes`` (a list of ``bytes`` for a list).
+    ``frames``: what :func:`render` takes -- arrays of any pitch, uint8 CUDA tensors on ``device`` read in place, ``cvsd_amd.YUVFrame``
+    (from the BGR the ingest conversion makes of it), :class:`DeviceFrame`, or a list of them of any sizes.  One call, three launches,
+    whatever the number of frames; only the streams' bytes come back from the GPU.  ``quality`` 1 .. 100 (the IJG scaling of the Annex K
+    tables), ``subsampling`` "420" or "444".  ``device=-1`` runs the host twin and touches no GPU.  ``handle``: an engine handle -- the
+    call runs on its stream with its scratch (``mi355_yolo_encode``), and ``frames=None`` then means the frames of that handle's last
+    call, read from where the call left them on the GPU.  ``timing``: a list that receives the launches' ms."""
+    import torch
+    from .yuv import YUVFrame
+    device = int(device)
+    quality, ss = _jpeg_args(quality, subsampling)
+    lib = _lib.lib()
+    single = isinstance(frames, (np.ndarray, YUVFrame, torch.Tensor, DeviceFrame))
+    fd, keep, frames = _frame_descriptors([frames] if single else frames, device, handle)
+    n = len(fd)
+    bufs, od = [], []
+    for f in fd:
+        cap = int(lib.mi355_jpeg_bound(f.height, f.width, ss))
+        b = np.empty(max(cap, 1), np.uint8)                 # the worst case of the frame's size; only the stream's pages are ever touched
+        bufs.append(b)
+        od.append(_lib.JpegOut(b.ctypes.data, cap, 0))
+    outs = (_lib.JpegOut * n)(*od)
+    ms = C.c_float(0.0)
+    msp = C.byref(ms) if timing is not None else None
+    if handle is not None:
+        _lib.check(lib.mi355_yolo_encode(handle, None if frames is None else (_lib.RenderFrame * n)(*fd), n, quality, ss, outs, msp))
+    else:
+        _lib.check(lib.mi355_jpeg_encode(device, (_lib.RenderFrame * n)(*fd), n, quality, ss, outs, None, msp))
+    if timing is not None:
+        timing.append(float(ms.value))
+    res = [bufs[i][:outs[i].length].tobytes() for i in range(n)]
+    return res[0] if single else res
+
+
+def jpeg_coefficients(frames, quality: int = 85, subsampling: str = "420", device: int = 0):
+    """The transform stage of :func:`jpeg_encode` alone (``mi355_op_jpeg_coefficients``): per frame int16 [blocks, 64] -- quantised DCT
+    coefficients in zigzag order, blocks in scan order (MCU rows, MCUs, then Y0 Y1 Y2 Y3 Cb Cr for "420", Y Cb Cr for "444").
+    ``device=-1`` runs the host twin."""
+    import torch
+    from .yuv import YUVFrame
+    device = int(device)
+    quality, ss = _jpeg_args(quality, subsampling)
+    lib = _lib.lib()
+    single = isinstance(frames, (np.ndarray, YUVFrame, torch.Tensor, DeviceFrame))
+    fd, keep, frames = _frame_descriptors([frames] if single else frames, device, None)
+    m, per = (16, 6) if ss == _lib.JPEG_420 else (8, 3)
+    outs = [np.zeros((max(-(-f.height // m) * -(-f.width // m) * per, 0), 64), np.int16) for f in fd]
+    ptrs = (C.c_void_p * len(fd))(*[o.ctypes.data or 1 for o in outs])
+    _lib.check(lib.mi355_op_jpeg_coefficients(device, (_lib.RenderFrame * len(fd))(*fd), len(fd), quality, ss, ptrs))
     return outs[0] if single else outs
 
 

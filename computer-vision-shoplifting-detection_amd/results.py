@@ -187,6 +187,9 @@ class Results:
         # call's device copy; None for any other call
         self.rendered = None
         self._render_device = 0
+        # predict / track / track_cameras(encode=...): bytes, a baseline JFIF stream of the rendered picture (with render=) or of the
+        # frame itself, encoded on the GPU; None for any other call
+        self.jpeg = None
 
     def plot(self, **spec) -> np.ndarray:
         """``results[0].plot()``: this result drawn into a COPY of its frame -> uint8 [H, W, 3] BGR, rendered on the GPU
@@ -198,6 +201,14 @@ class Results:
             raise ValueError("this Results holds no image (its frames were on the GPU, or YUV planes): ask for the picture at call time, "
                              "predict / track / track_cameras(..., render=True), and read Results.rendered")
         return ops.render(np.asarray(self.orig_img), primitives(self, RenderSpec(**spec)), device=self._render_device)
+
+    def save(self, filename) -> str:
+        """Writes ``Results.jpeg`` -- the stream ``encode=`` of predict / track / track_cameras made on the GPU -- to ``filename``."""
+        if self.jpeg is None:
+            raise ValueError("this Results holds no JPEG stream: ask for one at call time, predict / track / track_cameras(..., encode='jpeg')")
+        with open(filename, "wb") as fh:
+            fh.write(self.jpeg)
+        return str(filename)
 
     def __len__(self):
         return len(self.boxes) if self.boxes is not None else 0
@@ -216,7 +227,7 @@ class Results:
             r.tile_idx = self.tile_idx[[ix]] if isinstance(ix, (int, np.integer)) else self.tile_idx[ix]
         r.tiles = self.tiles
         r.motion = self.motion
-        r.rendered, r._render_device = self.rendered, self._render_device
+        r.rendered, r._render_device, r.jpeg = self.rendered, self._render_device, self.jpeg
         return r
 
     def update(self, boxes=None):
@@ -236,5 +247,5 @@ class Results:
         r.feats = self.feats
         r.tile_idx, r.tiles = self.tile_idx, self.tiles
         r.motion = self.motion
-        r.rendered, r._render_device = self.rendered, self._render_device
+        r.rendered, r._render_device, r.jpeg = self.rendered, self._render_device, self.jpeg
         return r

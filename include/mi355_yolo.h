@@ -663,6 +663,48 @@ int  mi355_render(int device, const mi355_render_frame* frames, int n, const int
 int  mi355_yolo_render(mi355_yolo* h, const mi355_render_frame* frames, int n, const int32_t* const* prims, const int* n_prims,
                        const mi355_render_out* outs, float* launch_ms);
 int  mi355_yolo_last_frames(mi355_yolo* h, mi355_render_frame* frames_out, int cap, int* n);
+
+/* ---- evidence frames as JPEG: a BGR frame in, a baseline JFIF stream out ------------------------------------------------
+ * Integer arithmetic throughout (csrc/jpeg_codec.h; the kernels of csrc/jpeg_kernels.hip and their host twin give the same bytes).
+ * The stream: SOI, APP0 (JFIF 1.01, no thumbnail), DQT (luminance), DQT (chrominance), SOF0, DHT x 4 (DC 0, AC 0, DC 1, AC 1), DRI, SOS,
+ * entropy-coded data, EOI.  Baseline sequential DCT, 8 bits, components Y (1), Cb (2), Cr (3); MI355_JPEG_420: Y 2x2 and chroma 1x1,
+ * 16 x 16 MCUs, six blocks per MCU (Y0 Y1 / Y2 Y3, Cb, Cr); MI355_JPEG_444: 8 x 8 MCUs of three blocks.  Height and width 1 .. 65535.
+ *   tables   Annex K.1 / K.2 scaled by the IJG rule: s = 5000 / q for q < 50, else 200 - 2 q; step = (base * s + 50) / 100 clamped to
+ *            1 .. 255; quality q in 1 .. 100.  Huffman: the four typical tables of Annex K.3, no optimisation pass.
+ *   restart  the restart interval is the number of MCUs of one MCU row: every MCU row is a segment with DC predictors starting at 0,
+ *            its last byte padded with 1-bits, 0x00 behind every 0xFF data byte, and RSTm, m = row mod 8, between it and the next (none
+ *            behind the last).  The rows are independent, which is what lets a GPU code them side by side.
+ *   pixels   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16,
+ *            Cr = (32768 R - 27439 G - 5329 B + 8421375) >> 16.  The frame is extended to whole MCUs by repeating its last column and
+ *            row; 4:2:0 chroma is (a + b + c + d + 2) >> 2 of the four Cb (Cr) values; level shift -128; forward DCT: the
+ *            Loeffler-Ligtenberg-Moschytz factorisation in 13-bit fixed point, rows then columns (jpeg_fdct_1d), giving 8 x the
+ *            coefficient; quantisation (|c| + 4 step) / (8 step) with the sign restored (round half away from zero); zigzag order.
+ *   capacity mi355_jpeg_bound(height, width, subsampling): no stream of such a frame is longer, whatever the pixels and the quality --
+ *            640 for the header + 416 per 8 x 8 block (1660 bits: the longest DC code and category, 63 x the longest AC code and
+ *            category; twice that for stuffing) + 2 per MCU row + 2.  outs[i].capacity must be at least that: there is no truncation path.
+ * Out-of-range quality, an unknown subsampling, a zero or > 65535 dimension or a capacity below the bound is MI355_EINVAL with a message
+ * naming the field, before a byte of any output is written.
+ *   mi355_jpeg_encode   device >= 0: that GPU; -1: the host twin (host memory only), which touches no GPU.  frames[i]: host memory (one
+ *            upload per frame) or memory of that GPU (on_device = 1, read in place).  outs[i].data: HOST memory; the call sets
+ *            outs[i].length.  All frames of a call, whatever their sizes and pitches, take three launches on `stream`; the call returns
+ *            when they and the copies have finished.  Only the streams' bytes cross the bus.  launch_ms (or NULL): the launches' device time.
+ *   mi355_yolo_encode   the same on an engine handle: its stream, scratch kept between calls; frames = NULL encodes the frames of the
+ *            handle's last blocking infer call where that call left them (mi355_yolo_render's rules on which copies are alive).
+ *   mi355_op_jpeg_coefficients   the transform stage alone: coefs[i] (host) receives int16 [blocks][64], quantised, zigzag order, blocks
+ *            in scan order (MCU rows, MCUs, blocks of an MCU); blocks = MCUs x (6 | 3). */
+#define MI355_JPEG_420 420
+#define MI355_JPEG_444 444
+typedef struct mi355_jpeg_out {
+    uint8_t* data;                      /* host memory of `capacity` bytes */
+    int64_t capacity;
+    int64_t length;                     /* set by the call */
+} mi355_jpeg_out;
+int64_t mi355_jpeg_bound(int height, int width, int subsampling);
+int  mi355_jpeg_encode(int device, const mi355_render_frame* frames, int n, int quality, int subsampling, mi355_jpeg_out* outs, void* stream,
+                       float* launch_ms);
+int  mi355_yolo_encode(mi355_yolo* h, const mi355_render_frame* frames, int n, int quality, int subsampling, mi355_jpeg_out* outs,
+                       float* launch_ms);
+int  mi355_op_jpeg_coefficients(int device, const mi355_render_frame* frames, int n, int quality, int subsampling, int16_t* const* coefs);
 /* Depthwise 3x3 conv (stride 1, pad 1) + bias (+SiLU) (+residual) on channel views, fp32, as the engine runs YOLO11's
  * DWConv and Attention.pe (ultralytics nn/modules/conv.py:DWConv, Conv with groups = c).  x[n][h][w][x_cs] holds the input view at
  * channels x_off .. x_off+c-1; residual (or NULL) [n][h][w][res_cs] at res_off; y[n][h][w][y_cs] is read in, its view y_off ..
