@@ -86,7 +86,19 @@ class JpegOut(C.Structure):
     _fields_ = [("data", C.c_void_p), ("capacity", C.c_int64), ("length", C.c_int64)]
 
 
+class JpegStream(C.Structure):
+    """mi355_jpeg_stream: one JPEG stream in host memory; the call reports where its entropy stage ran"""
+    _fields_ = [("data", C.c_void_p), ("length", C.c_int64), ("entropy_used", C.c_int), ("reserved", C.c_int)]
+
+
+class JpegStreamInfo(C.Structure):
+    """mi355_jpeg_stream_info"""
+    _fields_ = [("height", C.c_int), ("width", C.c_int), ("components", C.c_int), ("subsampling", C.c_int), ("restart_interval", C.c_int),
+                ("segments", C.c_int), ("blocks", C.c_int64)]
+
+
 RENDER_WORDS, RENDER_MAX_PRIMS, RENDER_MAX_FRAMES = 8, 16384, 256      # MI355_RENDER_*
+JPEG_ENTROPY = {"auto": 0, "gpu": 1, "host": 2}                         # MI355_JPEG_ENTROPY_*
 JPEG_420, JPEG_444 = 420, 444           # MI355_JPEG_*
 MOTION_MAX_CAMERAS = 64                 # MI355_MOTION_MAX_CAMERAS
 TILE_IOS, TILE_IOU = 0, 1               # MI355_TILE_IOS / MI355_TILE_IOU
@@ -253,6 +265,10 @@ SIGNATURES = {
     "mi355_jpeg_encode": (C.c_int, [C.c_int, _P(RenderFrame), C.c_int, C.c_int, C.c_int, _P(JpegOut), C.c_void_p, _f32p]),
     "mi355_yolo_encode": (C.c_int, [C.c_void_p, _P(RenderFrame), C.c_int, C.c_int, C.c_int, _P(JpegOut), _f32p]),
     "mi355_op_jpeg_coefficients": (C.c_int, [C.c_int, _P(RenderFrame), C.c_int, C.c_int, C.c_int, _P(C.c_void_p)]),
+    "mi355_jpeg_info": (C.c_int, [C.c_void_p, C.c_int64, _P(JpegStreamInfo)]),
+    "mi355_jpeg_decode": (C.c_int, [C.c_int, _P(JpegStream), C.c_int, C.c_int, _P(RenderOut), _i32p, C.c_void_p, _f32p]),
+    "mi355_yolo_decode": (C.c_int, [C.c_void_p, _P(JpegStream), C.c_int, C.c_int, _P(RenderOut), _i32p, _f32p]),
+    "mi355_op_jpeg_decode_coefficients": (C.c_int, [C.c_int, _P(JpegStream), C.c_int, C.c_int, _P(C.c_void_p), _i32p]),
     "mi355_op_nms": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,
                                C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
     "mi355_op_nms_ex": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,

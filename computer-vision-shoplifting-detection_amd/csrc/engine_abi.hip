@@ -1,6 +1,7 @@
 // The C ABI of include/mi355_yolo.h: engine handle entry points (create / infer / raw_head / plan_info / memory_plan ...).
 #include "engine_internal.h"
 #include "jpeg_codec.h"
+#include "jpeg_decode.h"
 
 namespace mi355 { thread_local std::string g_err; }
 using namespace mi355;
@@ -224,6 +225,15 @@ int mi355_yolo_encode(mi355_yolo* h, const mi355_render_frame* frames, int n, in
     HIPCHK(hipSetDevice(h->device));
     if (h->async_pending) { HIPCHK(hipStreamSynchronize(h->stream)); h->async_pending = false; }
     return jpeg_run(h->jpeg, h->device, frames, n, quality, subsampling, outs, nullptr, h->stream, launch_ms);
+}
+
+// ------------------------------------------------------------------------------------- JPEG ingest (jpeg_decode_kernels.hip)
+int mi355_yolo_decode(mi355_yolo* h, mi355_jpeg_stream* streams, int n, int entropy, const mi355_render_out* outs, int* status, float* launch_ms) {
+    if (!h) return fail(MI355_EINVAL, "jpeg decode: null handle");
+    if (!outs) return fail(MI355_EINVAL, "jpeg decode: null output");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->async_pending) { HIPCHK(hipStreamSynchronize(h->stream)); h->async_pending = false; }
+    return jpeg_dec_call(&h->jpeg_dec, h->device, streams, n, entropy, outs, nullptr, status, h->stream, launch_ms);
 }
 
 }  // extern "C"

@@ -70,6 +70,13 @@ int jpeg_run(JpegCtx& ctx, int device, const mi355_render_frame* frames, int n, 
              int16_t* const* coefs, hipStream_t st, float* launch_ms);
 void jpeg_ctx_free(JpegCtx& ctx);
 
+// jpeg_decode_kernels.hip: the grow-only scratch of JPEG decode calls -- one device buffer [descriptors | Huffman tables |
+// status | per frame: segment offsets and scan bytes, or host-decoded coefficients || coefficients of the lane frames | planes | frames
+// bound for the host], the pinned image of its first part and the pinned landing areas of the frames and the status words.  The calls
+// themselves are declared in jpeg_decode.h.
+struct JpegDecCtx { Buf d_work; Buf h_img{true}, h_out{true}, h_stat{true}; hipEvent_t ev0 = nullptr, ev1 = nullptr; };
+void jpeg_dec_ctx_free(JpegDecCtx& ctx);
+
 // OP_DWCONV / OP_ATTN (YOLO11, file version 2): FileOp.r0 = groups (== channels) / heads; for OP_ATTN k = key_dim, s = head_dim
 enum { OP_STEM = 0, OP_CONV = 1, OP_UPSAMPLE = 2, OP_SPPF_POOL = 3, OP_DWCONV = 4, OP_ATTN = 5 };
 
@@ -300,6 +307,7 @@ struct mi355_yolo {
     std::vector<LastFrame> last_frames;
     RenderCtx render;
     JpegCtx jpeg;                       // mi355_yolo_encode's scratch
+    JpegDecCtx jpeg_dec;                // mi355_yolo_decode's scratch
     unsigned long long plan_hash = 0;   // fingerprint of the candidate lists + the chosen indices of the current shape
     int plan_source = 0, plan_launches = 0;   // 0 static guess (autotune off), 1 memory, 2 this machine's plan cache, 3 tuned now, 4 shipped plan file; launches of one pass (stem..last conv)
     bool async_pending = false;         // mi355_yolo_infer_device_async work may still be in flight on `stream`

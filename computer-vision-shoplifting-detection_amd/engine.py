@@ -19,6 +19,7 @@ import torch
 from . import _lib
 from .results import Results
 from .weights import build_from_state_dict, from_bytes
+from .jpeg_decode import decode_sources, has_frames as has_jpeg_frames
 from .yuv import YUVFrame, as_frames, struct_array
 
 COCO_NAMES = ["person", "bicycle", "car", "motorcycle", "airplane", "bus", "train", "truck", "boat", "traffic light",
@@ -390,6 +391,8 @@ class YOLO:
         carries ``rendered``, uint8 [H, W, 3]: a COPY of its frame with its boxes, labels and skeletons drawn in (and people pixelated,
         ``anonymize=``), rendered on the GPU from the copy of the frame this call already put there.  The source frames, the rows and
         the keypoints are what they are without it.  ``None`` (default): the call as it always was.
+        ``source`` may hold :class:`cvsd_amd.JPEGFrame`s: baseline JPEG streams, all decoded to BGR on the GPU in one call
+        in front of everything else; the call then is what it is for CUDA BGR tensors of the same pixels.
         ``encode``: "jpeg" or a :class:`cvsd_amd.jpeg.JpegSpec` (or a dict of its fields) -- every ``Results`` carries
         ``jpeg``, the bytes of a baseline JFIF stream encoded on the GPU: of the rendered picture with ``render=`` (the picture stays
         on the GPU and ``Results.rendered`` stays None unless ``keep_pixels``), of the source frame itself without.  Only the bytes
@@ -399,6 +402,11 @@ class YOLO:
         if isinstance(imgsz, (list, tuple)):
             imgsz = int(max(imgsz))
         conf = 0.25 if conf is None else float(conf)
+        if has_jpeg_frames(source):
+            # JPEG ingest: every JPEGFrame of the call is decoded in ONE call on the engine's stream into CUDA tensors;
+            # from here on the call is the one it is for CUDA BGR tensors
+            with self._lock:                   # the handle's stream and decode scratch: no other call of this model in between
+                source = decode_sources(source, self.device, self._handle(half, feats))
         spec, jspec = as_spec(render), as_jpeg_spec(encode)
         if spec is None and jspec is None:
             if tile is not None:
@@ -628,6 +636,10 @@ class YOLO:
         reid = self._tracker.with_reid
         if reid:
             kwargs["feats"] = True
+        if has_jpeg_frames(source):
+            # JPEG frames are decoded on the GPU in one call and, as YUV frames below, brought to the host for the motion compensation
+            with self._lock:
+                source = decode_sources(source, self.device, self._h, to_host=True)
         yuv = as_frames(source)
         if yuv is not None:
             # the convenience form: the motion compensation takes a host BGR frame, so a YUV frame is converted on the GPU and its BGR
@@ -742,6 +754,9 @@ class YOLO:
             raise TypeError(f"track_cameras: unsupported argument(s) {sorted(unknown)} (iou, classes, max_det, imgsz, half pass through)")
         conf = 0.1 if conf is None else float(conf)
         # a camera that delivers a YUVFrame: converted on the GPU, its BGR bytes brought to the host for the motion compensation (as track())
+        if has_jpeg_frames(frames):                              # ... and the cameras that deliver JPEGFrames: one decode call for all of them
+            with self._lock:
+                frames = decode_sources(list(frames), self.device, self._h, to_host=True)
         frames = [f.to_bgr(self.device) if isinstance(f, YUVFrame) else f for f in frames]
         n = len(frames)
         if n == 0:

@@ -696,6 +696,95 @@ def jpeg_coefficients(frames, quality: int = 85, subsampling: str = "420", devic
     return outs[0] if single else outs
 
 
+def _jpeg_streams(streams):
+    """-> (list of JPEGFrame, single?): bytes-like streams are parsed here, so a refused one raises ``ValueError`` naming its index"""
+    from .jpeg_decode import JPEGFrame
+    single = isinstance(streams, (JPEGFrame, bytes, bytearray, memoryview))
+    fr = []
+    for i, s in enumerate([streams] if single else list(streams)):
+        if not isinstance(s, JPEGFrame):
+            try:
+                s = JPEGFrame(s)
+            except ValueError as e:
+                raise ValueError(f"streams[{i}]: {e}") from None
+        fr.append(s)
+    if not fr:
+        raise ValueError("streams: pass a JPEGFrame (or its bytes) or a list of them")
+    return fr, single
+
+
+def jpeg_decode(streams, device: int = 0, entropy: str = "auto", out=None, as_tensor: bool = False, handle=None,
+                timing: Optional[list] = None):
+    """Decode baseline JPEG streams to BGR frames (csrc/jpeg_decode_kernels.hip) -> uint8 [H, W, 3] (a list for a list).
+    ``streams``: ``cvsd_amd.JPEGFrame`` or bytes-like, or a list of them of any sizes and layouts (4:4:4, 4:2:2, 4:2:0, gray; with or
+    without restart markers).  One call, three launches, whatever the number of streams; only the compressed bytes go up.
+    ``entropy``: "gpu" -- one GPU lane per restart segment (a stream without restart markers is one segment on one lane: slow, correct);
+    "host" -- Huffman decoding on the calling thread, coefficients uploaded; "auto" -- "gpu" for a stream with a restart interval,
+    "host" for one without.  ``as_tensor=True``: CUDA tensors on ``device`` that never visit the host.  ``out``: arrays (or, on a GPU,
+    CUDA tensors) [H, W, 3] uint8 to write into, last strides (3, 1), any row pitch.  ``device=-1`` runs the host twin and touches no
+    GPU.  ``handle``: an engine handle -- the call runs on its stream with its scratch (``mi355_yolo_decode``).  ``timing``: a list that
+    receives ``{"ms": the launches' device time, "entropy": ["gpu" | "host" per stream]}``.  A stream whose entropy-coded data is
+    corrupt raises ``ValueError`` naming its index; the other streams' frames (in ``out``) are complete."""
+    import torch
+    device = int(device)
+    if entropy not in _lib.JPEG_ENTROPY:
+        raise ValueError(f"entropy must be 'auto', 'gpu' or 'host', got {entropy!r}")
+    if as_tensor and device < 0:
+        raise ValueError("as_tensor=True needs a GPU: the host twin (device=-1) returns numpy arrays")
+    fr, single = _jpeg_streams(streams)
+    n = len(fr)
+    if out is None:
+        outs = [torch.empty((f.shape[0], f.shape[1], 3), dtype=torch.uint8, device=f"cuda:{device}") if as_tensor
+                else np.empty((f.shape[0], f.shape[1], 3), np.uint8) for f in fr]
+    else:
+        outs = [out] if single and not isinstance(out, (list, tuple)) else list(out)
+        if len(outs) != n:
+            raise ValueError("out: one array per stream")
+    od = []
+    for f, o in zip(fr, outs):
+        on_dev = isinstance(o, torch.Tensor) and o.is_cuda
+        if isinstance(o, torch.Tensor) and not on_dev:
+            raise ValueError("out: numpy arrays or CUDA tensors")
+        dt_ok = o.dtype == (torch.uint8 if on_dev else np.uint8)
+        st = tuple(o.stride()) if on_dev else tuple(o.strides) if isinstance(o, np.ndarray) else None
+        if st is None or not dt_ok or tuple(o.shape) != (f.shape[0], f.shape[1], 3) or st[2] != 1 or st[1] != 3 or (f.shape[0] > 1 and st[0] < 3 * f.shape[1]):
+            raise ValueError(f"out: uint8 [H, W, 3] of the stream's size {f.shape} with pixel stride 3 and rows of at least 3 W bytes")
+        if on_dev and (device < 0 or o.device.index != device):
+            raise ValueError("out: a CUDA tensor must live on the call's GPU")
+        if not on_dev and not o.flags.writeable:
+            raise ValueError("out: a read-only array")
+        od.append(_lib.RenderOut(o.data_ptr() if on_dev else o.ctypes.data, int(max(st[0], 3 * f.shape[1])), int(on_dev)))
+    if any(d.on_device for d in od):
+        torch.cuda.current_stream(device).synchronize()      # the call runs on its own stream
+    sd = (_lib.JpegStream * n)(*[f.struct() for f in fr])
+    status = (C.c_int * n)()
+    ms = C.c_float(0.0)
+    msp = C.byref(ms) if timing is not None else None
+    lib = _lib.lib()
+    if handle is not None:
+        rc = lib.mi355_yolo_decode(handle, sd, n, _lib.JPEG_ENTROPY[entropy], (_lib.RenderOut * n)(*od), status, msp)
+    else:
+        rc = lib.mi355_jpeg_decode(device, sd, n, _lib.JPEG_ENTROPY[entropy], (_lib.RenderOut * n)(*od), status, None, msp)
+    _lib.check(rc)
+    if timing is not None:
+        timing.append({"ms": float(ms.value), "entropy": ["gpu" if s.entropy_used == 1 else "host" for s in sd]})
+    return outs[0] if single else outs
+
+
+def jpeg_decode_coefficients(streams, device: int = 0, entropy: str = "auto"):
+    """The entropy stage of :func:`jpeg_decode` alone (``mi355_op_jpeg_decode_coefficients``): per stream int16 [blocks, 64] -- the
+    quantised coefficients in zigzag order, blocks in scan order, DC absolute.  ``device=-1`` runs the host twin."""
+    if entropy not in _lib.JPEG_ENTROPY:
+        raise ValueError(f"entropy must be 'auto', 'gpu' or 'host', got {entropy!r}")
+    fr, single = _jpeg_streams(streams)
+    n = len(fr)
+    outs = [np.zeros((f.blocks, 64), np.int16) for f in fr]
+    ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    sd = (_lib.JpegStream * n)(*[f.struct() for f in fr])
+    _lib.check(_lib.lib().mi355_op_jpeg_decode_coefficients(int(device), sd, n, _lib.JPEG_ENTROPY[entropy], ptrs, (C.c_int * n)()))
+    return outs[0] if single else outs
+
+
 def nms(pred: np.ndarray, nc: int, conf: float = 0.25, iou: float = 0.7, classes: Optional[Sequence[int]] = None,
         max_det: int = 300, device: int = 0):
     """non_max_suppression on pred [N, 4+nc+extra, A] -> list of (rows [n,6+extra], anchor_idx [n])."""

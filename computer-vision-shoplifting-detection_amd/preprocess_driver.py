@@ -62,9 +62,12 @@ class ImageDirCapture:
 
     EXTS = (".jpg", ".jpeg", ".png", ".bmp")
 
-    def __init__(self, source: str):
+    def __init__(self, source: str, decode: bool = True):
+        """``decode=False``: ``.jpg`` / ``.jpeg`` files are not decoded here but handed on as ``cvsd_amd.JPEGFrame`` -- compressed bytes the
+        engine decodes on the GPU; other formats are decoded as always."""
         self._files: Optional[List[str]] = None
         self._pos = 0
+        self._decode = bool(decode)
         for cand in (source, os.path.splitext(source)[0]):
             if os.path.isdir(cand):
                 names = sorted((n for n in os.listdir(cand) if n.lower().endswith(self.EXTS)), key=self._natural_key)
@@ -87,6 +90,11 @@ class ImageDirCapture:
     def read(self):
         if self._files is None or self._pos >= len(self._files):
             return False, None
+        if not self._decode and self._files[self._pos].lower().endswith((".jpg", ".jpeg")):
+            from .jpeg_decode import JPEGFrame
+            frame = JPEGFrame.open(self._files[self._pos])
+            self._pos += 1
+            return True, frame
         from PIL import Image
         with Image.open(self._files[self._pos]) as im:
             rgb = np.asarray(im.convert("RGB"), dtype=np.uint8)
@@ -100,6 +108,49 @@ class ImageDirCapture:
 
     def release(self):
         self._files = None
+
+
+class MjpegCapture:
+    """cv2.VideoCapture look-alike over a raw concatenated MJPEG file (``.mjpeg`` / ``.mjpg``: one JPEG stream behind the other, as an IP
+    camera's HTTP stream is commonly dumped).  The file is split at SOI / EOI outside entropy-coded data; ``read()`` yields
+    ``cvsd_amd.JPEGFrame``s -- nothing is decoded here, the engine does that on the GPU.  No AVI or MP4 container is
+    parsed.  Opt-in: ``open_capture`` does not return it."""
+
+    EXTS = (".mjpeg", ".mjpg")
+
+    def __init__(self, source: str):
+        self._streams: Optional[List[bytes]] = None
+        self._pos = 0
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            data = bytes(source)
+        elif str(source).lower().endswith(self.EXTS) and os.path.isfile(source):
+            with open(source, "rb") as f:
+                data = f.read()
+        else:
+            return
+        from .jpeg_decode import split_mjpeg
+        streams = split_mjpeg(data)
+        if streams:
+            self._streams = streams
+
+    def isOpened(self) -> bool:
+        return self._streams is not None
+
+    def read(self):
+        if self._streams is None or self._pos >= len(self._streams):
+            return False, None
+        from .jpeg_decode import JPEGFrame
+        frame = JPEGFrame(self._streams[self._pos])
+        self._pos += 1
+        return True, frame
+
+    def get(self, prop):
+        if prop == CAP_PROP_FRAME_COUNT:
+            return float(len(self._streams)) if self._streams is not None else 0.0
+        return float(self._pos) if prop == CAP_PROP_POS_FRAMES else 0.0
+
+    def release(self):
+        self._streams = None
 
 
 def open_capture(path: str):

@@ -705,6 +705,69 @@ int  mi355_jpeg_encode(int device, const mi355_render_frame* frames, int n, int 
 int  mi355_yolo_encode(mi355_yolo* h, const mi355_render_frame* frames, int n, int quality, int subsampling, mi355_jpeg_out* outs,
                        float* launch_ms);
 int  mi355_op_jpeg_coefficients(int device, const mi355_render_frame* frames, int n, int quality, int subsampling, int16_t* const* coefs);
+/* ---- JPEG ingest: a baseline JPEG stream in host memory in, a BGR frame out ----------------------------------------------
+ * Integer arithmetic throughout, libjpeg's default decoder step for step (csrc/jpeg_decode.h; the kernels of
+ * csrc/jpeg_decode_kernels.hip and their host twin give the same bytes, and so does Pillow with libjpeg-turbo).
+ *   streams  baseline sequential DCT (SOF0), 8 bits, Huffman, one interleaved scan; 3 components with Y sampled 1x1 (4:4:4), 2x1 (4:2:2)
+ *            or 2x2 (4:2:0) and chroma 1x1, or 1 component (gray: B = G = R = Y).  Any DQT (8-bit steps, ids 0 .. 3), any DHT (ids 0 .. 1
+ *            per class, several tables per marker), DRI optional, APPn and COM skipped.  Height and width 1 .. 65535, a decoded frame
+ *            below 2 GiB.  Refused with MI355_EINVAL and a message naming the stream and the reason, before any work and with every
+ *            destination untouched: SOF1, SOF2 and the other SOFs, 12-bit precision, 4 components, other sampling factors, several
+ *            scans, arithmetic coding, DNL, a missing table, no EOI, a marker other than RSTn inside the scan, RSTn out of sequence.
+ *   entropy  Annex F.2.2 per restart segment, DC predictors 0 at each segment's start; coefficients int16 [blocks][64] in zigzag order,
+ *            blocks in scan order (MCU rows, MCUs, blocks of an MCU: the Y blocks row by row, Cb, Cr), DC absolute (the low 16 bits of
+ *            the running sum).  Decoding terminates inside its buffers for ANY bytes: reads past a segment's end supply zero bits, and
+ *            a 16-bit code that matches nothing (MI355_JPEG_CODE_NOT_FOUND), a run that leaves the block (_RUN_PAST_BLOCK), a segment
+ *            that ends early (_SEGMENT_SHORT) or has bytes left over (_SEGMENT_LONG) end that stream's decoding with status[i] set.
+ *   pixels   coef * step; libjpeg's jpeg_idct_islow (13-bit constants, columns with descale 11, then rows with descale 18, every
+ *            descale (x + (1 << (n - 1))) >> n), sample = clamp(x + 128, 0, 255); "fancy" chroma upsampling -- 4:2:2:
+ *            out[2x] = (3 p[x] + p[x-1] + 1) >> 2, out[2x+1] = (3 p[x] + p[x+1] + 2) >> 2; 4:2:0: s[x] = 3 p[near][x] + p[far][x] with
+ *            far = r - 1 (r + 1) for output row 2r (2r + 1), out[2x] = (3 s[x] + s[x-1] + 8) >> 4, out[2x+1] = (3 s[x] + s[x+1] + 7) >> 4;
+ *            neighbour indices clamped to the chroma plane of ceil(W/2) x ceil(H/2) (4:2:2: x H) samples; a chroma plane of at most 2
+ *            columns is replicated instead; R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+ *            B = Y + ((116130 cb + 32768) >> 16) with cb, cr less 128, clamped to 0 .. 255, stored B, G, R.
+ *   mi355_jpeg_info     parses a stream's header and finds its scan: geometry, subsampling (444, 422, 420; 400 = gray), restart
+ *            interval in MCUs (0: none), segments (restart intervals of the scan; 1 without DRI) and 8 x 8 blocks of the coefficient
+ *            array.  A refused stream gives MI355_EINVAL and its reason in mi355_last_error().
+ *   mi355_jpeg_decode   device >= 0: that GPU; -1: the host twin, which touches no GPU (host destinations only).  streams[i]: HOST
+ *            bytes.  outs[i]: the BGR destination of stream i in host memory or memory of that GPU (on_device = 1), row_stride >= 3 x
+ *            width.  entropy: MI355_JPEG_ENTROPY_GPU -- one GPU lane per restart segment (a stream without DRI is one segment on one
+ *            lane: slow, correct); _HOST -- the twin's segment routine on the calling thread, the coefficients uploaded (128 bytes per
+ *            block), only the idct and colour launches run; _AUTO -- _GPU for a stream with a restart interval, _HOST for one without.
+ *            The call sets streams[i].entropy_used.  All streams of a call, whatever their sizes and layouts, take three launches on
+ *            `stream` (two when no stream's entropy stage runs on the GPU); the stream bytes are staged through pinned memory in one
+ *            copy; the call returns when the launches and copies have finished.  status (n ints, or NULL) receives 0 or an
+ *            MI355_JPEG_* status per stream.  When any is non-zero the call returns MI355_EINVAL naming the first such stream; the
+ *            other streams' frames are complete, a failed stream's host destination is untouched.  launch_ms (or NULL): the launches'
+ *            device time.  At most MI355_RENDER_MAX_FRAMES streams per call.
+ *   mi355_yolo_decode   the same on an engine handle: its device and stream, scratch kept between calls.
+ *   mi355_op_jpeg_decode_coefficients   the entropy stage alone: coefs[i] (host) receives int16 [blocks][64]. */
+#define MI355_JPEG_ENTROPY_AUTO 0
+#define MI355_JPEG_ENTROPY_GPU  1
+#define MI355_JPEG_ENTROPY_HOST 2
+#define MI355_JPEG_CODE_NOT_FOUND 1
+#define MI355_JPEG_RUN_PAST_BLOCK 2
+#define MI355_JPEG_SEGMENT_SHORT  3
+#define MI355_JPEG_SEGMENT_LONG   4
+typedef struct mi355_jpeg_stream {
+    const uint8_t* data;                /* host memory */
+    int64_t length;
+    int entropy_used;                   /* set by the call: MI355_JPEG_ENTROPY_GPU or _HOST */
+    int reserved;
+} mi355_jpeg_stream;
+typedef struct mi355_jpeg_stream_info {
+    int height, width, components;
+    int subsampling;                    /* 444, 422, 420; 400: gray */
+    int restart_interval;               /* MCUs; 0: none */
+    int segments;
+    int64_t blocks;                     /* 8 x 8 blocks of the coefficient array */
+} mi355_jpeg_stream_info;
+int  mi355_jpeg_info(const uint8_t* data, int64_t length, mi355_jpeg_stream_info* info);
+int  mi355_jpeg_decode(int device, mi355_jpeg_stream* streams, int n, int entropy, const mi355_render_out* outs, int* status, void* stream,
+                       float* launch_ms);
+int  mi355_yolo_decode(mi355_yolo* h, mi355_jpeg_stream* streams, int n, int entropy, const mi355_render_out* outs, int* status,
+                       float* launch_ms);
+int  mi355_op_jpeg_decode_coefficients(int device, mi355_jpeg_stream* streams, int n, int entropy, int16_t* const* coefs, int* status);
 /* Depthwise 3x3 conv (stride 1, pad 1) + bias (+SiLU) (+residual) on channel views, fp32, as the engine runs YOLO11's
  * DWConv and Attention.pe (ultralytics nn/modules/conv.py:DWConv, Conv with groups = c).  x[n][h][w][x_cs] holds the input view at
  * channels x_off .. x_off+c-1; residual (or NULL) [n][h][w][res_cs] at res_off; y[n][h][w][y_cs] is read in, its view y_off ..
