@@ -88,7 +88,16 @@ class JpegOut(C.Structure):
 
 class JpegStream(C.Structure):
     """mi355_jpeg_stream: one JPEG stream in host memory; the call reports where its entropy stage ran"""
-    _fields_ = [("data", C.c_void_p), ("length", C.c_int64), ("entropy_used", C.c_int), ("reserved", C.c_int)]
+    _fields_ = [("data", C.c_void_p), ("length", C.c_int64), ("entropy_used", C.c_int), ("entropy", C.c_int)]
+
+
+class JpegSyncState(C.Structure):
+    """mi355_jpeg_sync_state: the true entry state of one subsequence (entropy="sync")"""
+    _fields_ = [("segment", C.c_int), ("byte", C.c_uint32), ("bit", C.c_int), ("j", C.c_int), ("k", C.c_int), ("block", C.c_uint32)]
+
+
+class JpegSyncStats(C.Structure):
+    _fields_ = [("nsub", C.c_int), ("nseq", C.c_int), ("rounds_local", C.c_int), ("rounds_global", C.c_int)]
 
 
 class JpegStreamInfo(C.Structure):
@@ -98,7 +107,7 @@ class JpegStreamInfo(C.Structure):
 
 
 RENDER_WORDS, RENDER_MAX_PRIMS, RENDER_MAX_FRAMES = 8, 16384, 256      # MI355_RENDER_*
-JPEG_ENTROPY = {"auto": 0, "gpu": 1, "host": 2}                         # MI355_JPEG_ENTROPY_*
+JPEG_ENTROPY = {"auto": 0, "gpu": 1, "host": 2, "sync": 3}                       # MI355_JPEG_ENTROPY_*
 JPEG_420, JPEG_444 = 420, 444           # MI355_JPEG_*
 MOTION_MAX_CAMERAS = 64                 # MI355_MOTION_MAX_CAMERAS
 TILE_IOS, TILE_IOU = 0, 1               # MI355_TILE_IOS / MI355_TILE_IOU
@@ -269,6 +278,7 @@ SIGNATURES = {
     "mi355_jpeg_decode": (C.c_int, [C.c_int, _P(JpegStream), C.c_int, C.c_int, _P(RenderOut), _i32p, C.c_void_p, _f32p]),
     "mi355_yolo_decode": (C.c_int, [C.c_void_p, _P(JpegStream), C.c_int, C.c_int, _P(RenderOut), _i32p, _f32p]),
     "mi355_op_jpeg_decode_coefficients": (C.c_int, [C.c_int, _P(JpegStream), C.c_int, C.c_int, _P(C.c_void_p), _i32p]),
+    "mi355_op_jpeg_sync": (C.c_int, [C.c_int, _P(JpegStream), C.c_int, C.c_int, C.c_void_p, _i32p, _P(JpegSyncState), C.c_int, _P(JpegSyncStats)]),
     "mi355_op_nms": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,
                                C.c_int, C.c_int, C.c_void_p, C.c_int, _i32p]),
     "mi355_op_nms_ex": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _i32p,

@@ -71,8 +71,8 @@ int jpeg_run(JpegCtx& ctx, int device, const mi355_render_frame* frames, int n, 
 void jpeg_ctx_free(JpegCtx& ctx);
 
 // jpeg_decode_kernels.hip: the grow-only scratch of JPEG decode calls -- one device buffer [descriptors | Huffman tables |
-// status | per frame: segment offsets and scan bytes, or host-decoded coefficients || coefficients of the lane frames | planes | frames
-// bound for the host], the pinned image of its first part and the pinned landing areas of the frames and the status words.  The calls
+// status | per frame: segment offsets (sync: segment and sequence tables) and scan bytes, or host-decoded coefficients || coefficients of
+// the lane and sync frames | a sync frame's states, counts and block indices | planes | frames bound for the host], the pinned image of its first part and the pinned landing areas of the frames and the status words.  The calls
 // themselves are declared in jpeg_decode.h.
 struct JpegDecCtx { Buf d_work; Buf h_img{true}, h_out{true}, h_stat{true}; hipEvent_t ev0 = nullptr, ev1 = nullptr; };
 void jpeg_dec_ctx_free(JpegDecCtx& ctx);

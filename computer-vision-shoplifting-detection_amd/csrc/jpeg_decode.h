@@ -50,6 +50,45 @@ struct JpegHuff {
     uint8_t vals[256];
 };
 
+// entropy = sync (jpeg_sync.h): a decoder state, the segment and sequence tables, and what a sync frame's launches work on
+constexpr int kJpegSyncSubBytes = 128;          // S of product calls (measured against 64 and 256: DESIGN.md 3.21)
+constexpr int kJpegSyncSeqSubs = 256;           // Q: the lanes of a workgroup
+struct JpegSyncOpts {                           // mi355_op_jpeg_sync's S and Q, and where its states and stats go
+    int S = kJpegSyncSubBytes, Q = kJpegSyncSeqSubs;
+    mi355_jpeg_sync_state* states = nullptr;
+    mi355_jpeg_sync_stats* stats = nullptr;
+};
+struct JpegSyncState {
+    uint32_t byte, meta;                        // meta: bit | j << 3 | k << 6
+};
+MI355_HD bool jpeg_sync_same(JpegSyncState a, JpegSyncState b) { return a.byte == b.byte && a.meta == b.meta; }
+
+struct JpegSyncSeg {
+    uint32_t begin, len;                        // the segment's bytes within the scan
+    uint32_t blk0, nblk;                        // its blocks
+    uint32_t sub0, nsub;                        // its subsequences (of the frame's), at least one
+    uint32_t seq0, nseq;
+};
+struct JpegSyncSeq {
+    uint32_t seg;
+    uint32_t sub0, nsub;                        // of the frame's subsequences
+    uint32_t lsub0;                             // sub0's index within its segment
+};
+// what a sync frame's launches work on: tables from the host, the rest in the work buffer
+struct JpegSync {
+    int S, Q;
+    uint32_t nsub, nseq;
+    const JpegSyncSeg* segs;
+    const JpegSyncSeq* seqs;
+    JpegSyncState* X;                           // [nsub] exit states
+    uint32_t* E;                                // [nsub] blocks completed
+    uint32_t* B;                                // [nsub] block in progress at the entry
+    uint32_t* seq_blk;                          // [nseq] B of a sequence's first subsequence
+    JpegSyncState* entry;                       // [nseq] global rounds: the entry read before anything is written
+    uint32_t* mark;                             // [2][nseq]
+    uint32_t* stats;                            // rounds_local, rounds_global (zeroed with the coefficients)
+};
+
 // One frame of a call: geometry and tables from the parser, then the GPU path's pointers
 struct JpegDecFrame {
     int H, W, ncomp, hs, vs;                    // Y's sampling factors: 1x1, 2x1, 2x2 (gray: 1x1)
@@ -57,7 +96,7 @@ struct JpegDecFrame {
     int ri, nseg, seg_mcus;                     // restart interval (0: none), segments, MCUs per segment (the last may hold fewer)
     int cw, ch;                                 // the chroma planes' real extent: ceil(W / hs) x ceil(H / vs)
     int pitch;                                  // of `out`
-    int lanes;                                  // GPU path: 1 when the frame's entropy stage runs on the GPU's lanes
+    int lanes;                                  // GPU path: 1 when the frame's entropy stage runs on the GPU's lanes, 2: entropy = sync
     uint8_t zigzag[64];                         // GPU path: kJpegZigzag, which device code cannot index
     uint8_t q[3][64];                           // per component: the quantisation steps in zigzag order
     uint8_t dc_tab[3], ac_tab[3];               // per component: index into huff[] (DC tables 0 .. 1, AC tables 2 .. 3)
@@ -68,6 +107,7 @@ struct JpegDecFrame {
     int* status;
     uint8_t* plane[3]; int pw[3], ph[3];        // component planes, padded to whole MCUs
     uint8_t* out;                               // BGR [H][pitch]
+    JpegSync sy;                                // entropy = sync
 };
 MI355_HD long long jpeg_dec_blocks(const JpegDecFrame& f) { return (long long)f.mcus_x * f.mcus_y * f.bpm; }
 
@@ -106,8 +146,8 @@ struct JpegBits {
 };
 
 // one symbol: -1 when the next 16 bits match no code.  The window holds at least 32 bits behind a fill.
-template <class Fetch>
-MI355_HD int jpeg_dec_symbol(JpegBits<Fetch>& b, const JpegHuff& h) {
+template <class Bits>
+MI355_HD int jpeg_dec_symbol(Bits& b, const JpegHuff& h) {
     const unsigned e = h.look[b.peek(8)];
     if (e) { b.drop((int)(e >> 8)); return (int)(e & 0xFFu); }
     int len = 9;
@@ -118,8 +158,8 @@ MI355_HD int jpeg_dec_symbol(JpegBits<Fetch>& b, const JpegHuff& h) {
     return h.vals[(code + h.valoff[len]) & 0xFF];
 }
 // s bits, 0 <= s <= 15, as the signed value they stand for (F.2.2.1 EXTEND)
-template <class Fetch>
-MI355_HD int jpeg_dec_receive(JpegBits<Fetch>& b, int s) {
+template <class Bits>
+MI355_HD int jpeg_dec_receive(Bits& b, int s) {
     if (!s) return 0;
     const int v = (int)b.peek(s);
     b.drop(s);
@@ -464,10 +504,10 @@ inline void jpeg_dec_pixels_host(const JpegParsed& P, const int16_t* coef, uint8
 // ---- one call (jpeg_decode_host.cpp; the GPU half is jpeg_decode_kernels.hip's) -------------------------------------------------------------
 struct JpegDecCtx;                              // the GPU path's grow-only scratch (engine_internal.h); NULL: scratch of the call's own
 // parses and checks everything, then runs the twin (device -1) or the GPU.  outs: BGR destinations, or NULL with coefs: the entropy
-// stage alone into host int16 [blocks][64]
+// stage alone into host int16 [blocks][64].  lanes[i]: 0 host, 1 a lane per segment, 2 sync.  sync: the hook's, NULL for product calls
 int jpeg_dec_call(JpegDecCtx* ctx, int device, mi355_jpeg_stream* streams, int n, int entropy, const mi355_render_out* outs,
-                  int16_t* const* coefs, int* status, void* stream, float* launch_ms);
+                  int16_t* const* coefs, int* status, void* stream, float* launch_ms, const JpegSyncOpts* sync = nullptr);
 int jpeg_dec_run_gpu(JpegDecCtx* ctx, int device, std::vector<JpegParsed>& P, const mi355_jpeg_stream* streams, int n, const int* lanes,
-                     const mi355_render_out* outs, int16_t* const* coefs, int* status, void* stream, float* launch_ms);
+                     const mi355_render_out* outs, int16_t* const* coefs, int* status, void* stream, float* launch_ms, const JpegSyncOpts& sync);
 
 }  // namespace mi355

@@ -8,10 +8,14 @@
 //            then the row pass, one 8-vector each, and every lane stores one row of 8 samples to its component's plane.
 //   colour   one lane per four pixels of a row: chroma upsampling (the triangle filter reads its neighbours across MCU borders from the
 //            planes), colour conversion, three 32-bit stores where the row is aligned.
+// entropy = sync (jpeg_sync.h) decodes a restart segment with many lanes and puts four launches in front of idct and colour, whatever the
+// number of frames: local rounds (a workgroup per sequence: round 0 and the re-walks, states in LDS), global rounds + block index (a
+// workgroup per frame), write pass (a lane per subsequence; the block indices of a sequence by a scan in LDS), DC pass (a workgroup per
+// frame and component).  No workgroup waits for another one and nothing is read back between the launches.
 // entropy = host replaces the first launch by the twin's segment routine on the calling thread; the coefficients travel with the
 // descriptors.  The rules themselves are jpeg_decode.h's, shared with the host twin (device = -1).
 #include "engine_internal.h"
-#include "jpeg_decode.h"
+#include "jpeg_sync.h"
 
 namespace mi355 {
 namespace {
@@ -23,7 +27,7 @@ constexpr int kDecBlkStride = 72, kDecRowStride = 9;      // LDS layout of a sta
 __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const JpegDecFrame* __restrict__ frames) {
     const JpegDecFrame& f = frames[blockIdx.y];
     const int s0 = (int)blockIdx.x * 64;
-    if (!f.lanes || s0 >= f.nseg) return;                              // block-uniform
+    if (f.lanes != 1 || s0 >= f.nseg) return;                              // block-uniform
     const int t = (int)threadIdx.x;
     __shared__ JpegHuff s_h[4];
     __shared__ uint32_t s_seg[128];
@@ -122,14 +126,202 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const JpegDecFrame* __
     }
 }
 
+// ---- entropy = sync (jpeg_sync.h) ----------------------------------------------------------------------------------------------------------
+__device__ void jpeg_stage_huff(const JpegDecFrame& f, JpegHuff* s_h, int t) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(f.huff);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(s_h);
+    for (int i = t; i < (int)(4 * sizeof(JpegHuff) / 4); i += kDecLanes) dst[i] = src[i];
+}
+
+// inclusive segmented sum over the 256 lanes: fl starts a segment at its lane.  Every lane of the block calls it.
+__device__ uint32_t jpeg_seg_scan(uint32_t v, uint32_t fl, uint32_t* s_v, uint32_t* s_f, int t) {
+    s_v[t] = v; s_f[t] = fl;
+    __syncthreads();
+    for (int d = 1; d < kDecLanes; d <<= 1) {
+        const uint32_t pv = t >= d ? s_v[t - d] : 0u, pf = t >= d ? s_f[t - d] : 1u;
+        __syncthreads();
+        if (!fl) { v += pv; fl = pf; }
+        s_v[t] = v; s_f[t] = fl;
+        __syncthreads();
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(256) void jpeg_sync_local_kernel(const JpegDecFrame* __restrict__ frames) {
+    const JpegDecFrame& f = frames[blockIdx.y];
+    if (f.lanes != 2 || blockIdx.x >= f.sy.nseq) return;                // block-uniform
+    const int t = (int)threadIdx.x;
+    __shared__ JpegHuff s_h[4];
+    __shared__ JpegSyncState s_x[kDecLanes];
+    __shared__ uint32_t s_chg[2][kDecLanes];
+    jpeg_stage_huff(f, s_h, t);
+    const JpegSyncSeq sq = f.sy.seqs[blockIdx.x];
+    const JpegSyncSeg sg = f.sy.segs[sq.seg];
+    const int S = f.sy.S, Q = f.sy.Q;
+    const bool live = (uint32_t)t < sq.nsub;
+    const uint32_t li = sq.lsub0 + (uint32_t)t, end = live ? jpeg_sync_end(li, S, sg.len) : 0u;
+    JpegFetchWords fetch{reinterpret_cast<const uint32_t*>(f.scan)};
+    JpegSyncState x{0u, 0u};
+    uint32_t e = 0;
+    __syncthreads();
+    if (live) x = jpeg_sync_walk(f, s_h, fetch, sg.begin, sg.len, end, jpeg_sync_guess(fetch, sg.begin, li, S), e, nullptr, (JpegPosBits<JpegFetchWords>*)nullptr);
+    s_x[t] = x; s_chg[0][t] = live;
+    __syncthreads();
+    int cur = 0, rounds = 0;
+    for (int r = 1; r < Q; ++r) {                                       // at most Q rounds with round 0
+        const bool redo = live && t > 0 && s_chg[cur][t - 1];
+        const JpegSyncState in = redo ? s_x[t - 1] : x;
+        __syncthreads();                                                // every read of the round before any write
+        uint32_t c = 0;
+        if (redo) {
+            const JpegSyncState nx = jpeg_sync_walk(f, s_h, fetch, sg.begin, sg.len, end, in, e, nullptr, (JpegPosBits<JpegFetchWords>*)nullptr);
+            c = !jpeg_sync_same(nx, x);
+            x = nx; s_x[t] = x;
+        }
+        s_chg[cur ^ 1][t] = c;
+        if (!__syncthreads_or((int)c)) break;
+        rounds = r; cur ^= 1;
+    }
+    if (live) { f.sy.X[sq.sub0 + t] = x; f.sy.E[sq.sub0 + t] = e; }
+    if (t == 0 && rounds) atomicMax(&f.sy.stats[0], (uint32_t)rounds);
+}
+
+__global__ __launch_bounds__(256) void jpeg_sync_global_kernel(const JpegDecFrame* __restrict__ frames) {
+    const JpegDecFrame& f = frames[blockIdx.x];
+    if (f.lanes != 2) return;                                           // block-uniform
+    const int t = (int)threadIdx.x;
+    __shared__ JpegHuff s_h[4];
+    __shared__ uint32_t s_v[kDecLanes], s_f[kDecLanes], s_carry;
+    jpeg_stage_huff(f, s_h, t);
+    const uint32_t nseq = f.sy.nseq;
+    const int S = f.sy.S;
+    const JpegSyncSeq* seqs = f.sy.seqs;
+    JpegSyncState* X = f.sy.X;
+    uint32_t* E = f.sy.E;
+    uint32_t* mk = f.sy.mark;
+    uint32_t* nm = f.sy.mark + nseq;
+    JpegFetchWords fetch{reinterpret_cast<const uint32_t*>(f.scan)};
+    int some = 0;
+    for (uint32_t q = (uint32_t)t; q < nseq; q += kDecLanes) {
+        const uint32_t m = seqs[q].lsub0 != 0u;                          // all but a segment's first: walked from the guess so far
+        mk[q] = m; nm[q] = 0u; some |= (int)m;
+    }
+    int any = __syncthreads_or(some);
+    uint32_t rounds = 0;
+    for (uint32_t r = 1; r <= nseq && any; ++r) {                       // at most as many rounds as the frame has sequences
+        for (uint32_t q = (uint32_t)t; q < nseq; q += kDecLanes)
+            if (mk[q]) f.sy.entry[q] = X[seqs[q].sub0 - 1];
+        __syncthreads();                                                // every read of the round before any write
+        int wrote = 0, next = 0;
+        for (uint32_t q = (uint32_t)t; q < nseq; q += kDecLanes) {
+            if (!mk[q]) continue;
+            mk[q] = 0u;
+            const JpegSyncSeq sq = seqs[q];
+            const JpegSyncSeg sg = f.sy.segs[sq.seg];
+            JpegSyncState in = f.sy.entry[q];
+            for (uint32_t u = 0; u < sq.nsub; ++u) {
+                const uint32_t i = sq.sub0 + u;
+                uint32_t e;
+                const JpegSyncState x = jpeg_sync_walk(f, s_h, fetch, sg.begin, sg.len, jpeg_sync_end(sq.lsub0 + u, S, sg.len), in, e, nullptr,
+                                                       (JpegPosBits<JpegFetchWords>*)nullptr);
+                E[i] = e;
+                if (jpeg_sync_same(x, X[i])) break;
+                X[i] = x; in = x; wrote = 1;
+                if (u + 1 == sq.nsub && q + 1 < nseq && seqs[q + 1].seg == sq.seg) { nm[q + 1] = 1u; next = 1; }
+            }
+        }
+        any = __syncthreads_or(next);
+        if (__syncthreads_or(wrote)) rounds = r;
+        uint32_t* sw = mk; mk = nm; nm = sw;
+    }
+    if (t == 0) f.sy.stats[1] = rounds;
+    // the block in progress at every sequence's entry: the segment's first block + the blocks its earlier sequences completed
+    if (t == 0) s_carry = 0u;
+    __syncthreads();
+    for (uint32_t base = 0; base < nseq; base += kDecLanes) {
+        const uint32_t q = base + (uint32_t)t;
+        uint32_t tot = 0, fl = 1u, blk0 = 0;
+        if (q < nseq) {
+            const JpegSyncSeq sq = seqs[q];
+            for (uint32_t u = 0; u < sq.nsub; ++u) tot += E[sq.sub0 + u];
+            fl = sq.lsub0 == 0u;
+            blk0 = f.sy.segs[sq.seg].blk0;
+        }
+        uint32_t v = tot;
+        if (t == 0 && !fl) { v += s_carry; fl = 1u; }
+        const uint32_t incl = jpeg_seg_scan(v, fl, s_v, s_f, t);
+        if (q < nseq) f.sy.seq_blk[q] = blk0 + incl - tot;
+        if (t == kDecLanes - 1) s_carry = incl;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void jpeg_sync_write_kernel(const JpegDecFrame* __restrict__ frames) {
+    const JpegDecFrame& f = frames[blockIdx.y];
+    if (f.lanes != 2 || blockIdx.x >= f.sy.nseq) return;                // block-uniform
+    const int t = (int)threadIdx.x;
+    __shared__ JpegHuff s_h[4];
+    __shared__ uint32_t s_v[kDecLanes], s_f[kDecLanes];
+    jpeg_stage_huff(f, s_h, t);
+    const JpegSyncSeq sq = f.sy.seqs[blockIdx.x];
+    const JpegSyncSeg sg = f.sy.segs[sq.seg];
+    const bool live = (uint32_t)t < sq.nsub;
+    const uint32_t g = sq.sub0 + (uint32_t)t, e = live ? f.sy.E[g] : 0u;
+    const uint32_t B = f.sy.seq_blk[blockIdx.x] + jpeg_seg_scan(e, t == 0, s_v, s_f, t) - e;     // the scan's barriers also publish s_h
+    if (!live) return;
+    f.sy.B[g] = B;
+    JpegFetchWords fetch{reinterpret_cast<const uint32_t*>(f.scan)};
+    const JpegSyncState in = sq.lsub0 + (uint32_t)t ? f.sy.X[g - 1] : JpegSyncState{0u, 0u};
+    const uint32_t key = jpeg_sync_write_lane(f, s_h, fetch, sg, sq, (uint32_t)t, in, B);
+    if (key != 0xFFFFFFFFu) atomicMin(reinterpret_cast<unsigned int*>(f.status), key);
+}
+
+constexpr int kSyncDcRun = 8;                                           // DC values per lane and chunk
+__global__ __launch_bounds__(256) void jpeg_sync_dc_kernel(const JpegDecFrame* __restrict__ frames) {
+    const JpegDecFrame& f = frames[blockIdx.y];
+    const int c = (int)blockIdx.x;
+    if (f.lanes != 2 || c >= f.ncomp) return;                           // block-uniform
+    const int t = (int)threadIdx.x;
+    __shared__ uint32_t s_v[kDecLanes], s_f[kDecLanes], s_carry;
+    const long long ne = jpeg_sync_dc_count(f, c);
+    const long long nblk = jpeg_dec_blocks(f);
+    if (t == 0) s_carry = 0u;
+    __syncthreads();
+    for (long long base = 0; base < ne; base += (long long)kDecLanes * kSyncDcRun) {
+        const long long e0 = base + (long long)t * kSyncDcRun;
+        uint32_t val[kSyncDcRun], blk[kSyncDcRun];
+        uint32_t run = t == 0 ? s_carry : 0u, fl = 0u;
+        int head = kSyncDcRun;                                          // the values in front of the run's first segment start take the prefix
+#pragma unroll
+        for (int i = 0; i < kSyncDcRun; ++i) {
+            val[i] = 0u; blk[i] = 0xFFFFFFFFu;
+            if (e0 + i >= ne) continue;
+            bool first;
+            const long long b = jpeg_sync_dc_block(f, c, e0 + i, first);
+            if (b >= nblk) continue;
+            if (first) { run = 0u; if (!fl) head = i; fl = 1u; }
+            run += (uint32_t)(int)f.coef[b * 64];
+            val[i] = run; blk[i] = (uint32_t)b;
+        }
+        const uint32_t incl = jpeg_seg_scan(run, fl, s_v, s_f, t);
+        const uint32_t prefix = t ? s_v[t - 1] : 0u;
+#pragma unroll
+        for (int i = 0; i < kSyncDcRun; ++i)
+            if (blk[i] != 0xFFFFFFFFu) f.coef[(size_t)blk[i] * 64] = (int16_t)(uint16_t)(val[i] + (i < head ? prefix : 0u));
+        __syncthreads();                                                // s_v read before the next chunk's scan writes it
+        if (t == kDecLanes - 1) s_carry = incl;
+        __syncthreads();
+    }
+}
+
 constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
 // The GPU half of one call; the streams are parsed and every argument checked (jpeg_dec_call).  lanes[i]: frame i's entropy stage runs
-// on the GPU.  outs (BGR) or coefs (the entropy stage alone, host int16) is given.
+// on the GPU -- 1: a lane per segment, 2: sync.  outs (BGR) or coefs (the entropy stage alone, host int16) is given.
 int jpeg_dec_run_gpu(JpegDecCtx* ctxp, int device, std::vector<JpegParsed>& P, const mi355_jpeg_stream* streams, int n, const int* lanes,
-                     const mi355_render_out* outs, int16_t* const* coefs, int* status, void* stream, float* launch_ms) {
+                     const mi355_render_out* outs, int16_t* const* coefs, int* status, void* stream, float* launch_ms, const JpegSyncOpts& so) {
     hipStream_t st = (hipStream_t)stream;
     JpegDecCtx local;
     JpegDecCtx& ctx = ctxp ? *ctxp : local;
@@ -139,22 +331,36 @@ int jpeg_dec_run_gpu(JpegDecCtx* ctxp, int device, std::vector<JpegParsed>& P, c
     if (device >= ndev) return fail(MI355_EINVAL, "jpeg decode: device out of range");
     HIPCHK(hipSetDevice(device));
     if (launch_ms) *launch_ms = 0.f;
-    // the image, built in pinned memory and uploaded in one copy: [descriptors | Huffman tables | status | per frame: segment offsets,
-    // scan bytes (lanes) or coefficients (host entropy)]; behind it on the device: [coefficients of the lane frames | planes | host outputs]
+    // the image, built in pinned memory and uploaded in one copy: [descriptors | Huffman tables | status | per frame: segment offsets (sync:
+    // the segment and sequence tables), scan bytes (lanes, sync) or coefficients (host entropy)]; behind it on the device: [coefficients
+    // of the lane and sync frames, a sync frame's round counts | a sync frame's states, counts and block indices | planes | host outputs]
     const size_t huff_off = al256((size_t)n * sizeof(JpegDecFrame)), stat_off = al256(huff_off + (size_t)n * 4 * sizeof(JpegHuff));
     size_t at = al256(stat_off + (size_t)n * 4);
     std::vector<size_t> seg_off((size_t)n), data_off((size_t)n), coef_off((size_t)n), plane_off((size_t)n * 3, 0), out_off((size_t)n, 0);
+    std::vector<JpegSyncTables> T((size_t)n);
+    std::vector<size_t> stats_off((size_t)n, 0), sync_off((size_t)n, 0);
     for (int i = 0; i < n; ++i) {
         const JpegDecFrame& f = P[i].f;
+        if (lanes[i] == 2) jpeg_sync_tables(P[i], so.S, so.Q, T[i]);
         if (lanes[i]) {
-            seg_off[i] = at; at = al256(at + (size_t)f.nseg * 8);
+            seg_off[i] = at; at = al256(at + (lanes[i] == 2 ? T[i].segs.size() * sizeof(JpegSyncSeg) + T[i].seqs.size() * sizeof(JpegSyncSeq) : (size_t)f.nseg * 8));
             data_off[i] = at; at = al256(at + (size_t)(P[i].scan_end - P[i].scan_begin) + 8);
         } else { coef_off[i] = at; at = al256(at + (size_t)jpeg_dec_blocks(f) * 128); }
     }
     const size_t img_bytes = at, zero_off = at;
     for (int i = 0; i < n; ++i)
-        if (lanes[i]) { coef_off[i] = at; at = al256(at + (size_t)jpeg_dec_blocks(P[i].f) * 128); }
+        if (lanes[i]) {
+            coef_off[i] = at; at = al256(at + (size_t)jpeg_dec_blocks(P[i].f) * 128);
+            if (lanes[i] == 2) { stats_off[i] = at; at = al256(at + 16); }
+        }
     const size_t zero_bytes = at - zero_off;
+    long long most_seq = 0;
+    for (int i = 0; i < n; ++i)
+        if (lanes[i] == 2) {                                             // X | entry | E | B | seq_blk | mark
+            const size_t ns = T[i].nsub, nq = T[i].seqs.size();
+            sync_off[i] = at; at = al256(at + ns * 8 + nq * 8 + ns * 4 + ns * 4 + nq * 4 + nq * 8);
+            most_seq = std::max(most_seq, (long long)nq);
+        }
     size_t back_bytes = 0;
     std::vector<size_t> back((size_t)n, 0);
     long long most_seg = 0, most_grp = 1, most_quad = 1;
@@ -167,7 +373,7 @@ int jpeg_dec_run_gpu(JpegDecCtx* ctxp, int device, std::vector<JpegParsed>& P, c
             }
             if (!outs[i].on_device) { out_off[i] = at; at = al256(at + (size_t)f.H * f.W * 3); back[i] = back_bytes; back_bytes = al256(back_bytes + (size_t)f.H * f.W * 3); }
         }
-        if (lanes[i]) most_seg = std::max(most_seg, (long long)f.nseg);
+        if (lanes[i] == 1) most_seg = std::max(most_seg, (long long)f.nseg);
         most_grp = std::max(most_grp, (jpeg_dec_blocks(f) + kDecGroupBlocks - 1) / kDecGroupBlocks);
         most_quad = std::max(most_quad, ((long long)((f.W + 3) / 4) * f.H + kDecLanes - 1) / kDecLanes);
     }
@@ -190,6 +396,17 @@ int jpeg_dec_run_gpu(JpegDecCtx* ctxp, int device, std::vector<JpegParsed>& P, c
         if (lanes[i]) {
             const size_t nb = (size_t)(P[i].scan_end - P[i].scan_begin);
             f.seg = (const uint32_t*)(base + seg_off[i]); f.scan = base + data_off[i];
+            if (lanes[i] == 2) {
+                const size_t ns = T[i].nsub, nq = T[i].seqs.size(), sb = T[i].segs.size() * sizeof(JpegSyncSeg);
+                f.seg = nullptr;
+                std::memcpy(img + seg_off[i], T[i].segs.data(), sb);
+                std::memcpy(img + seg_off[i] + sb, T[i].seqs.data(), nq * sizeof(JpegSyncSeq));
+                uint8_t* w = base + sync_off[i];
+                f.sy = JpegSync{so.S, so.Q, (uint32_t)ns, (uint32_t)nq, (const JpegSyncSeg*)(base + seg_off[i]), (const JpegSyncSeq*)(base + seg_off[i] + sb),
+                                (JpegSyncState*)w, (uint32_t*)(w + ns * 8 + nq * 8), (uint32_t*)(w + ns * 12 + nq * 8), (uint32_t*)(w + ns * 16 + nq * 8),
+                                (JpegSyncState*)(w + ns * 8), (uint32_t*)(w + ns * 16 + nq * 12), (uint32_t*)(base + stats_off[i])};
+                ((uint32_t*)(img + stat_off))[i] = 0xFFFFFFFFu;          // the status key: a minimum (jpeg_sync.h)
+            } else
             std::memcpy(img + seg_off[i], P[i].seg.data(), (size_t)f.nseg * 8);
             std::memcpy(img + data_off[i], streams[i].data + P[i].scan_begin, nb);
             std::memset(img + data_off[i] + nb, 0, 8);
@@ -209,9 +426,19 @@ int jpeg_dec_run_gpu(JpegDecCtx* ctxp, int device, std::vector<JpegParsed>& P, c
     if (launch_ms) HIPCHK(hipEventRecord(ctx.ev0, st));
     const JpegDecFrame* dd = (const JpegDecFrame*)base;
     auto launched = [&]() -> const char* { const hipError_t e = hipGetLastError(); return e != hipSuccess ? hipGetErrorString(e) : nullptr; };
+    if (most_seg > 0 || most_seq > 0) HIPCHK(hipMemsetAsync(base + zero_off, 0, zero_bytes, st));
     if (most_seg > 0) {
-        HIPCHK(hipMemsetAsync(base + zero_off, 0, zero_bytes, st));
         hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((most_seg + 63) / 64), (unsigned)n), dim3(64), 0, st, dd);
+        KCHK(launched());
+    }
+    if (most_seq > 0) {                                                  // entropy = sync: four launches, whatever the number of frames
+        hipLaunchKernelGGL(jpeg_sync_local_kernel, dim3((unsigned)most_seq, (unsigned)n), dim3(kDecLanes), 0, st, dd);
+        KCHK(launched());
+        hipLaunchKernelGGL(jpeg_sync_global_kernel, dim3((unsigned)n), dim3(kDecLanes), 0, st, dd);
+        KCHK(launched());
+        hipLaunchKernelGGL(jpeg_sync_write_kernel, dim3((unsigned)most_seq, (unsigned)n), dim3(kDecLanes), 0, st, dd);
+        KCHK(launched());
+        hipLaunchKernelGGL(jpeg_sync_dc_kernel, dim3(3, (unsigned)n), dim3(kDecLanes), 0, st, dd);
         KCHK(launched());
     }
     if (outs) {
@@ -229,10 +456,29 @@ int jpeg_dec_run_gpu(JpegDecCtx* ctxp, int device, std::vector<JpegParsed>& P, c
     if (outs)
         for (int i = 0; i < n; ++i)
             if (!outs[i].on_device) HIPCHK(hipMemcpyAsync(ctx.h_out.p + back[i], base + out_off[i], (size_t)P[i].f.H * P[i].f.W * 3, hipMemcpyDeviceToHost, st));
+    std::vector<JpegSyncState> hx;                                       // the hook: exit states, block indices and round counts of its one frame
+    std::vector<uint32_t> hb;
+    uint32_t hstats[4] = {0u, 0u, 0u, 0u};
+    if ((so.states || so.stats) && n == 1 && lanes[0] == 2) {
+        hx.resize(T[0].nsub); hb.resize(T[0].nsub);
+        HIPCHK(hipMemcpyAsync(hx.data(), P[0].f.sy.X, hx.size() * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hb.data(), P[0].f.sy.B, hb.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hstats, P[0].f.sy.stats, 16, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipStreamSynchronize(st));
+    if (!hx.empty()) {
+        if (so.stats) *so.stats = mi355_jpeg_sync_stats{(int)T[0].nsub, (int)T[0].seqs.size(), (int)hstats[0], (int)hstats[1]};
+        if (so.states)
+            for (const JpegSyncSeg& g : T[0].segs)
+                for (uint32_t u = 0; u < g.nsub; ++u) {
+                    const uint32_t i = g.sub0 + u;
+                    const JpegSyncState e = u ? hx[i - 1] : JpegSyncState{0u, 0u};
+                    so.states[i] = mi355_jpeg_sync_state{(int)(&g - T[0].segs.data()), e.byte, (int)(e.meta & 7u), (int)((e.meta >> 3) & 7u), (int)(e.meta >> 6), hb[i]};
+                }
+    }
     if (launch_ms) HIPCHK(hipEventElapsedTime(launch_ms, ctx.ev0, ctx.ev1));
     for (int i = 0; i < n; ++i) {
-        const int s = lanes[i] ? h_stat[i] : host_status[i];
+        const int s = lanes[i] == 2 ? ((uint32_t)h_stat[i] == 0xFFFFFFFFu ? 0 : h_stat[i] & 7) : lanes[i] ? h_stat[i] : host_status[i];
         if (status) status[i] = s;
         if (outs && !outs[i].on_device && !s) {
             const JpegDecFrame& f = P[i].f;

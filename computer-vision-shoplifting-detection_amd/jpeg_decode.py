@@ -22,11 +22,17 @@ class JPEGFrame:
     (progressive, 12-bit, CMYK, other sampling factors, several scans, arithmetic coding, a missing table or EOI ...) raises
     ``ValueError`` with the reason here, not at the call that would decode it.  ``shape`` is (H, W), ``subsampling`` "444", "422", "420"
     or "gray", ``restart_interval`` the DRI value in MCUs (0: none), ``segments`` the number of restart segments of the scan (what the
-    GPU's lanes decode side by side; 1 without restart markers) and ``blocks`` the number of 8 x 8 coefficient blocks."""
+    GPU's lanes decode side by side; 1 without restart markers) and ``blocks`` the number of 8 x 8 coefficient blocks.  ``entropy``:
+    this frame's own request for where its Huffman decoding runs -- "auto", "gpu", "host" or "sync" (``ops.jpeg_decode``) -- which goes
+    before the decoding call's; ``None``: the call decides.  It travels with the frame through predict, track and track_cameras."""
 
-    def __init__(self, data):
+    def __init__(self, data, entropy=None):
         if isinstance(data, JPEGFrame):
+            entropy = data.entropy if entropy is None else entropy
             data = data.data
+        if entropy is not None and entropy not in _lib.JPEG_ENTROPY:
+            raise ValueError(f"entropy must be None, 'auto', 'gpu', 'host' or 'sync', got {entropy!r}")
+        self.entropy = entropy
         if isinstance(data, (str, os.PathLike)):
             raise TypeError("JPEGFrame takes the stream's bytes; JPEGFrame.open(path) reads a file")
         self.data = bytes(data)
@@ -41,16 +47,16 @@ class JPEGFrame:
         self.blocks = int(info.blocks)
 
     @classmethod
-    def open(cls, path) -> "JPEGFrame":
+    def open(cls, path, entropy=None) -> "JPEGFrame":
         with open(path, "rb") as f:
-            return cls(f.read())
+            return cls(f.read(), entropy=entropy)
 
     def __len__(self) -> int:
         return len(self.data)
 
     def struct(self) -> _lib.JpegStream:
         """mi355_jpeg_stream of this frame; the frame must stay alive while the engine reads it."""
-        return _lib.JpegStream(self._buf.ctypes.data, len(self.data), 0, 0)
+        return _lib.JpegStream(self._buf.ctypes.data, len(self.data), 0, _lib.JPEG_ENTROPY[self.entropy] if self.entropy and self.entropy != "auto" else 0)
 
     def to_bgr(self, device: int = 0) -> np.ndarray:
         """The BGR frame [H, W, 3] the engine makes of this one (``device=-1``: the kernels' host twin, no GPU)."""

@@ -720,15 +720,17 @@ def jpeg_decode(streams, device: int = 0, entropy: str = "auto", out=None, as_te
     without restart markers).  One call, three launches, whatever the number of streams; only the compressed bytes go up.
     ``entropy``: "gpu" -- one GPU lane per restart segment (a stream without restart markers is one segment on one lane: slow, correct);
     "host" -- Huffman decoding on the calling thread, coefficients uploaded; "auto" -- "gpu" for a stream with a restart interval,
-    "host" for one without.  ``as_tensor=True``: CUDA tensors on ``device`` that never visit the host.  ``out``: arrays (or, on a GPU,
+    "host" for one without; "sync" -- many GPU lanes per restart segment, the self-synchronising parallel Huffman decoder of
+    csrc/jpeg_sync.h, meant for streams without restart markers (opt-in: "auto" never chooses it; four more launches).  A
+    ``JPEGFrame(data, entropy=...)`` carries its own request, which goes before the call's.  ``as_tensor=True``: CUDA tensors on ``device`` that never visit the host.  ``out``: arrays (or, on a GPU,
     CUDA tensors) [H, W, 3] uint8 to write into, last strides (3, 1), any row pitch.  ``device=-1`` runs the host twin and touches no
     GPU.  ``handle``: an engine handle -- the call runs on its stream with its scratch (``mi355_yolo_decode``).  ``timing``: a list that
-    receives ``{"ms": the launches' device time, "entropy": ["gpu" | "host" per stream]}``.  A stream whose entropy-coded data is
+    receives ``{"ms": the launches' device time, "entropy": ["gpu" | "host" | "sync" per stream]}``.  A stream whose entropy-coded data is
     corrupt raises ``ValueError`` naming its index; the other streams' frames (in ``out``) are complete."""
     import torch
     device = int(device)
     if entropy not in _lib.JPEG_ENTROPY:
-        raise ValueError(f"entropy must be 'auto', 'gpu' or 'host', got {entropy!r}")
+        raise ValueError(f"entropy must be 'auto', 'gpu', 'host' or 'sync', got {entropy!r}")
     if as_tensor and device < 0:
         raise ValueError("as_tensor=True needs a GPU: the host twin (device=-1) returns numpy arrays")
     fr, single = _jpeg_streams(streams)
@@ -767,7 +769,7 @@ def jpeg_decode(streams, device: int = 0, entropy: str = "auto", out=None, as_te
         rc = lib.mi355_jpeg_decode(device, sd, n, _lib.JPEG_ENTROPY[entropy], (_lib.RenderOut * n)(*od), status, None, msp)
     _lib.check(rc)
     if timing is not None:
-        timing.append({"ms": float(ms.value), "entropy": ["gpu" if s.entropy_used == 1 else "host" for s in sd]})
+        timing.append({"ms": float(ms.value), "entropy": [{1: "gpu", 3: "sync"}.get(s.entropy_used, "host") for s in sd]})
     return outs[0] if single else outs
 
 
@@ -775,7 +777,7 @@ def jpeg_decode_coefficients(streams, device: int = 0, entropy: str = "auto"):
     """The entropy stage of :func:`jpeg_decode` alone (``mi355_op_jpeg_decode_coefficients``): per stream int16 [blocks, 64] -- the
     quantised coefficients in zigzag order, blocks in scan order, DC absolute.  ``device=-1`` runs the host twin."""
     if entropy not in _lib.JPEG_ENTROPY:
-        raise ValueError(f"entropy must be 'auto', 'gpu' or 'host', got {entropy!r}")
+        raise ValueError(f"entropy must be 'auto', 'gpu', 'host' or 'sync', got {entropy!r}")
     fr, single = _jpeg_streams(streams)
     n = len(fr)
     outs = [np.zeros((f.blocks, 64), np.int16) for f in fr]
@@ -783,6 +785,30 @@ def jpeg_decode_coefficients(streams, device: int = 0, entropy: str = "auto"):
     sd = (_lib.JpegStream * n)(*[f.struct() for f in fr])
     _lib.check(_lib.lib().mi355_op_jpeg_decode_coefficients(int(device), sd, n, _lib.JPEG_ENTROPY[entropy], ptrs, (C.c_int * n)()))
     return outs[0] if single else outs
+
+
+def jpeg_sync(stream, device: int = 0, sub_bytes: int = 128, seq_subs: int = 256):
+    """``entropy="sync"`` on one stream with subsequences of ``sub_bytes`` bytes (a power of two >= 8) and sequences of ``seq_subs``
+    subsequences (2 .. 256) -- the test hook ``mi355_op_jpeg_sync`` (csrc/jpeg_sync.h); ``device=-1`` runs the host twin.
+    -> ``{"coefficients": int16 [blocks, 64], "status": 0 | 1 .. 4, "states": int64 [nsub, 6] -- per subsequence (segment, byte, bit, j,
+    k, B) of its true entry state, "stats": {"nsub", "nseq", "rounds_local", "rounds_global"}}``."""
+    fr, single = _jpeg_streams(stream)
+    if not single:
+        raise ValueError("jpeg_sync takes one stream")
+    f = fr[0]
+    lib = _lib.lib()
+    sd = f.struct()
+    stats = _lib.JpegSyncStats()
+    _lib.check(lib.mi355_op_jpeg_sync(int(device), C.byref(sd), int(sub_bytes), int(seq_subs), None, None, None, 0, C.byref(stats)))
+    nsub = int(stats.nsub)
+    coef = np.zeros((f.blocks, 64), np.int16)
+    states = (_lib.JpegSyncState * nsub)()
+    status = C.c_int(0)
+    _lib.check(lib.mi355_op_jpeg_sync(int(device), C.byref(sd), int(sub_bytes), int(seq_subs), coef.ctypes.data, C.byref(status), states, nsub,
+                                      C.byref(stats)))
+    rows = np.array([(s.segment, s.byte, s.bit, s.j, s.k, s.block) for s in states], np.int64).reshape(nsub, 6)
+    return {"coefficients": coef, "status": int(status.value), "states": rows,
+            "stats": {k: int(getattr(stats, k)) for k in ("nsub", "nseq", "rounds_local", "rounds_global")}}
 
 
 def nms(pred: np.ndarray, nc: int, conf: float = 0.25, iou: float = 0.7, classes: Optional[Sequence[int]] = None,

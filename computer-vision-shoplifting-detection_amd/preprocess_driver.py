@@ -62,9 +62,11 @@ class ImageDirCapture:
 
     EXTS = (".jpg", ".jpeg", ".png", ".bmp")
 
-    def __init__(self, source: str, decode: bool = True):
+    def __init__(self, source: str, decode: bool = True, entropy: Optional[str] = None):
         """``decode=False``: ``.jpg`` / ``.jpeg`` files are not decoded here but handed on as ``cvsd_amd.JPEGFrame`` -- compressed bytes the
-        engine decodes on the GPU; other formats are decoded as always."""
+        engine decodes on the GPU; other formats are decoded as always.  ``entropy``: the frames' own request
+        (``JPEGFrame(data, entropy=...)``), e.g. "sync" for a dump without restart markers."""
+        self._entropy = entropy
         self._files: Optional[List[str]] = None
         self._pos = 0
         self._decode = bool(decode)
@@ -92,7 +94,7 @@ class ImageDirCapture:
             return False, None
         if not self._decode and self._files[self._pos].lower().endswith((".jpg", ".jpeg")):
             from .jpeg_decode import JPEGFrame
-            frame = JPEGFrame.open(self._files[self._pos])
+            frame = JPEGFrame.open(self._files[self._pos], entropy=self._entropy)
             self._pos += 1
             return True, frame
         from PIL import Image
@@ -114,11 +116,12 @@ class MjpegCapture:
     """cv2.VideoCapture look-alike over a raw concatenated MJPEG file (``.mjpeg`` / ``.mjpg``: one JPEG stream behind the other, as an IP
     camera's HTTP stream is commonly dumped).  The file is split at SOI / EOI outside entropy-coded data; ``read()`` yields
     ``cvsd_amd.JPEGFrame``s -- nothing is decoded here, the engine does that on the GPU.  No AVI or MP4 container is
-    parsed.  Opt-in: ``open_capture`` does not return it."""
+    parsed.  Opt-in: ``open_capture`` does not return it.  ``entropy``: the frames' own request (``JPEGFrame(data, entropy=...)``)."""
 
     EXTS = (".mjpeg", ".mjpg")
 
-    def __init__(self, source: str):
+    def __init__(self, source: str, entropy: Optional[str] = None):
+        self._entropy = entropy
         self._streams: Optional[List[bytes]] = None
         self._pos = 0
         if isinstance(source, (bytes, bytearray, memoryview)):
@@ -140,7 +143,7 @@ class MjpegCapture:
         if self._streams is None or self._pos >= len(self._streams):
             return False, None
         from .jpeg_decode import JPEGFrame
-        frame = JPEGFrame(self._streams[self._pos])
+        frame = JPEGFrame(self._streams[self._pos], entropy=self._entropy)
         self._pos += 1
         return True, frame
 

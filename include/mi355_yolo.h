@@ -733,18 +733,30 @@ int  mi355_op_jpeg_coefficients(int device, const mi355_render_frame* frames, in
  *            bytes.  outs[i]: the BGR destination of stream i in host memory or memory of that GPU (on_device = 1), row_stride >= 3 x
  *            width.  entropy: MI355_JPEG_ENTROPY_GPU -- one GPU lane per restart segment (a stream without DRI is one segment on one
  *            lane: slow, correct); _HOST -- the twin's segment routine on the calling thread, the coefficients uploaded (128 bytes per
- *            block), only the idct and colour launches run; _AUTO -- _GPU for a stream with a restart interval, _HOST for one without.
+ *            block), only the idct and colour launches run; _AUTO -- _GPU for a stream with a restart interval, _HOST for one without;
+ *            _SYNC -- many GPU lanes per restart segment: the self-synchronising parallel Huffman decoder of csrc/jpeg_sync.h, for
+ *            streams without restart markers (opt-in: _AUTO never chooses it; device -1 runs its host twin, round for round).
+ *            streams[i].entropy, when non-zero, is that stream's own request and replaces the call's argument for it.
  *            The call sets streams[i].entropy_used.  All streams of a call, whatever their sizes and layouts, take three launches on
- *            `stream` (two when no stream's entropy stage runs on the GPU); the stream bytes are staged through pinned memory in one
+ *            `stream` (two when no stream's entropy stage runs on the GPU, four more when any stream is decoded with _SYNC: local
+ *            rounds, global rounds + block index, write pass, DC pass); the stream bytes are staged through pinned memory in one
  *            copy; the call returns when the launches and copies have finished.  status (n ints, or NULL) receives 0 or an
  *            MI355_JPEG_* status per stream.  When any is non-zero the call returns MI355_EINVAL naming the first such stream; the
  *            other streams' frames are complete, a failed stream's host destination is untouched.  launch_ms (or NULL): the launches'
  *            device time.  At most MI355_RENDER_MAX_FRAMES streams per call.
  *   mi355_yolo_decode   the same on an engine handle: its device and stream, scratch kept between calls.
- *   mi355_op_jpeg_decode_coefficients   the entropy stage alone: coefs[i] (host) receives int16 [blocks][64]. */
+ *   mi355_op_jpeg_decode_coefficients   the entropy stage alone: coefs[i] (host) receives int16 [blocks][64].
+ *   mi355_op_jpeg_sync   test hook of _SYNC on one stream with subsequences of sub_bytes bytes (a power of two >= 8) and sequences of
+ *            seq_subs subsequences (2 .. 256); device -1: the host twin.  coef (host, int16 [blocks][64]) and status as above (a corrupt
+ *            stream is no error of this call); states[i], i < stats->nsub: the true entry state of subsequence i -- its segment, the
+ *            position (byte, bit) relative to the segment's begin, the block j within the MCU, the zigzag index k of the next coefficient
+ *            (0: a DC symbol) and the block in progress; stats: subsequences, sequences, rounds_local (the most local rounds in which
+ *            something changed, over the sequences) and rounds_global (the global rounds in which something changed).  With coef NULL
+ *            only stats->nsub and stats->nseq are filled: what the caller needs to size `states` (max_states entries). */
 #define MI355_JPEG_ENTROPY_AUTO 0
 #define MI355_JPEG_ENTROPY_GPU  1
 #define MI355_JPEG_ENTROPY_HOST 2
+#define MI355_JPEG_ENTROPY_SYNC 3
 #define MI355_JPEG_CODE_NOT_FOUND 1
 #define MI355_JPEG_RUN_PAST_BLOCK 2
 #define MI355_JPEG_SEGMENT_SHORT  3
@@ -752,9 +764,18 @@ int  mi355_op_jpeg_coefficients(int device, const mi355_render_frame* frames, in
 typedef struct mi355_jpeg_stream {
     const uint8_t* data;                /* host memory */
     int64_t length;
-    int entropy_used;                   /* set by the call: MI355_JPEG_ENTROPY_GPU or _HOST */
-    int reserved;
+    int entropy_used;                   /* set by the call: MI355_JPEG_ENTROPY_GPU, _HOST or _SYNC */
+    int entropy;                        /* this stream's own request, MI355_JPEG_ENTROPY_*; 0: the call's argument */
 } mi355_jpeg_stream;
+typedef struct mi355_jpeg_sync_state {
+    int segment;
+    uint32_t byte;
+    int bit, j, k;
+    uint32_t block;
+} mi355_jpeg_sync_state;
+typedef struct mi355_jpeg_sync_stats {
+    int nsub, nseq, rounds_local, rounds_global;
+} mi355_jpeg_sync_stats;
 typedef struct mi355_jpeg_stream_info {
     int height, width, components;
     int subsampling;                    /* 444, 422, 420; 400: gray */
@@ -768,6 +789,8 @@ int  mi355_jpeg_decode(int device, mi355_jpeg_stream* streams, int n, int entrop
 int  mi355_yolo_decode(mi355_yolo* h, mi355_jpeg_stream* streams, int n, int entropy, const mi355_render_out* outs, int* status,
                        float* launch_ms);
 int  mi355_op_jpeg_decode_coefficients(int device, mi355_jpeg_stream* streams, int n, int entropy, int16_t* const* coefs, int* status);
+int  mi355_op_jpeg_sync(int device, mi355_jpeg_stream* stream, int sub_bytes, int seq_subs, int16_t* coef, int* status,
+                        mi355_jpeg_sync_state* states, int max_states, mi355_jpeg_sync_stats* stats);
 /* Depthwise 3x3 conv (stride 1, pad 1) + bias (+SiLU) (+residual) on channel views, fp32, as the engine runs YOLO11's
  * DWConv and Attention.pe (ultralytics nn/modules/conv.py:DWConv, Conv with groups = c).  x[n][h][w][x_cs] holds the input view at
  * channels x_off .. x_off+c-1; residual (or NULL) [n][h][w][res_cs] at res_off; y[n][h][w][y_cs] is read in, its view y_off ..
