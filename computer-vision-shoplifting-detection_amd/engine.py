@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+from contextlib import nullcontext
 from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
@@ -18,9 +19,11 @@ import torch
 
 from . import _lib
 from .results import Results
+from .sources import (IMGSZ, IOU, MAX_DET, DetArgs, DeviceFrame, DeviceFrames, Ragged, YuvBatch, as_batch, bgr_view, det_args,
+                      det_args_from, ready)
 from .weights import build_from_state_dict, from_bytes
 from .jpeg_decode import decode_sources, has_frames as has_jpeg_frames
-from .yuv import YUVFrame, as_frames, struct_array
+from .yuv import YUVFrame, as_frames
 
 COCO_NAMES = ["person", "bicycle", "car", "motorcycle", "airplane", "bus", "train", "truck", "boat", "traffic light",
               "fire hydrant", "stop sign", "parking meter", "bench", "bird", "cat", "dog", "horse", "sheep", "cow",
@@ -147,172 +150,61 @@ class YOLO:
         return i.n_convs, int(i.n_params), 0, 2.0 * i.macs_640 / 1e9     # (layers, params, gradients, GFLOPs)
 
     # ------------------------------------------------------------------------------------------ inference
-    class _Ragged:
-        """Frames of different (h, w) in one call (several cameras): host arrays or CUDA tensors on the engine's GPU, each passed to
-        ``mi355_yolo_infer_multi`` by pointer with its own row stride.  The engine letterboxes them to the square ``imgsz x imgsz``
-        canvas, as Ultralytics' ``BasePredictor.pre_transform`` does for a batch whose shapes differ."""
-        def __init__(self, frames, on_device: bool):
-            self.on_device = bool(on_device)
-            self.frames = []
-            for f in frames:
-                if on_device:
-                    if f.dtype != torch.uint8 or f.ndim != 3 or f.shape[-1] != 3:
-                        raise ValueError("tensor frames must be uint8 [H,W,3] BGR")
-                    if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.shape[1]:
-                        f = f.contiguous()
-                else:
-                    f = np.asarray(f)
-                    if f.dtype != np.uint8 or f.ndim != 3 or f.shape[-1] != 3:
-                        raise ValueError("frames must be uint8 arrays of shape [H,W,3] (BGR, as cv2 delivers them)")
-                    if f.strides[2] != 1 or f.strides[1] != 3 or f.strides[0] < 3 * f.shape[1]:
-                        f = np.ascontiguousarray(f)
-                self.frames.append(f)                       # kept alive for the call: the engine reads them by pointer
-            n = len(self.frames)
-            self.shape = (n,)
-            self.shapes = [(int(f.shape[0]), int(f.shape[1])) for f in self.frames]
-            self.heights = np.array([s[0] for s in self.shapes], np.int32)
-            self.widths = np.array([s[1] for s in self.shapes], np.int32)
-            self.row_strides = np.array([f.stride(0) if on_device else f.strides[0] for f in self.frames], np.int32)
-            self.ptrs = (C.c_void_p * n)(*[f.data_ptr() if on_device else f.ctypes.data for f in self.frames])
-
-        def args(self):
-            i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
-            return self.ptrs, i32(self.heights), i32(self.widths), i32(self.row_strides), int(self.on_device), self.shape[0]
-
-    class _RaggedDevice(_Ragged):
-        """Dense BGR uint8 frames of different (h, w) that already sit on the engine's GPU, known by raw pointer (YOLO.track_cameras: the
-        copies the tick's motion compensation uploaded)."""
-        def __init__(self, ptrs, shapes):
-            n = len(ptrs)
-            self.on_device, self.frames = True, None
-            self.shape = (n,)
-            self.shapes = [(int(h), int(w)) for h, w in shapes]
-            self.heights = np.array([s[0] for s in self.shapes], np.int32)
-            self.widths = np.array([s[1] for s in self.shapes], np.int32)
-            self.row_strides = np.array([3 * s[1] for s in self.shapes], np.int32)
-            self.ptrs = (C.c_void_p * n)(*[int(p) for p in ptrs])
-
-    class _YuvBatch:
-        """NV12 / I420 frames (:class:`YUVFrame`) of any sizes in one call, all on the host or all on the engine's GPU, passed to
-        ``mi355_yolo_infer_yuv`` by plane pointers: the engine converts them to BGR on the GPU in front of the letterbox."""
-        def __init__(self, frames):
-            self.frames = list(frames)                          # kept alive for the call: the engine reads the planes by pointer
-            on_dev = {f.on_device for f in self.frames}
-            if len(on_dev) != 1:
-                raise ValueError("a list of YUVFrames must be all host planes or all CUDA planes")
-            self.on_device = on_dev.pop()
-            self.shape = (len(self.frames),)
-            self.shapes = [f.shape for f in self.frames]
-            self.structs = struct_array(self.frames)
-
-        def check_device(self, device: int):
-            if self.on_device:
-                if any(p.device.index != device for f in self.frames for p in f._planes()):
-                    raise ValueError("frames live on a different GPU than the engine")
-                torch.cuda.current_stream(self.frames[0].y.device).synchronize()     # the engine runs on its own stream
-
-    @staticmethod
-    def _as_batch(source):
-        """-> (array-or-tensor [N,H,W,3] uint8, list of originals or None); a list of frames of different shapes -> (_Ragged, list of
-        originals or None); YUVFrames -> (_YuvBatch, None)"""
-        yuv = as_frames(source)
-        if yuv is not None:
-            return YOLO._YuvBatch(yuv), None
-        if isinstance(source, torch.Tensor):
-            if source.dtype != torch.uint8 or source.ndim != 4 or source.shape[-1] != 3:
-                raise ValueError("tensor sources must be uint8 [N,H,W,3] BGR frames")
-            return source.contiguous(), None
-        if isinstance(source, np.ndarray):
-            if source.ndim == 3:
-                source = source[None]
-            if source.dtype != np.uint8 or source.ndim != 4 or source.shape[-1] != 3:
-                raise ValueError("frames must be uint8 arrays of shape [H,W,3] (BGR, as cv2 delivers them)")
-            return np.ascontiguousarray(source), list(source)
-        if isinstance(source, (list, tuple)):
-            if not source:
-                raise ValueError("empty source")
-            shapes = {tuple(np.shape(f)) for f in source}
-            on_dev = [isinstance(f, torch.Tensor) and f.is_cuda for f in source]
-            if any(on_dev):
-                if not all(on_dev):
-                    raise ValueError("a list of frames must be all host arrays or all CUDA tensors")
-                if len(shapes) == 1:
-                    return YOLO._as_batch(torch.stack(list(source)))
-                return YOLO._Ragged(source, True), None
-            if len(shapes) != 1:
-                return YOLO._Ragged(source, False), list(source)
-            arr = np.ascontiguousarray(np.stack([np.asarray(f) for f in source]))
-            return YOLO._as_batch(arr)[0], list(source)
-        raise TypeError(f"unsupported source type {type(source).__name__}: pass decoded BGR uint8 frames "
-                        f"(frame decode stays on the host, as in the reference's cv2.VideoCapture loop)")
-
-    class _DeviceFrames:
-        """n dense BGR uint8 frames that already sit on the engine's GPU, known by raw pointer (YOLO.track: the copy the tracker's motion
-        compensation uploaded)."""
-        def __init__(self, ptr: int, n: int, h: int, w: int):
-            self.ptr, self.shape = int(ptr), (int(n), int(h), int(w), 3)
+    # the batch kinds and the source normaliser live in sources.py; these names are what tests, tools and bench.py use
+    _Ragged, _RaggedDevice, _DeviceFrames, _YuvBatch = Ragged, Ragged.from_pointers, DeviceFrames, YuvBatch
+    _as_batch = staticmethod(as_batch)
 
     def _infer_rows(self, batch, conf, iou, classes, max_det, imgsz, half=None, feats=None, feats_out: Optional[list] = None):
         """-> (rows [n, max_det, 58 words], counts [n], (h, w) or the list of them).  An engine with feature output appends
-        float32 [n, max_det, s] to ``feats_out``, parallel to ``rows``."""
-        if feats_out is None or not (self.feats if feats is None else feats):
-            return self._infer_rows_locked(batch, conf, iou, classes, max_det, imgsz, half, feats)      # the call as it always was
-        with self._lock:                       # re-entered by the call below: the features are fetched before another thread's call replaces them
-            out = self._infer_rows_locked(batch, conf, iou, classes, max_det, imgsz, half, feats)
-            hnd = self._last_handle
-            dim = C.c_int()
-            _lib.check(_lib.lib().mi355_yolo_feat_dim(hnd, C.byref(dim)))
-            if dim.value:
-                f = np.empty((len(out[1]), max_det, dim.value), np.float32)      # only f[i, :counts[i]] are written / meaningful
-                _lib.check(_lib.lib().mi355_yolo_last_feats(hnd, f.ctypes.data, max_det, len(out[1])))
-                feats_out.append(f)
-        return out
+        float32 [n, max_det, s] to ``feats_out``, parallel to ``rows``.  A dense ``batch`` is used as it is: no check, no copy."""
+        a = det_args(conf, iou, classes, max_det, imgsz, half, feats)
+        shape = batch.shapes if isinstance(batch, (Ragged, YuvBatch)) else (int(batch.shape[1]), int(batch.shape[2]))
+        want = feats_out is not None and (self.feats if feats is None else feats)
+        # without features the lock is held around the device wait and the C call alone (inside _run); with them it is held (and
+        # re-entered there) until they are fetched, before another thread's call replaces them
+        with self._lock if want else nullcontext():
+            rows, counts, _ = self._run(batch, a)
+            if want:
+                dim = C.c_int()
+                _lib.check(_lib.lib().mi355_yolo_feat_dim(self._last_handle, C.byref(dim)))
+                if dim.value:
+                    f = np.empty((len(counts), a.max_det, dim.value), np.float32)      # only f[i, :counts[i]] are written / meaningful
+                    _lib.check(_lib.lib().mi355_yolo_last_feats(self._last_handle, f.ctypes.data, a.max_det, len(counts)))
+                    feats_out.append(f)
+        return rows, counts, shape
 
-    def _infer_rows_locked(self, batch, conf, iou, classes, max_det, imgsz, half, feats):
+    def _run(self, batch, a: DetArgs, tile_opts=None):
+        """THE blocking detector call: allocates the outputs, takes the lock, waits for the batch (``sources.ready``), notes the engine
+        that runs (``_last_handle``) and dispatches on the batch kind -- the only place that does.  -> (rows [n, max_det, 58 words],
+        counts [n], tile_idx [n, max_det] of a tiled call or None).  ``tile_opts``: the ``mi355_tile_opts`` of a tiled call, whose batch
+        is by pointer (Ragged or YuvBatch)."""
         lib = _lib.lib()
-        hnd = self._handle(half, feats)
-        self._last_handle = hnd
+        hnd = self._handle(a.half, a.feats)
         n = int(batch.shape[0])
-        h, w = (0, 0) if isinstance(batch, (YOLO._Ragged, YOLO._YuvBatch)) else (int(batch.shape[1]), int(batch.shape[2]))
-        rows = np.empty((n, max_det, _lib.DET_WORDS), dtype=np.float32)    # only rows[i, :counts[i]] are written / meaningful
+        rows = np.empty((n, a.max_det, _lib.DET_WORDS), dtype=np.float32)    # only rows[i, :counts[i]] are written / meaningful
         counts = np.zeros(n, dtype=np.int32)
-        cls_arr = None
-        ncls = 0
-        if classes is not None:
-            cl = [int(classes)] if np.isscalar(classes) else [int(c) for c in classes]
-            cls_arr = (C.c_int * len(cl))(*cl)
-            ncls = len(cl)
-        cp = counts.ctypes.data_as(C.POINTER(C.c_int))
+        det = (a.conf, a.iou, *a.classes, a.max_det, a.imgsz, rows.ctypes.data, a.max_det, counts.ctypes.data_as(C.POINTER(C.c_int)))
+        tile_idx = None if tile_opts is None else np.full((n, a.max_det), -1, np.int32)
         with self._lock:
-            if isinstance(batch, YOLO._YuvBatch):
-                batch.check_device(self.device)
-                _lib.check(lib.mi355_yolo_infer_yuv(hnd, batch.structs, int(batch.on_device), n, conf, iou, cls_arr, ncls, max_det, imgsz,
-                                                    rows.ctypes.data, max_det, cp))
-                return rows, counts, batch.shapes
-            if isinstance(batch, YOLO._Ragged):
-                if batch.on_device and batch.frames is not None:
-                    if any(f.device.index != self.device for f in batch.frames):
-                        raise ValueError("frames live on a different GPU than the engine")
-                    torch.cuda.current_stream(batch.frames[0].device).synchronize()   # engine runs on its own stream
-                _lib.check(lib.mi355_yolo_infer_multi(hnd, *batch.args(), conf, iou, cls_arr, ncls, max_det, imgsz, rows.ctypes.data,
-                                                      max_det, cp))
-                return rows, counts, batch.shapes
-            if isinstance(batch, YOLO._DeviceFrames):
-                _lib.check(lib.mi355_yolo_infer_device(hnd, batch.ptr, n, h, w, conf, iou, cls_arr, ncls, max_det, imgsz, rows.ctypes.data, max_det, cp))
-                return rows, counts, (h, w)
-            if isinstance(batch, torch.Tensor):
-                if not batch.is_cuda:
-                    batch = batch.numpy()
+            self._last_handle = hnd           # inside the lock: what _build_results, _render_into, plan_info and last_timing read is this call's
+            ready(batch, self.device)
+            if tile_opts is not None:
+                if isinstance(batch, YuvBatch):
+                    rc = lib.mi355_yolo_infer_tiled_yuv(hnd, batch.structs, int(batch.on_device), n, C.byref(tile_opts), *det, tile_idx.ctypes.data)
                 else:
-                    if batch.device.index != self.device:
-                        raise ValueError("frames live on a different GPU than the engine")
-                    torch.cuda.current_stream(batch.device).synchronize()   # engine runs on its own stream
-                    _lib.check(lib.mi355_yolo_infer_device(hnd, batch.data_ptr(), n, h, w, conf, iou, cls_arr, ncls,
-                                                           max_det, imgsz, rows.ctypes.data, max_det, cp))
-                    return rows, counts, (h, w)
-            _lib.check(lib.mi355_yolo_infer(hnd, batch.ctypes.data, n, h, w, 0, conf, iou, cls_arr, ncls, max_det,
-                                            imgsz, rows.ctypes.data, max_det, cp))
-        return rows, counts, (h, w)
+                    rc = lib.mi355_yolo_infer_tiled(hnd, *batch.args(), C.byref(tile_opts), *det, tile_idx.ctypes.data)
+            elif isinstance(batch, YuvBatch):
+                rc = lib.mi355_yolo_infer_yuv(hnd, batch.structs, int(batch.on_device), n, *det)
+            elif isinstance(batch, Ragged):
+                rc = lib.mi355_yolo_infer_multi(hnd, *batch.args(), *det)
+            elif isinstance(batch, DeviceFrames) or (isinstance(batch, torch.Tensor) and batch.is_cuda):
+                rc = lib.mi355_yolo_infer_device(hnd, batch.data_ptr(), *batch.shape[:3], *det)
+            else:
+                if isinstance(batch, torch.Tensor):
+                    batch = batch.numpy()     # a CPU tensor goes in as the array it is
+                rc = lib.mi355_yolo_infer(hnd, batch.ctypes.data, *batch.shape[:3], 0, *det)
+            _lib.check(rc)
+        return rows, counts, tile_idx
 
     # ---- device-resident results (multi-GPU pipelines): nothing crosses PCIe, nothing blocks --------------------------
     def new_device_rows(self, n: int, max_det: int = 300):
@@ -321,8 +213,8 @@ class YOLO:
         return (torch.empty((n * max_det, _lib.DET_WORDS), dtype=torch.float32, device=dev),
                 torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
 
-    def infer_async(self, frames: torch.Tensor, out, conf: float = 0.25, iou: float = 0.7, classes=None, max_det: int = 300,
-                    imgsz: int = 640, half=None) -> None:
+    def infer_async(self, frames: torch.Tensor, out, conf: float = 0.25, iou: float = IOU, classes=None, max_det: int = MAX_DET,
+                    imgsz: int = IMGSZ, half=None) -> None:
         """Enqueue one batch of CUDA-resident uint8 frames [n,H,W,3]; the packed post-NMS rows (frame order), the per-frame
         counts and their sum land in ``out`` (from :meth:`new_device_rows`) -- all in HBM.  Returns at once; order other
         streams behind :attr:`stream` (or call :meth:`sync`) before reading ``out``.  ``frames`` may also be a list of CUDA
@@ -330,32 +222,24 @@ class YOLO:
         rows, counts, total = out
         yuv = as_frames(frames)
         if yuv is not None:
-            yuv = YOLO._YuvBatch(yuv)
-            if not yuv.on_device or len(set(yuv.shapes)) != 1:
+            frames = YuvBatch(yuv)
+            if not frames.on_device or len(set(frames.shapes)) != 1:
                 raise ValueError("infer_async needs YUVFrames of one size with planes on the engine's GPU")
-            n = yuv.shape[0]
-        else:
-            n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-            if not frames.is_cuda or frames.dtype != torch.uint8 or frames.device.index != self.device:
-                raise ValueError("infer_async needs uint8 frames on the engine's GPU")
+        elif not frames.is_cuda or frames.dtype != torch.uint8 or frames.device.index != self.device:
+            raise ValueError("infer_async needs uint8 frames on the engine's GPU")
+        n = int(frames.shape[0])
         if rows.shape[0] < n * max_det or counts.numel() < n:
             raise ValueError("output buffers are too small for n * max_det rows")
-        cls_arr, ncls = None, 0
-        if classes is not None:
-            cl = [int(classes)] if np.isscalar(classes) else [int(c) for c in classes]
-            cls_arr, ncls = (C.c_int * len(cl))(*cl), len(cl)
+        a = det_args(conf, iou, classes, max_det, imgsz, half)
+        det = (a.conf, a.iou, *a.classes, a.max_det, a.imgsz, rows.data_ptr(), counts.data_ptr(), total.data_ptr())
         hnd = self._handle(half)
         self._async_handle = hnd              # `stream` / `sync()` refer to the engine that received the last asynchronous call
         with self._lock:
+            ready(frames, self.device)        # the frames must be complete; the engine has its own stream
             if yuv is not None:
-                yuv.check_device(self.device)
-                _lib.check(_lib.lib().mi355_yolo_infer_yuv_device_async(hnd, yuv.structs, n, float(conf), float(iou), cls_arr, ncls, int(max_det),
-                                                                        int(imgsz), rows.data_ptr(), counts.data_ptr(), total.data_ptr()))
-                return
-            torch.cuda.current_stream(frames.device).synchronize()       # the frames must be complete; the engine has its own stream
-            _lib.check(_lib.lib().mi355_yolo_infer_device_async(hnd, frames.data_ptr(), n, h, w, float(conf), float(iou), cls_arr, ncls,
-                                                                int(max_det), int(imgsz), rows.data_ptr(), counts.data_ptr(),
-                                                                total.data_ptr()))
+                _lib.check(_lib.lib().mi355_yolo_infer_yuv_device_async(hnd, frames.structs, n, *det))
+            else:
+                _lib.check(_lib.lib().mi355_yolo_infer_device_async(hnd, frames.data_ptr(), *frames.shape[:3], *det))
 
     @property
     def stream(self) -> "torch.cuda.ExternalStream":
@@ -373,8 +257,8 @@ class YOLO:
         for hnd in self._all_handles():
             _lib.check(_lib.lib().mi355_yolo_sync(hnd))
 
-    def predict(self, source=None, conf: Optional[float] = None, iou: float = 0.7, classes=None, max_det: int = 300,
-                imgsz: int = 640, half: Optional[bool] = None, verbose: bool = False, stream: bool = False,
+    def predict(self, source=None, conf: Optional[float] = None, iou: float = IOU, classes=None, max_det: int = MAX_DET,
+                imgsz: int = IMGSZ, half: Optional[bool] = None, verbose: bool = False, stream: bool = False,
                 feats: Optional[bool] = None, tile=None, overlap: float = 0.2, full_frame: bool = True, tile_iou: float = 0.5,
                 tile_metric: str = "ios", render=None, encode=None, **kwargs) -> List[Results]:
         """``model.predict`` / ``model(...)``: ultralytics/engine/model.py:Model.predict.
@@ -399,39 +283,32 @@ class YOLO:
         come back.  ``None`` (default): the call as it always was."""
         from .jpeg import as_spec as as_jpeg_spec
         from .render import as_spec
-        if isinstance(imgsz, (list, tuple)):
-            imgsz = int(max(imgsz))
-        conf = 0.25 if conf is None else float(conf)
+        a = det_args(0.25 if conf is None else conf, iou, classes, max_det, imgsz, half, feats)
         if has_jpeg_frames(source):
             # JPEG ingest (DESIGN.md 3.21): every JPEGFrame of the call is decoded in ONE call on the engine's stream into CUDA tensors;
             # from here on the call is the one it is for CUDA BGR tensors
             with self._lock:                   # the handle's stream and decode scratch: no other call of this model in between
                 source = decode_sources(source, self.device, self._handle(half, feats))
         spec, jspec = as_spec(render), as_jpeg_spec(encode)
-        if spec is None and jspec is None:
-            if tile is not None:
-                batch, originals = self._as_tile_batch(source)
-                return self._predict_tiled(batch, originals, conf, iou, classes, max_det, imgsz, half, feats, tile, overlap, full_frame, tile_iou, tile_metric)
-            batch, originals = self._as_batch(source)
-            return self._predict_batch(batch, originals, conf, iou, classes, max_det, imgsz, half, feats)
-        with self._lock:                       # the picture is drawn from the frames this call leaves on the GPU: no other call in between
-            if tile is not None:
-                batch, originals = self._as_tile_batch(source)
-                res = self._predict_tiled(batch, originals, conf, iou, classes, max_det, imgsz, half, feats, tile, overlap, full_frame, tile_iou, tile_metric)
-            else:
-                batch, originals = self._as_batch(source)
-                res = self._predict_batch(batch, originals, conf, iou, classes, max_det, imgsz, half, feats)
-            return self._render_into(res, spec, None, lambda: self._batch_frames(batch), jspec)
+        tiling = None if tile is None else dict(tile=tile, overlap=overlap, full_frame=full_frame, tile_iou=tile_iou, tile_metric=tile_metric)
+        plain = spec is None and jspec is None
+        # render= / encode=: the picture is drawn from the frames this call leaves on the GPU, so no other call may come in between
+        # (the lock is re-entrant); a plain call holds the lock around its C call only
+        with nullcontext() if plain else self._lock:
+            batch, originals = as_batch(source, by_pointer=tiling is not None)
+            res = self._detect(batch, originals, a, tiling)
+            return res if plain else self._render_into(res, spec, None, lambda: self._batch_frames(batch), jspec)
+
+    def _detect(self, batch, originals, a: DetArgs, tiling: Optional[dict] = None) -> List[Results]:
+        """one detector call on a batch: tiled (``tiling``: the tile arguments of :meth:`predict`) or not"""
+        if tiling is not None:
+            return self._predict_tiled(batch, originals, *a, **tiling)
+        return self._predict_batch(batch, originals, *a)
 
     @staticmethod
     def _batch_frames(batch) -> list:
         """the frames of a call as ``ops.render`` takes them (the fallback of ``_render_into``: a copy that has left the GPU)"""
-        if isinstance(batch, (YOLO._Ragged, YOLO._YuvBatch)):
-            if batch.frames is None:
-                from .ops import DeviceFrame
-                return [DeviceFrame(p, h, w) for p, (h, w) in zip(batch.ptrs, batch.shapes)]
-            return list(batch.frames)
-        return list(batch)
+        return batch.render_frames() if isinstance(batch, (Ragged, YuvBatch)) else list(batch)
 
     def _render_into(self, results, spec, sources, fallback=None, jspec=None):
         """Fills ``Results.rendered`` of every non-None result with ONE render call on the engine that ran the detector.  ``sources``
@@ -472,12 +349,12 @@ class YOLO:
                 results[i].rendered = pic
         return results
 
-    def detect_rows(self, batch, conf: float = 0.25, iou: float = 0.7, classes=None, max_det: int = 300, imgsz: int = 640, half=None):
+    def detect_rows(self, batch, conf: float = 0.25, iou: float = IOU, classes=None, max_det: int = MAX_DET, imgsz: int = IMGSZ, half=None):
         """``Results.boxes.data`` of every frame of ``batch`` -- float32 [M, 6] rows x1, y1, x2, y2, conf, cls -- and the frames' (h, w),
         without building the Results objects (a sweep reads nothing else: cvsd_amd/sweep.py).  ``batch``: what :meth:`predict` takes
         after stacking, or frames already on the engine's GPU (:class:`_DeviceFrames`).  For frames of different shapes
         (:class:`_Ragged`) the second value is the list of every frame's (h, w)."""
-        rows, counts, shape = self._infer_rows(batch, float(conf), float(iou), classes, int(max_det), int(imgsz), half)
+        rows, counts, shape = self._infer_rows(batch, conf, iou, classes, max_det, imgsz, half)
         out = []
         for i in range(len(counts)):
             r = rows[i, :counts[i]]
@@ -489,7 +366,7 @@ class YOLO:
 
     def _predict_batch(self, batch, originals, conf, iou, classes, max_det, imgsz, half, feats=None) -> List[Results]:
         fout = []
-        rows, counts, shape = self._infer_rows(batch, conf, float(iou), classes, int(max_det), int(imgsz), half, feats, fout)
+        rows, counts, shape = self._infer_rows(batch, conf, iou, classes, max_det, imgsz, half, feats, fout)
         return self._build_results(rows, counts, shape, originals, fout)
 
     def _build_results(self, rows, counts, shape, originals, fout, tile_idx=None, tiles=None) -> List[Results]:
@@ -523,32 +400,6 @@ class YOLO:
     __call__ = predict
 
     # ---- tiled predict -----------------------------------------------------------------------------------------
-    @staticmethod
-    def _as_tile_batch(source):
-        """The frames of a tiled call, each passed by pointer with its own row stride: -> (_Ragged or _YuvBatch, originals or None).
-        Takes what :meth:`predict` takes; `_as_batch` is not involved, so calls without ``tile`` see no change."""
-        yuv = as_frames(source)
-        if yuv is not None:
-            return YOLO._YuvBatch(yuv), None
-        if isinstance(source, torch.Tensor):
-            if source.dtype != torch.uint8 or source.ndim not in (3, 4) or source.shape[-1] != 3:
-                raise ValueError("tensor sources must be uint8 [N,H,W,3] BGR frames")
-            source = [source] if source.ndim == 3 else list(source)
-        elif isinstance(source, np.ndarray):
-            if source.dtype != np.uint8 or source.ndim not in (3, 4) or source.shape[-1] != 3:
-                raise ValueError("frames must be uint8 arrays of shape [H,W,3] (BGR, as cv2 delivers them)")
-            source = [source] if source.ndim == 3 else list(source)
-        if not isinstance(source, (list, tuple)):
-            raise TypeError(f"unsupported source type {type(source).__name__}: pass decoded BGR uint8 frames")
-        if not source:
-            raise ValueError("empty source")
-        on_dev = [isinstance(f, torch.Tensor) and f.is_cuda for f in source]
-        if any(on_dev) and not all(on_dev):
-            raise ValueError("a list of frames must be all host arrays or all CUDA tensors")
-        if not any(on_dev):
-            source = [f.numpy() if isinstance(f, torch.Tensor) else f for f in source]
-        return YOLO._Ragged(source, all(on_dev)), (None if all(on_dev) else list(source))
-
     def _predict_tiled(self, batch, originals, conf, iou, classes, max_det, imgsz, half, feats, tile, overlap=0.2, full_frame=True,
                        tile_iou=0.5, tile_metric="ios") -> List[Results]:
         """One tiled call (``mi355_yolo_infer_tiled`` / ``_tiled_yuv``): every argument is checked here, before any launch."""
@@ -562,7 +413,7 @@ class YOLO:
             raise TypeError(f"tile_iou must be a number in [0, 1], got {tile_iou!r}")
         if not 0 <= float(tile_iou) <= 1:
             raise ValueError(f"tile_iou must be in [0, 1], got {tile_iou!r}")
-        max_det, imgsz = int(max_det), int(imgsz)
+        max_det = int(max_det)
         tiles = []
         for h, w in batch.shapes:
             g = self._grid_px(h, w, th, tw, oy, ox)
@@ -574,30 +425,8 @@ class YOLO:
             tiles.append(g)
         opts = _lib.TileOpts(struct_size=C.sizeof(_lib.TileOpts), tile_h=th, tile_w=tw, overlap_y_px=oy, overlap_x_px=ox,
                              full_frame=int(bool(full_frame)), metric=ops.TILE_METRICS[tile_metric], thr=float(tile_iou))
-        lib = _lib.lib()
-        hnd = self._handle(half, False)
-        n = int(batch.shape[0])
-        rows = np.empty((n, max_det, _lib.DET_WORDS), dtype=np.float32)    # only rows[i, :counts[i]] are written / meaningful
-        counts = np.zeros(n, dtype=np.int32)
-        tile_idx = np.full((n, max_det), -1, np.int32)
-        cls_arr, ncls = None, 0
-        if classes is not None:
-            cl = [int(classes)] if np.isscalar(classes) else [int(c) for c in classes]
-            cls_arr, ncls = (C.c_int * len(cl))(*cl), len(cl)
-        cp = counts.ctypes.data_as(C.POINTER(C.c_int))
-        with self._lock:
-            self._last_handle = hnd
-            if isinstance(batch, YOLO._YuvBatch):
-                batch.check_device(self.device)
-                _lib.check(lib.mi355_yolo_infer_tiled_yuv(hnd, batch.structs, int(batch.on_device), n, C.byref(opts), float(conf), float(iou), cls_arr,
-                                                          ncls, max_det, imgsz, rows.ctypes.data, max_det, cp, tile_idx.ctypes.data))
-            else:
-                if batch.on_device and batch.frames is not None:
-                    if any(f.device.index != self.device for f in batch.frames):
-                        raise ValueError("frames live on a different GPU than the engine")
-                    torch.cuda.current_stream(batch.frames[0].device).synchronize()   # engine runs on its own stream
-                _lib.check(lib.mi355_yolo_infer_tiled(hnd, *batch.args(), C.byref(opts), float(conf), float(iou), cls_arr, ncls, max_det, imgsz,
-                                                      rows.ctypes.data, max_det, cp, tile_idx.ctypes.data))
+        with self._lock:                       # re-entered by the call: the Results read the timing of the engine that ran it
+            rows, counts, tile_idx = self._run(batch, det_args(conf, iou, classes, max_det, imgsz, half, False), opts)
             return self._build_results(rows, counts, list(batch.shapes), originals, [], tile_idx, tiles)
 
     @staticmethod
@@ -622,7 +451,6 @@ class YOLO:
         ``render=`` as in :meth:`predict`: drawn after the tracker step, so ``Results.rendered`` shows the tracker's boxes and ids; the
         picture is rendered from the copy of the frame the motion compensation uploaded.  ``encode=`` as in :meth:`predict`."""
         from .jpeg import as_spec as as_jpeg_spec
-        from .ops import DeviceFrame
         from .render import as_spec
         from .tracker import BYTETracker
         kwargs.pop("batch", None)
@@ -645,9 +473,11 @@ class YOLO:
             # the convenience form: the motion compensation takes a host BGR frame, so a YUV frame is converted on the GPU and its BGR
             # bytes come back to the host (one device-to-host copy per frame); the call then proceeds as on BGR frames
             source = [f.to_bgr(self.device) for f in yuv]
-        batch, originals = self._as_batch(source)
-        if isinstance(batch, YOLO._Ragged):
+        batch, originals = as_batch(source)
+        if isinstance(batch, Ragged):
             raise ValueError("frames of different shapes in one call are not supported; call once per shape")
+        a = det_args_from(conf, kwargs)
+        tiling = None if kwargs.get("tile") is None else {k: kwargs[k] for k in ("tile", "overlap", "full_frame", "tile_iou", "tile_metric") if k in kwargs}
         results = []
         for i in range(int(batch.shape[0])):
             frame = originals[i] if originals is not None else batch[i].cpu().numpy()
@@ -659,21 +489,14 @@ class YOLO:
             # the other, tools/track_timeline.py)
             share = os.environ.get("MI355_TRACK_SHARED_FRAME", "1") != "0"            # A/B and tests only
             dev = self._tracker.gmc.pending_device_frame() if share and isinstance(frame, np.ndarray) and frame.ndim == 3 else None
-            if dev is not None and dev[1:] == tuple(frame.shape[:2]) and not kwargs.get("stream") and kwargs.get("tile") is not None:
-                # tiled: the tiles are cut from the same uploaded copy, and the tracker consumes the merged rows
-                imgsz = kwargs.get("imgsz", 640)
-                res = self._predict_tiled(YOLO._RaggedDevice([dev[0]], [dev[1:]]), None, float(conf), kwargs.get("iou", 0.7), kwargs.get("classes"),
-                                          kwargs.get("max_det", 300), int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"),
-                                          kwargs.get("feats"), kwargs["tile"],
-                                          **{k: kwargs[k] for k in ("overlap", "full_frame", "tile_iou", "tile_metric") if k in kwargs})[0]
-            elif dev is not None and dev[1:] == tuple(frame.shape[:2]) and not kwargs.get("stream"):
-                imgsz = kwargs.get("imgsz", 640)
-                res = self._predict_batch(YOLO._DeviceFrames(dev[0], 1, dev[1], dev[2]), None, float(conf), kwargs.get("iou", 0.7), kwargs.get("classes"),
-                                          kwargs.get("max_det", 300), int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"),
-                                          kwargs.get("feats"))[0]
-            else:
+            if dev is not None and (dev[1:] != tuple(frame.shape[:2]) or kwargs.get("stream")):
                 dev = None
+            if dev is None:
                 res = self.predict(batch[i:i + 1], conf=conf, **kwargs)[0]
+            else:
+                # tiled: the tiles are cut from the same uploaded copy (by pointer), and the tracker consumes the merged rows
+                shared = DeviceFrames(dev[0], 1, dev[1], dev[2]) if tiling is None else Ragged.from_pointers([dev[0]], [dev[1:]])
+                res = self._detect(shared, None, a, tiling)[0]
             if originals is not None:
                 res.orig_img = originals[i]
             # trackers/track.py:on_predict_postprocess_end: the tracker steps on EVERY frame (an empty frame still advances
@@ -752,7 +575,7 @@ class YOLO:
         unknown = set(kwargs) - {"iou", "classes", "max_det", "imgsz", "half", "feats", "show", "verbose"}
         if unknown:                                              # show / verbose are accepted and ignored, as in track()
             raise TypeError(f"track_cameras: unsupported argument(s) {sorted(unknown)} (iou, classes, max_det, imgsz, half pass through)")
-        conf = 0.1 if conf is None else float(conf)
+        a = det_args_from(0.1 if conf is None else conf, kwargs)
         # a camera that delivers a YUVFrame: converted on the GPU, its BGR bytes brought to the host for the motion compensation (as track())
         if has_jpeg_frames(frames):                              # ... and the cameras that deliver JPEGFrames: one decode call for all of them
             with self._lock:
@@ -764,10 +587,9 @@ class YOLO:
         for i, f in enumerate(frames):
             if f is None:
                 continue
-            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[-1] != 3:
+            if not isinstance(f, np.ndarray):
                 raise ValueError("frames must be uint8 arrays of shape [H,W,3] (BGR, as cv2 delivers them), or None for an absent camera")
-            if not f.flags.c_contiguous:
-                frames[i] = np.ascontiguousarray(f)
+            frames[i] = bgr_view(f, dense=True).keep             # dense: the motion compensation takes C-contiguous frames
         spec = self._motion_gate_spec(motion_gate, n)
         cams = getattr(self, "_cameras", None)
         if persist and cams is not None and len(cams[0]) != n:
@@ -808,14 +630,11 @@ class YOLO:
         res = []
         if run:
             if dev is not None:
-                batch = YOLO._RaggedDevice([dev[i] for i in run], [f.shape[:2] for f in originals])
+                batch = Ragged.from_pointers([dev[i] for i in run], [f.shape[:2] for f in originals])
             else:
-                batch = YOLO._Ragged(originals, False)
-            imgsz = kwargs.get("imgsz", 640)
+                batch = Ragged(originals, False)
             try:
-                res = self._predict_batch(batch, originals, conf, kwargs.get("iou", 0.7), kwargs.get("classes"), kwargs.get("max_det", 300),
-                                          int(max(imgsz)) if isinstance(imgsz, (list, tuple)) else int(imgsz), kwargs.get("half"),
-                                          True if reid else kwargs.get("feats"))
+                res = self._predict_batch(batch, originals, *a._replace(feats=True if reid else a.feats))
             except BaseException:
                 gmc.reset()                                      # the enqueued tick must not be taken for the next call's frames
                 if gate is not None:
@@ -842,7 +661,6 @@ class YOLO:
     def _render_cameras(self, out, spec, frames, dev, jspec=None):
         """``track_cameras(render=..., encode=...)``: the present cameras' pictures from the tick's uploaded frames (valid until the next tick's
         motion-compensation step), or from the host frames when that step shared none"""
-        from .ops import DeviceFrame
         src = [None if f is None else (f if dev is None else DeviceFrame(dev[i], f.shape[0], f.shape[1])) for i, f in enumerate(frames)]
         return self._render_into(out, spec, src, None, jspec)
 
@@ -908,25 +726,20 @@ class YOLO:
         hnd = self._handle(half)
         if as_frames(source) is not None:
             raise TypeError("raw_head takes BGR frames: convert a YUVFrame with .to_bgr() first")
-        batch, _ = self._as_batch(source)
-        if isinstance(batch, YOLO._Ragged):
-            ch, an = C.c_int(), C.c_int()
-            _lib.check(lib.mi355_yolo_raw_head_multi(hnd, *batch.args(), imgsz, None, C.byref(ch), C.byref(an)))
-            out = np.empty((len(batch.frames), ch.value, an.value), dtype=np.float32)
-            with self._lock:
-                if batch.on_device:
-                    torch.cuda.current_stream(batch.frames[0].device).synchronize()
-                _lib.check(lib.mi355_yolo_raw_head_multi(hnd, *batch.args(), imgsz, out.ctypes.data, C.byref(ch), C.byref(an)))
-            return out
-        if isinstance(batch, torch.Tensor):
-            batch = batch.cpu().numpy()
-        n, h, w = batch.shape[:3]
+        batch, _ = as_batch(source)
+        if isinstance(batch, Ragged):
+            call = lambda data: lib.mi355_yolo_raw_head_multi(hnd, *batch.args(), imgsz, data, C.byref(ch), C.byref(an))     # noqa: E731
+        else:
+            if isinstance(batch, torch.Tensor):
+                batch = batch.cpu().numpy()   # a dense tensor is brought to the host: the hook takes host memory
+            call = lambda data: lib.mi355_yolo_raw_head(hnd, batch.ctypes.data if data else None, *batch.shape[:3], 0, imgsz, data,     # noqa: E731
+                                                        C.byref(ch), C.byref(an))
         ch, an = C.c_int(), C.c_int()
-        _lib.check(lib.mi355_yolo_raw_head(hnd, None, n, h, w, 0, imgsz, None, C.byref(ch), C.byref(an)))
-        out = np.empty((n, ch.value, an.value), dtype=np.float32)
+        _lib.check(call(None))                # the sizing call: null output, nothing is launched
+        out = np.empty((batch.shape[0], ch.value, an.value), dtype=np.float32)
         with self._lock:
-            _lib.check(lib.mi355_yolo_raw_head(hnd, batch.ctypes.data, n, h, w, 0, imgsz, out.ctypes.data,
-                                               C.byref(ch), C.byref(an)))
+            ready(batch, self.device)
+            _lib.check(call(out.ctypes.data))
         return out
 
     def plan_info(self) -> dict:

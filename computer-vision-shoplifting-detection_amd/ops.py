@@ -11,6 +11,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
+from .sources import DeviceFrame, Ragged, bgr_view, one_or_many, wait_for_torch  # noqa: F401  (DeviceFrame: part of this module's surface)
 
 
 def _f32(a):
@@ -472,9 +473,7 @@ def letterbox(bgr_u8: np.ndarray, imgsz: int = 640, device: int = 0) -> np.ndarr
 
 def letterbox_multi(frames: Sequence[np.ndarray], imgsz: int = 640, device: int = 0) -> np.ndarray:
     """Frames of any (h, w) (row strides honoured) -> the square [n, imgsz, imgsz, 3] canvas of a mixed batch (LetterBox auto=False)."""
-    from .engine import YOLO
-    rb = YOLO._Ragged(frames, False)
-    ptrs, hs, ws, rs, _, n = rb.args()
+    ptrs, hs, ws, rs, _, n = Ragged(frames, False).args()
     out = np.empty((n, imgsz, imgsz, 3), dtype=np.uint8)
     _lib.check(_lib.lib().mi355_op_letterbox_multi(device, ptrs, hs, ws, rs, n, imgsz, out.ctypes.data))
     return out
@@ -524,16 +523,9 @@ def motion_grid(frames, block: int = 16, device: int = 0):
     return out
 
 
-class DeviceFrame:
-    """A dense-or-pitched BGR uint8 frame on a GPU known by raw pointer (``ops.render``): the copy a motion-compensation step uploaded"""
-    def __init__(self, ptr: int, h: int, w: int, pitch: Optional[int] = None):
-        self.ptr, self.shape, self.pitch = int(ptr), (int(h), int(w), 3), int(pitch) if pitch else 3 * int(w)
-
-
 def _frame_descriptors(frames, device: int, handle):
     """The ``mi355_render_frame`` records of a render or JPEG call -> (records, what they point into, ``frames`` or None): a list of
     arrays, CUDA tensors, ``YUVFrame`` and ``DeviceFrame``; or None with a handle -- the frames of the handle's last call."""
-    import torch
     from .yuv import YUVFrame
     lib = _lib.lib()
     keep, fd = [], []
@@ -555,32 +547,35 @@ def _frame_descriptors(frames, device: int, handle):
         for f in frames:
             if isinstance(f, YUVFrame):
                 f = yuv_to_bgr([f], device=-1)[0] if device < 0 else f.to_bgr(device)
+            v = bgr_view(f, empty_ok=True)
             if isinstance(f, DeviceFrame):
                 if device < 0:
                     raise ValueError("a frame on a GPU cannot be rendered by the host twin")
-                fd.append(_lib.RenderFrame(f.ptr, f.shape[0], f.shape[1], f.pitch, 1))
+                fd.append(_lib.RenderFrame(v.ptr, *v.hw, v.pitch, 1))      # a raw pointer: passed on as it was given
                 continue
-            on_dev = isinstance(f, torch.Tensor) and f.is_cuda
-            if isinstance(f, torch.Tensor) and not on_dev:
-                f = f.numpy()
-            if f.dtype != (torch.uint8 if on_dev else np.uint8) or f.ndim != 3 or f.shape[-1] != 3:
-                raise ValueError("frames must be uint8 [H, W, 3] BGR arrays or CUDA tensors")
-            if on_dev:
-                if device < 0 or f.device.index != device:
+            if v.on_device:
+                if device < 0 or v.keep.device.index != device:
                     raise ValueError("a CUDA frame must live on the GPU the call runs on")
-                if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.shape[1]:
-                    f = f.contiguous()
-                torch.cuda.current_stream(f.device).synchronize()
-                ptr, pitch = f.data_ptr(), f.stride(0)
-            else:
-                f = np.asarray(f)
-                if f.size and (f.strides[2] != 1 or f.strides[1] != 3 or f.strides[0] < 3 * f.shape[1]):
-                    f = np.ascontiguousarray(f)
-                ptr, pitch = f.ctypes.data, f.strides[0]
-            h, w = int(f.shape[0]), int(f.shape[1])
-            keep.append(f)
-            fd.append(_lib.RenderFrame(ptr or 1, h, w, int(max(pitch, 3 * w)), int(on_dev)))
+                wait_for_torch(v.keep.device)
+            keep.append(v.keep)
+            # an empty array has no address and may report any pitch: the entries take a non-null pointer and a pitch of at least one
+            # row, and refuse the frame by its size
+            fd.append(_lib.RenderFrame(v.ptr or 1, *v.hw, int(max(v.pitch, 3 * v.hw[1])), int(v.on_device)))
     return fd, keep, frames
+
+
+def _call_on_frames(handle, device: int, by_handle, by_device, fd, frames, args, timing: Optional[list]) -> None:
+    """One render / encode call over the records ``fd``: with an engine ``handle`` on its stream with its scratch (``frames`` None:
+    the frames of the handle's last call), else on ``device`` with the call's own; ``timing`` receives the launches' ms."""
+    n = len(fd)
+    ms = C.c_float(0.0)
+    msp = C.byref(ms) if timing is not None else None
+    if handle is not None:
+        _lib.check(by_handle(handle, None if frames is None else (_lib.RenderFrame * n)(*fd), n, *args, msp))
+    else:
+        _lib.check(by_device(device, (_lib.RenderFrame * n)(*fd), n, *args, None, msp))
+    if timing is not None:
+        timing.append(float(ms.value))
 
 
 def render(frames, prims, device: int = 0, out: str = "numpy", timing: Optional[list] = None, handle=None):
@@ -593,17 +588,14 @@ def render(frames, prims, device: int = 0, out: str = "numpy", timing: Optional[
     ``handle``: an engine handle -- the call runs on its stream with its scratch (``mi355_yolo_render``), and ``frames=None`` then means
     the frames of that handle's last call, read from where the call left them on the GPU."""
     import torch
-    from .yuv import YUVFrame
     if out not in ("numpy", "cuda"):
         raise ValueError(f"out must be 'numpy' or 'cuda', got {out!r}")
     device = int(device)
     if out == "cuda" and device < 0:
         raise ValueError("out='cuda' needs a GPU: the host twin (device=-1) returns numpy arrays")
     lib = _lib.lib()
-    single = isinstance(frames, (np.ndarray, YUVFrame, torch.Tensor, DeviceFrame))
-    if single:
-        frames, prims = [frames], [prims]
-    prims = list(prims)
+    frames, single = one_or_many(frames)
+    prims = [prims] if single else list(prims)
     fd, keep, frames = _frame_descriptors(frames, device, handle)
     if len(fd) != len(prims):
         raise ValueError("prims: one int32 [P, 8] array per frame")
@@ -625,14 +617,7 @@ def render(frames, prims, device: int = 0, out: str = "numpy", timing: Optional[
     n = len(fd)
     ptrs = (C.c_void_p * n)(*[p.ctypes.data if len(p) else None for p in pp])
     counts = (C.c_int * n)(*[len(p) for p in pp])
-    ms = C.c_float(0.0)
-    msp = C.byref(ms) if timing is not None else None
-    if handle is not None:
-        _lib.check(lib.mi355_yolo_render(handle, None if frames is None else (_lib.RenderFrame * n)(*fd), n, ptrs, counts, (_lib.RenderOut * n)(*od), msp))
-    else:
-        _lib.check(lib.mi355_render(device, (_lib.RenderFrame * n)(*fd), n, ptrs, counts, (_lib.RenderOut * n)(*od), None, msp))
-    if timing is not None:
-        timing.append(float(ms.value))
+    _call_on_frames(handle, device, lib.mi355_yolo_render, lib.mi355_render, fd, frames, (ptrs, counts, (_lib.RenderOut * n)(*od)), timing)
     return outs[0] if single else outs
 
 
@@ -651,13 +636,11 @@ def jpeg_encode(frames, quality: int = 85, subsampling: str = "420", device: int
     tables), ``subsampling`` "420" or "444".  ``device=-1`` runs the host twin and touches no GPU.  ``handle``: an engine handle -- the
     call runs on its stream with its scratch (``mi355_yolo_encode``), and ``frames=None`` then means the frames of that handle's last
     call, read from where the call left them on the GPU.  ``timing``: a list that receives the launches' ms."""
-    import torch
-    from .yuv import YUVFrame
     device = int(device)
     quality, ss = _jpeg_args(quality, subsampling)
     lib = _lib.lib()
-    single = isinstance(frames, (np.ndarray, YUVFrame, torch.Tensor, DeviceFrame))
-    fd, keep, frames = _frame_descriptors([frames] if single else frames, device, handle)
+    frames, single = one_or_many(frames)
+    fd, keep, frames = _frame_descriptors(frames, device, handle)
     n = len(fd)
     bufs, od = [], []
     for f in fd:
@@ -666,14 +649,7 @@ def jpeg_encode(frames, quality: int = 85, subsampling: str = "420", device: int
         bufs.append(b)
         od.append(_lib.JpegOut(b.ctypes.data, cap, 0))
     outs = (_lib.JpegOut * n)(*od)
-    ms = C.c_float(0.0)
-    msp = C.byref(ms) if timing is not None else None
-    if handle is not None:
-        _lib.check(lib.mi355_yolo_encode(handle, None if frames is None else (_lib.RenderFrame * n)(*fd), n, quality, ss, outs, msp))
-    else:
-        _lib.check(lib.mi355_jpeg_encode(device, (_lib.RenderFrame * n)(*fd), n, quality, ss, outs, None, msp))
-    if timing is not None:
-        timing.append(float(ms.value))
+    _call_on_frames(handle, device, lib.mi355_yolo_encode, lib.mi355_jpeg_encode, fd, frames, (quality, ss, outs), timing)
     res = [bufs[i][:outs[i].length].tobytes() for i in range(n)]
     return res[0] if single else res
 
@@ -682,13 +658,11 @@ def jpeg_coefficients(frames, quality: int = 85, subsampling: str = "420", devic
     """The transform stage of :func:`jpeg_encode` alone (``mi355_op_jpeg_coefficients``): per frame int16 [blocks, 64] -- quantised DCT
     coefficients in zigzag order, blocks in scan order (MCU rows, MCUs, then Y0 Y1 Y2 Y3 Cb Cr for "420", Y Cb Cr for "444").
     ``device=-1`` runs the host twin."""
-    import torch
-    from .yuv import YUVFrame
     device = int(device)
     quality, ss = _jpeg_args(quality, subsampling)
     lib = _lib.lib()
-    single = isinstance(frames, (np.ndarray, YUVFrame, torch.Tensor, DeviceFrame))
-    fd, keep, frames = _frame_descriptors([frames] if single else frames, device, None)
+    frames, single = one_or_many(frames)
+    fd, keep, frames = _frame_descriptors(frames, device, None)
     m, per = (16, 6) if ss == _lib.JPEG_420 else (8, 3)
     outs = [np.zeros((max(-(-f.height // m) * -(-f.width // m) * per, 0), 64), np.int16) for f in fd]
     ptrs = (C.c_void_p * len(fd))(*[o.ctypes.data or 1 for o in outs])
@@ -757,7 +731,7 @@ def jpeg_decode(streams, device: int = 0, entropy: str = "auto", out=None, as_te
             raise ValueError("out: a read-only array")
         od.append(_lib.RenderOut(o.data_ptr() if on_dev else o.ctypes.data, int(max(st[0], 3 * f.shape[1])), int(on_dev)))
     if any(d.on_device for d in od):
-        torch.cuda.current_stream(device).synchronize()      # the call runs on its own stream
+        wait_for_torch(device)                               # the call runs on its own stream
     sd = (_lib.JpegStream * n)(*[f.struct() for f in fr])
     status = (C.c_int * n)()
     ms = C.c_float(0.0)
