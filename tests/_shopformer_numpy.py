@@ -23,7 +23,7 @@ def _mha(q_in, kv_in, t, name, heads):
     n, s, hd = q.shape[0], q.shape[1], d // heads
     sp = lambda a: a.reshape(n, -1, heads, hd).transpose(0, 2, 1, 3)
     q, k, v = sp(q), sp(k), sp(v)
-    a = q @ k.transpose(0, 1, 3, 2) / np.sqrt(hd)
+    a = q @ k.transpose(0, 1, 3, 2) / q.dtype.type(np.sqrt(hd))             # a scalar of the evaluation's own type: float32 stays float32
     a = np.exp(a - a.max(-1, keepdims=True))
     a = a / a.sum(-1, keepdims=True)
     o = (a @ v).transpose(0, 2, 1, 3).reshape(n, s, d)

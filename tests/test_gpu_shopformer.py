@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import _shopformer_numpy as R
+from _shopformer_sweep_cases import check_elements
 from _shopformer_c_forms import old_c_forms_equal_forward
 
 pytestmark = pytest.mark.gpu
@@ -36,11 +37,23 @@ def _within(got, fix, name, tag=""):
         assert e_gpu <= 1.25 * e_ref + 1e-6, (key, e_gpu, e_ref)
 
 
+def _every_element(got, fix, name, x, tag="", img64=None):
+    """each output, element by element, against the float64 numpy evaluation of the SAME fp32 weight image (``img64``, computed here
+    when not given), in units of the float32 numpy evaluation's own error (tests/_shopformer_sweep_cases.py)"""
+    from cvsd_amd import shopformer as SF
+    cfg, sd, _ = R.fixture_model(fix, name)
+    image = SF.parse_image(SF.image_from_state_dict(sd, cfg))
+    img64, img32 = R.forward(*image, x) if img64 is None else img64, R.forward(*image, x, dtype=np.float32)
+    for key, _ in KEYS:
+        r = check_elements(got[key], img64[key], img32[key], key, f"{name} {tag}")
+        print(f"{name} {tag}{key}: max |gpu - f64(image)| {r['err_max']:.3e} = {r['ratio_max']:.3f} x numpy fp32's, mean {r['ratio_mean']:.3f} x")
+
+
 @pytest.mark.parametrize("name", CONFIGS)
 def test_outputs_within_the_references_own_fp32_error(fix, models, name):
     model, x = models[name]
     got = model.forward(x)
-    # reported, not asserted: the part of the error that is summation order alone = distance to a float64 evaluation of the SAME fp32
+    # the part of the error that is summation order alone (asserted per element by _every_element) = distance to a float64 evaluation of the SAME fp32
     # weight image (the rest of the distance to the reference is the second rounding of the folded weights)
     from cvsd_amd import shopformer as SF
     cfg, sd, _ = R.fixture_model(fix, name)
@@ -48,6 +61,7 @@ def test_outputs_within_the_references_own_fp32_error(fix, models, name):
     for key, ref in KEYS:
         print(f"{name} {key}: mean |gpu - f64(image)| {np.abs(got[key] - img64[key]).mean():.3e}, "
               f"mean |f64(image) - f64 reference| {np.abs(img64[key] - fix[f'{name}.{ref}_f64']).mean():.3e}")
+    _every_element(got, fix, name, x, img64=img64)
     _within(got, fix, name)
 
 
@@ -126,6 +140,7 @@ def test_video_to_scores_end_to_end(fix, models, v8n_pose):
     scores, index = score_poselift(model, data)
     assert np.array_equal(scores, model.score(windows_from_poselift(data)[0]))
     _within(model.forward(windows_from_poselift(data)[0]), fix, "default", tag="poselift_")
+    _every_element(model.forward(windows_from_poselift(data)[0]), fix, "default", windows_from_poselift(data)[0], tag="poselift_")
     st, live = StreamScorer(model), []
     for f in sorted(data):
         rows = np.asarray([[b[0], b[1], b[0] + b[2], b[1] + b[3], pid] for pid, (b, _) in data[f].items()], np.float32).reshape(-1, 5)

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import _shopformer_decoder_numpy as RD
+from _shopformer_sweep_cases import check_elements
 
 pytestmark = pytest.mark.gpu
 CONFIGS = ["default", "kp18_t24", "h32_l4", "paper", "default24"]
@@ -38,13 +39,17 @@ def test_decoder_within_the_references_own_fp32_error(fix, models, name):
     assert model.has_decoder and model.decoder_info.frames == int(fix[f"{name}.frames"])
     got = model.decode(fix[f"{name}.tokens_f32"])
     f64, f32 = fix[f"{name}.poses_f64"], fix[f"{name}.poses_f32"]
-    # reported, not asserted: summation order alone (distance to a float64 evaluation of the SAME fp32 image on the same fp32 tokens)
+    # summation order alone, asserted per element below (distance to a float64 evaluation of the SAME fp32 image on the same fp32 tokens)
     # and what is left of the distance to the reference (the fp32 rounding of the folded weights and of the fp32 tokens)
-    img64 = RD.decode(*SF.parse_image(SF.image_from_state_dict(sd, cfg, decoder=True)), fix[f"{name}.tokens_f32"])
+    image = SF.parse_image(SF.image_from_state_dict(sd, cfg, decoder=True))
+    img64 = RD.decode(*image, fix[f"{name}.tokens_f32"])
     e_gpu, e_ref = float(np.abs(got - f64).mean()), float(np.abs(f32 - f64).mean())
     print(f"{name} poses: gpu mean err {e_gpu:.3e}, reference fp32 mean err {e_ref:.3e}, ratio {e_gpu / e_ref:.3f}; "
           f"mean |gpu - f64(image)| {np.abs(got - img64).mean():.3e}, mean |f64(image) - f64 reference| {np.abs(img64 - f64).mean():.3e}")
     assert got.shape == f64.shape and got.dtype == np.float32
+    # every element, in units of the float32 numpy evaluation's own error (tests/_shopformer_sweep_cases.py)
+    r = check_elements(got, img64, RD.decode(*image, fix[f"{name}.tokens_f32"], dtype=np.float32), "gcae_reconstructed", name)
+    print(f"{name} poses: max |gpu - f64(image)| {r['err_max']:.3e} = {r['ratio_max']:.3f} x numpy fp32's, mean {r['ratio_mean']:.3f} x")
     assert e_gpu <= 1.25 * e_ref + 1e-6, (e_gpu, e_ref)
 
 
