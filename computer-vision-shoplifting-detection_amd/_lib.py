@@ -81,6 +81,11 @@ class RenderOut(C.Structure):
     _fields_ = [("data", C.c_void_p), ("row_stride", C.c_int), ("on_device", C.c_int)]
 
 
+class CropSpec(C.Structure):
+    """mi355_crop_spec: the size (0, 0: native), fit and fill of a crop call"""
+    _fields_ = [("struct_size", C.c_int), ("height", C.c_int), ("width", C.c_int), ("fit", C.c_int), ("fill", C.c_int)]
+
+
 class JpegOut(C.Structure):
     """mi355_jpeg_out: host memory for one JPEG stream, and the length the call reports"""
     _fields_ = [("data", C.c_void_p), ("capacity", C.c_int64), ("length", C.c_int64)]
@@ -108,6 +113,7 @@ class JpegStreamInfo(C.Structure):
 
 RENDER_WORDS, RENDER_MAX_PRIMS, RENDER_MAX_FRAMES = 8, 16384, 256      # MI355_RENDER_*
 JPEG_ENTROPY = {"auto": 0, "gpu": 1, "host": 2, "sync": 3}                       # MI355_JPEG_ENTROPY_*
+CROP_FIT = {"stretch": 0, "pad": 1}                                              # MI355_CROP_*
 JPEG_420, JPEG_444 = 420, 444           # MI355_JPEG_*
 MOTION_MAX_CAMERAS = 64                 # MI355_MOTION_MAX_CAMERAS
 TILE_IOS, TILE_IOU = 0, 1               # MI355_TILE_IOS / MI355_TILE_IOU
@@ -270,6 +276,8 @@ SIGNATURES = {
     "mi355_render": (C.c_int, [C.c_int, _P(RenderFrame), C.c_int, _P(C.c_void_p), _i32p, _P(RenderOut), C.c_void_p, _f32p]),
     "mi355_yolo_render": (C.c_int, [C.c_void_p, _P(RenderFrame), C.c_int, _P(C.c_void_p), _i32p, _P(RenderOut), _f32p]),
     "mi355_yolo_last_frames": (C.c_int, [C.c_void_p, _P(RenderFrame), C.c_int, _i32p]),
+    "mi355_crops": (C.c_int, [C.c_int, _P(RenderFrame), C.c_int, _P(C.c_void_p), _i32p, _P(CropSpec), _P(RenderOut), C.c_void_p, _f32p]),
+    "mi355_yolo_crops": (C.c_int, [C.c_void_p, _P(RenderFrame), C.c_int, _P(C.c_void_p), _i32p, _P(CropSpec), _P(RenderOut), _f32p]),
     "mi355_jpeg_bound": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mi355_jpeg_encode": (C.c_int, [C.c_int, _P(RenderFrame), C.c_int, C.c_int, C.c_int, _P(JpegOut), C.c_void_p, _f32p]),
     "mi355_yolo_encode": (C.c_int, [C.c_void_p, _P(RenderFrame), C.c_int, C.c_int, C.c_int, _P(JpegOut), _f32p]),

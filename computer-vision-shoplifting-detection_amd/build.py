@@ -13,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmi355yolo.so")
 SOURCES = ["conv_f32_k3s1.hip", "conv_f32_k3s2.hip", "conv_f32_k1.hip", "conv_f32_pipe.hip", "conv_f32_splitk.hip", "conv_f32_fused_s1.hip", "conv_f32_fused_s2.hip", "conv_f32_group.hip", "conv_f32_sparse.hip", "conv_igemm_f16.hip", "conv_f16_fused.hip", "conv_f16_small.hip", "conv_f16_lw.hip", "conv_plan.hip",
-           "misc_kernels.hip", "dw_attn_kernels.hip", "post_kernels.hip", "engine_load.hip", "engine_memory.hip", "engine_plans.hip", "engine_run.hip", "engine_multi.hip", "engine_yuv.hip", "engine_tiled.hip", "yuv_kernels.hip", "engine_abi.hip", "engine_ops.hip", "shopformer_kernels.hip", "shopformer_host.hip", "shopformer_decoder.hip", "pose_windows.hip", "gmc_kernels.hip", "motion_kernels.hip", "render_kernels.hip", "jpeg_kernels.hip", "jpeg_decode_kernels.hip", "gmc_host.cpp", "tracker_host.cpp", "jpeg_decode_host.cpp"]
-HEADERS = ["common.h", "detmath.h", "conv_f32.h", "conv_f32_inst.h", "conv_f16.h", "engine_internal.h", "shopformer.h", "pose_windows.h", "tile_merge.h", "motion_grid.h", "render_raster.h", "jpeg_codec.h", "jpeg_decode.h", "jpeg_sync.h", "dev_buf.h", os.path.join("..", "..", "include", "mi355_yolo.h")]
+           "misc_kernels.hip", "dw_attn_kernels.hip", "post_kernels.hip", "engine_load.hip", "engine_memory.hip", "engine_plans.hip", "engine_run.hip", "engine_multi.hip", "engine_yuv.hip", "engine_tiled.hip", "yuv_kernels.hip", "engine_abi.hip", "engine_ops.hip", "shopformer_kernels.hip", "shopformer_host.hip", "shopformer_decoder.hip", "pose_windows.hip", "gmc_kernels.hip", "motion_kernels.hip", "render_kernels.hip", "jpeg_kernels.hip", "jpeg_decode_kernels.hip", "crop_kernels.hip", "gmc_host.cpp", "tracker_host.cpp", "jpeg_decode_host.cpp", "crops_host.cpp"]
+HEADERS = ["common.h", "detmath.h", "conv_f32.h", "conv_f32_inst.h", "conv_f16.h", "engine_internal.h", "shopformer.h", "pose_windows.h", "tile_merge.h", "motion_grid.h", "render_raster.h", "jpeg_codec.h", "jpeg_decode.h", "jpeg_sync.h", "crop_resize.h", "dev_buf.h", os.path.join("..", "..", "include", "mi355_yolo.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-result"]
 
 

@@ -5,6 +5,7 @@
 #pragma once
 #include "common.h"
 #include "dev_buf.h"
+#include "crop_resize.h"
 #include "../../include/mi355_yolo.h"
 
 #include <algorithm>
@@ -59,6 +60,12 @@ struct RenderCtx { Buf d_work; Buf h_img{true}, h_out{true}; hipEvent_t ev0 = nu
 int render_run(RenderCtx& ctx, int device, const mi355_render_frame* frames, int n, const int32_t* const* prims, const int* n_prims,
                const mi355_render_out* outs, hipStream_t st, float* launch_ms);
 void render_ctx_free(RenderCtx& ctx);
+
+// crop_kernels.hip: the grow-only scratch of crop calls -- one device buffer [descriptors | tap tables | staged rows of host
+// frames | outputs bound for the host], the pinned image of its first two parts and the pinned landing area of host outputs.  The call
+// itself (crops_call, crops_run_gpu) is declared in crop_resize.h.
+struct CropCtx { Buf d_work; Buf h_img{true}, h_out{true}; hipEvent_t ev0 = nullptr, ev1 = nullptr; };
+void crop_ctx_free(CropCtx& ctx);
 
 // jpeg_kernels.hip: the grow-only scratch of JPEG calls -- one device buffer [descriptors | tables | lengths | headers |
 // per frame: coefficients, segment words, segment sizes, stream | staged host frames], the pinned image of its first part and the pinned
@@ -134,20 +141,12 @@ inline Geometry make_geometry(int h0, int w0, int imgsz, bool auto_pad = true) {
     return g;
 }
 
-// cv2.resize(INTER_LINEAR) coefficient table: for each destination index: source index, 2 taps in 1/2048 units
+// cv2.resize(INTER_LINEAR) coefficient table: for each destination index: source index, 2 taps in 1/2048 units.  The arithmetic is
+// crop_resize.h's crop_tap_table (that header also builds without HIP, for the crop host twin): the letterbox kernel and the crop
+// kernel read tables of ONE builder
 inline void resize_table(int dn, int sn, std::vector<int>& tab) {
     tab.resize((size_t)dn * 3);
-    const double scale = (double)sn / dn;
-    for (int d = 0; d < dn; ++d) {
-        float fx = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)std::floor(fx);
-        fx -= (float)s;
-        if (s < 0) { s = 0; fx = 0.f; }
-        if (s >= sn - 1) { s = sn - 1; fx = 0.f; }
-        tab[d * 3] = s;
-        tab[d * 3 + 1] = (int)std::lrintf((1.f - fx) * 2048.f);
-        tab[d * 3 + 2] = (int)std::lrintf(fx * 2048.f);
-    }
+    crop_tap_table(dn, sn, tab.data());
 }
 
 }  // namespace mi355
@@ -308,6 +307,7 @@ struct mi355_yolo {
     RenderCtx render;
     JpegCtx jpeg;                       // mi355_yolo_encode's scratch
     JpegDecCtx jpeg_dec;                // mi355_yolo_decode's scratch
+    CropCtx crops;                      // mi355_yolo_crops' scratch
     unsigned long long plan_hash = 0;   // fingerprint of the candidate lists + the chosen indices of the current shape
     int plan_source = 0, plan_launches = 0;   // 0 static guess (autotune off), 1 memory, 2 this machine's plan cache, 3 tuned now, 4 shipped plan file; launches of one pass (stem..last conv)
     bool async_pending = false;         // mi355_yolo_infer_device_async work may still be in flight on `stream`

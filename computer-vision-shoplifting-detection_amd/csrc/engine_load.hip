@@ -33,6 +33,7 @@ mi355_yolo::~mi355_yolo() {
     render_ctx_free(render);
     jpeg_ctx_free(jpeg);
     jpeg_dec_ctx_free(jpeg_dec);
+    crop_ctx_free(crops);
     if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1);
     for (auto e : pev) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) { if (ev_copied[i]) (void)hipEventDestroy(ev_copied[i]); if (ev_consumed[i]) (void)hipEventDestroy(ev_consumed[i]); }

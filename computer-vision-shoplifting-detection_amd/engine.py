@@ -260,7 +260,7 @@ class YOLO:
     def predict(self, source=None, conf: Optional[float] = None, iou: float = IOU, classes=None, max_det: int = MAX_DET,
                 imgsz: int = IMGSZ, half: Optional[bool] = None, verbose: bool = False, stream: bool = False,
                 feats: Optional[bool] = None, tile=None, overlap: float = 0.2, full_frame: bool = True, tile_iou: float = 0.5,
-                tile_metric: str = "ios", render=None, encode=None, **kwargs) -> List[Results]:
+                tile_metric: str = "ios", render=None, encode=None, crops=None, save_crop: bool = False, **kwargs) -> List[Results]:
         """``model.predict`` / ``model(...)``: ultralytics/engine/model.py:Model.predict.
         ``half=True`` runs the fp16-storage engine (fp32 accumulate; results differ from fp32 by fp16 rounding);
         ``None`` = the precision the model was constructed with (fp32 unless ``YOLO(..., half=True)``).
@@ -280,7 +280,15 @@ class YOLO:
         ``encode``: "jpeg" or a :class:`cvsd_amd.jpeg.JpegSpec` (or a dict of its fields) -- every ``Results`` carries
         ``jpeg``, the bytes of a baseline JFIF stream encoded on the GPU: of the rendered picture with ``render=`` (the picture stays
         on the GPU and ``Results.rendered`` stays None unless ``keep_pixels``), of the source frame itself without.  Only the bytes
-        come back.  ``None`` (default): the call as it always was."""
+        come back.  ``None`` (default): the call as it always was.
+        ``crops``: True or a :class:`cvsd_amd.crops.CropSpec` (or a dict of its fields) -- every ``Results`` carries
+        ``crops``, crop i the picture of box i (``save_one_box``'s rectangle; native size, or all resampled to ``size``), cut on the
+        GPU in ONE launch from the copy of the frames this call already put there (``source="rendered"``: from the drawn picture of
+        ``render=``); ``out="cuda"`` with a size leaves one uint8 tensor [M, h, w, 3] per frame on the GPU for a downstream torch
+        model.  With ``encode=`` the crops are encoded as well (``Results.crop_jpegs``; their pixels then come back only with
+        ``keep_pixels`` or stay on the GPU with ``out="cuda"``).  ``save_crop=True`` is ``crops=True, encode="jpeg"`` when neither is
+        given; ``Results.save_crop(dir)`` writes the files.  ``None`` (default): the call as it always was."""
+        from .crops import crop_call_args
         from .jpeg import as_spec as as_jpeg_spec
         from .render import as_spec
         a = det_args(0.25 if conf is None else conf, iou, classes, max_det, imgsz, half, feats)
@@ -289,15 +297,16 @@ class YOLO:
             # from here on the call is the one it is for CUDA BGR tensors
             with self._lock:                   # the handle's stream and decode scratch: no other call of this model in between
                 source = decode_sources(source, self.device, self._handle(half, feats))
+        cspec, encode = crop_call_args(crops, encode, save_crop, render)
         spec, jspec = as_spec(render), as_jpeg_spec(encode)
         tiling = None if tile is None else dict(tile=tile, overlap=overlap, full_frame=full_frame, tile_iou=tile_iou, tile_metric=tile_metric)
-        plain = spec is None and jspec is None
+        plain = spec is None and jspec is None and cspec is None
         # render= / encode=: the picture is drawn from the frames this call leaves on the GPU, so no other call may come in between
         # (the lock is re-entrant); a plain call holds the lock around its C call only
         with nullcontext() if plain else self._lock:
             batch, originals = as_batch(source, by_pointer=tiling is not None)
             res = self._detect(batch, originals, a, tiling)
-            return res if plain else self._render_into(res, spec, None, lambda: self._batch_frames(batch), jspec)
+            return res if plain else self._render_into(res, spec, None, lambda: self._batch_frames(batch), jspec, cspec)
 
     def _detect(self, batch, originals, a: DetArgs, tiling: Optional[dict] = None) -> List[Results]:
         """one detector call on a batch: tiled (``tiling``: the tile arguments of :meth:`predict`) or not"""
@@ -310,19 +319,24 @@ class YOLO:
         """the frames of a call as ``ops.render`` takes them (the fallback of ``_render_into``: a copy that has left the GPU)"""
         return batch.render_frames() if isinstance(batch, (Ragged, YuvBatch)) else list(batch)
 
-    def _render_into(self, results, spec, sources, fallback=None, jspec=None):
+    def _render_into(self, results, spec, sources, fallback=None, jspec=None, cspec=None):
         """Fills ``Results.rendered`` of every non-None result with ONE render call on the engine that ran the detector.  ``sources``
         None: the frames of that engine's last call, from where the call left them on the GPU (``fallback()`` -> the frames to pass again
         when a copy has been overwritten: host calls of more than two chunks); else one frame per result as ``ops.render`` takes them.
         ``jspec`` (``encode=``): the pictures stay on the GPU and ONE encode call on the same stream fills ``Results.jpeg`` (the pixels
-        come back only with ``keep_pixels``); with ``spec`` None the source frames themselves are encoded."""
+        come back only with ``keep_pixels``); with ``spec`` None the source frames themselves are encoded.
+        ``cspec`` (``crops=``): ONE crop call on the same stream, after the render call and before the encode calls, fills
+        ``Results.crops`` from the boxes the results carry (the tracker's, after a tracker step); with ``jspec`` ONE more encode call
+        fills ``Results.crop_jpegs``."""
         from . import ops
+        from .crops import crop_rects
         from .render import primitives
         idx = [i for i, r in enumerate(results) if r is not None]
         if not idx:
             return results
         hnd = getattr(self, "_last_handle", None) or self._h
-        where = "numpy" if jspec is None else "cuda"
+        from_pics = cspec is not None and cspec.source == "rendered"
+        where = "numpy" if jspec is None and not from_pics else "cuda"
 
         def on_frames(call):
             if sources is not None:
@@ -337,6 +351,23 @@ class YOLO:
             if spec is not None:
                 prims = [primitives(results[i], spec) for i in idx]
                 pics = on_frames(lambda fr: ops.render(fr, prims, device=self.device, handle=hnd, out=where))
+            if cspec is not None:
+                rects = [crop_rects(results[i].boxes.xyxy.numpy(), results[i].orig_shape, cspec.gain, cspec.pad, cspec.square) for i in idx]
+                cwhere = "cuda" if jspec is not None else cspec.out
+                cut = lambda fr: ops.crop_resize(fr, rects, cspec.size, cspec.fit, cspec.fill, device=self.device, out=cwhere, handle=hnd)   # noqa: E731
+                cuts = cut(pics) if from_pics else on_frames(cut)
+                if jspec is not None:
+                    # the crops of non-empty rectangles, all results' in one encode call; an empty rectangle has no stream
+                    live = [[bool(r[2] > r[0] and r[3] > r[1]) for r in rr.tolist()] for rr in rects]
+                    flat = [c for cc, ll in zip(cuts, live) for c, ok in zip(cc, ll) if ok]
+                    enc = iter(ops.jpeg_encode(flat, jspec.quality, jspec.subsampling, device=self.device, handle=hnd) if flat else [])
+                    for i, ll in zip(idx, live):
+                        results[i].crop_jpegs = [next(enc) if ok else None for ok in ll]
+                    if cspec.out != "cuda":
+                        cuts = [[c.cpu().numpy() for c in cc] for cc in cuts] if jspec.keep_pixels else None
+                if cuts is not None:
+                    for i, cc in zip(idx, cuts):
+                        results[i].crops = cc
             if jspec is not None:
                 enc = lambda fr: ops.jpeg_encode(fr, jspec.quality, jspec.subsampling, device=self.device, handle=hnd)   # noqa: E731
                 streams = enc(pics) if pics is not None else on_frames(enc)
@@ -344,6 +375,8 @@ class YOLO:
                     results[i].jpeg = b
                 if pics is not None:
                     pics = [p.cpu().numpy() for p in pics] if jspec.keep_pixels else None
+            elif from_pics:
+                pics = [p.cpu().numpy() for p in pics]
         if pics is not None:
             for i, pic in zip(idx, pics):
                 results[i].rendered = pic
@@ -449,13 +482,17 @@ class YOLO:
         ``tile=...`` (with ``overlap``, ``full_frame``, ``tile_iou``, ``tile_metric``) is passed on to :meth:`predict`: the tracker consumes
         the merged rows of the tiled call (not together with ``with_reid``: a tiled call has no features).
         ``render=`` as in :meth:`predict`: drawn after the tracker step, so ``Results.rendered`` shows the tracker's boxes and ids; the
-        picture is rendered from the copy of the frame the motion compensation uploaded.  ``encode=`` as in :meth:`predict`."""
+        picture is rendered from the copy of the frame the motion compensation uploaded.  ``encode=`` as in :meth:`predict`.
+        ``crops=`` / ``save_crop=`` as in :meth:`predict`: cut after the tracker step, of the tracker's boxes -- the rows the ``Results``
+        carry, the ones ``render=`` draws."""
+        from .crops import crop_call_args
         from .jpeg import as_spec as as_jpeg_spec
         from .render import as_spec
         from .tracker import BYTETracker
         kwargs.pop("batch", None)
+        cspec, encode = crop_call_args(kwargs.pop("crops", None), kwargs.pop("encode", None), kwargs.pop("save_crop", False), kwargs.get("render"))
         spec = as_spec(kwargs.pop("render", None))
-        jspec = as_jpeg_spec(kwargs.pop("encode", None))
+        jspec = as_jpeg_spec(encode)
         conf = 0.1 if conf is None else conf
         cfg = self._tracker_settings("track", tracker, continuing=self._tracker is not None and persist)
         if cfg is not None:
@@ -504,9 +541,9 @@ class YOLO:
             # result is skipped when no track comes back
             tracks = self._tracker.update(res.boxes.data.numpy(), frame, feats=res.feats if reid else None)   # trackers/track.py: tracker.update(det, im0, feats)
             res = self._with_tracks(res, tracks)
-            if spec is not None or jspec is not None:
+            if spec is not None or jspec is not None or cspec is not None:
                 # the motion compensation's copy stays where it is until its next step; without one, the detector call's own copy
-                self._render_into([res], spec, None if dev is None else [DeviceFrame(dev[0], dev[1], dev[2])], lambda: [frame], jspec)
+                self._render_into([res], spec, None if dev is None else [DeviceFrame(dev[0], dev[1], dev[2])], lambda: [frame], jspec, cspec)
             results.append(res)
         return results
 
@@ -563,15 +600,20 @@ class YOLO:
         boxes and ids drawn in, all cameras in ONE render call reading the frames the motion compensation uploaded; an absent camera has
         no picture, and a camera the motion gate skipped is drawn with the rows its tracker stepped on.
         ``encode`` (DESIGN.md 3.20): as in :meth:`predict` -- ``Results.jpeg`` of every present camera, all cameras in ONE encode call;
-        an absent camera has no bytes."""
+        an absent camera has no bytes.
+        ``crops`` / ``save_crop``: as in :meth:`predict` -- ``Results.crops`` of every present camera, the tracker's
+        boxes, all cameras in ONE crop launch; an absent camera stays None, and a camera the motion gate skipped has its carried rows
+        cut out of this tick's frame."""
+        from .crops import crop_call_args
         from .gmc import MultiGMC
         from .jpeg import as_spec as as_jpeg_spec
         from .render import as_spec
         from .tracker import BYTETracker
         tracker = kwargs.pop("tracker", None)
         motion_gate = kwargs.pop("motion_gate", None)
+        cspec, encode = crop_call_args(kwargs.pop("crops", None), kwargs.pop("encode", None), kwargs.pop("save_crop", False), kwargs.get("render"))
         rspec = as_spec(kwargs.pop("render", None))
-        jspec = as_jpeg_spec(kwargs.pop("encode", None))
+        jspec = as_jpeg_spec(encode)
         unknown = set(kwargs) - {"iou", "classes", "max_det", "imgsz", "half", "feats", "show", "verbose"}
         if unknown:                                              # show / verbose are accepted and ignored, as in track()
             raise TypeError(f"track_cameras: unsupported argument(s) {sorted(unknown)} (iou, classes, max_det, imgsz, half pass through)")
@@ -644,7 +686,7 @@ class YOLO:
         if gate is None:
             for r, i in zip(res, present):
                 out[i] = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i], feats=r.feats if reid else None))    # an empty frame still steps
-            return out if rspec is None and jspec is None else self._render_cameras(out, rspec, frames, dev, jspec)
+            return out if rspec is None and jspec is None and cspec is None else self._render_cameras(out, rspec, frames, dev, jspec, cspec)
         fresh = dict(zip(run, res))
         for i in present:
             r = fresh.get(i)
@@ -656,13 +698,13 @@ class YOLO:
             r = self._with_tracks(r, trackers[i].update(r.boxes.data.numpy(), warp=warps[i], feats=r.feats if reid else None))
             r.motion = {"moving": bool(moving[i]), "changed": int(changed[i]), "skipped": i not in fresh}
             out[i] = r
-        return out if rspec is None and jspec is None else self._render_cameras(out, rspec, frames, dev, jspec)
+        return out if rspec is None and jspec is None and cspec is None else self._render_cameras(out, rspec, frames, dev, jspec, cspec)
 
-    def _render_cameras(self, out, spec, frames, dev, jspec=None):
+    def _render_cameras(self, out, spec, frames, dev, jspec=None, cspec=None):
         """``track_cameras(render=..., encode=...)``: the present cameras' pictures from the tick's uploaded frames (valid until the next tick's
         motion-compensation step), or from the host frames when that step shared none"""
         src = [None if f is None else (f if dev is None else DeviceFrame(dev[i], f.shape[0], f.shape[1])) for i, f in enumerate(frames)]
-        return self._render_into(out, spec, src, None, jspec)
+        return self._render_into(out, spec, src, None, jspec, cspec)
 
     # ---- motion gate of track_cameras (DESIGN.md 3.18) --------------------------------------------------------------------------
     @staticmethod

@@ -621,6 +621,80 @@ def render(frames, prims, device: int = 0, out: str = "numpy", timing: Optional[
     return outs[0] if single else outs
 
 
+def crop_resize(frames, rects, size=None, fit: str = "stretch", fill: int = 114, device: int = 0, out: str = "numpy", handle=None,
+                timing: Optional[list] = None):
+    """Cut rectangles out of frames and copy or resample them (csrc/crop_kernels.hip).  ``frames``: what :func:`render`
+    takes -- arrays of any pitch, uint8 CUDA tensors on ``device`` read in place, ``cvsd_amd.YUVFrame``, :class:`DeviceFrame`, or a list
+    of them of any sizes; ``rects``: int32 [M, 4] (x1, y1, x2, y2) per frame (``cvsd_amd.crops.crop_rects`` makes them of boxes), M may
+    be 0 and x2 <= x1 or y2 <= y1 is an empty rectangle.  ``size=None``: crop k is the copy ``frame[y1:y2, x1:x2]``; ``size=(h, w)``:
+    ``fit="stretch"`` is ``cv2.resize(crop, (w, h), INTER_LINEAR)`` bit for bit, ``"pad"`` LetterBox(auto=False) with ``fill``; an empty
+    rectangle is all ``fill``.  One call, ONE launch, whatever the number of frames and rectangles.  Returns, per frame, a list of uint8
+    arrays (``out="numpy"``) or CUDA tensors (``"cuda"``); with a fixed size and ``"cuda"`` one tensor [M, h, w, 3] per frame, all views
+    of a single allocation -- nothing comes back to the host.  A single frame gives a single such value.  ``device=-1`` runs the host
+    twin and touches no GPU.  ``handle``: an engine handle -- the call runs on its stream with its scratch (``mi355_yolo_crops``), and
+    ``frames=None`` then means the frames of that handle's last call.  ``timing``: a list that receives the launch's ms."""
+    import torch
+    if out not in ("numpy", "cuda"):
+        raise ValueError(f"out must be 'numpy' or 'cuda', got {out!r}")
+    if fit not in _lib.CROP_FIT:
+        raise ValueError(f"fit must be 'stretch' or 'pad', got {fit!r}")
+    device = int(device)
+    if out == "cuda" and device < 0:
+        raise ValueError("out='cuda' needs a GPU: the host twin (device=-1) returns numpy arrays")
+    lib = _lib.lib()
+    frames, single = one_or_many(frames)
+    rects = [rects] if single else list(rects)
+    fd, keep, frames = _frame_descriptors(frames, device, handle)
+    if len(fd) != len(rects):
+        raise ValueError("rects: one int32 [M, 4] array per frame")
+    rr = []
+    for r in rects:
+        r = np.ascontiguousarray(np.zeros((0, 4), np.int32) if r is None else r)
+        if r.dtype != np.int32 or r.ndim != 2 or r.shape[1] != 4:
+            raise ValueError("rects must be int32 arrays of shape [M, 4]")
+        rr.append(r)
+    if size is not None and (int(size[0]), int(size[1])) == (0, 0):
+        raise ValueError("size must be None (native) or (h, w) of positive integers, got (0, 0)")
+    if size is None:
+        spec = _lib.CropSpec(C.sizeof(_lib.CropSpec), 0, 0, _lib.CROP_FIT[fit], int(fill))
+    else:
+        spec = _lib.CropSpec(C.sizeof(_lib.CropSpec), int(size[0]), int(size[1]), _lib.CROP_FIT[fit], int(fill))
+    cuda = out == "cuda"
+    dev = torch.device("cuda", device) if cuda else None
+    res, od = [], []
+
+    def record(o):
+        if cuda:
+            return _lib.RenderOut(o.data_ptr() or 1, 3 * o.shape[1], 1)
+        return _lib.RenderOut(o.ctypes.data or 1, 3 * o.shape[1], 0)
+
+    if size is None:
+        for r in rr:
+            per = []
+            for x1, y1, x2, y2 in r.tolist():
+                h, w = (y2 - y1, x2 - x1) if x2 > x1 and y2 > y1 else (0, 0)
+                o = torch.empty((h, w, 3), dtype=torch.uint8, device=dev) if cuda else np.empty((h, w, 3), np.uint8)
+                per.append(o)
+                od.append(record(o))
+            res.append(per)
+    else:
+        h, w = max(int(size[0]), 0), max(int(size[1]), 0)
+        total = sum(len(r) for r in rr)
+        block = torch.empty((total, h, w, 3), dtype=torch.uint8, device=dev) if cuda else np.empty((total, h, w, 3), np.uint8)
+        at = 0
+        for r in rr:
+            part = block[at:at + len(r)]
+            at += len(r)
+            od.extend(record(part[k]) for k in range(len(r)))
+            res.append(part if cuda else list(part))
+    n = len(fd)
+    ptrs = (C.c_void_p * n)(*[r.ctypes.data if len(r) else None for r in rr])
+    counts = (C.c_int * n)(*[len(r) for r in rr])
+    outs = (_lib.RenderOut * max(len(od), 1))(*od)
+    _call_on_frames(handle, device, lib.mi355_yolo_crops, lib.mi355_crops, fd, frames, (ptrs, counts, C.byref(spec), outs), timing)
+    return res[0] if single else res
+
+
 def _jpeg_args(quality, subsampling):
     ss = {"420": _lib.JPEG_420, "444": _lib.JPEG_444, 420: _lib.JPEG_420, 444: _lib.JPEG_444}.get(subsampling)
     if ss is None:

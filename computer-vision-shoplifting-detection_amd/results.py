@@ -158,6 +158,24 @@ class Keypoints(_BaseTensor):
         return self.data[..., 2] if self.has_visible else None
 
 
+def _rows_of(seq, idx):
+    """``Results.crops`` / ``crop_jpegs`` under the index a ``Results`` is subscripted with: a tensor is indexed as it is, a list by an
+    integer (one row), a slice, a boolean mask or an index array"""
+    if seq is None:
+        return None
+    if isinstance(seq, torch.Tensor):
+        if isinstance(idx, (int, np.integer)):
+            return seq[[int(idx)]]
+        return seq[torch.as_tensor(idx, device=seq.device) if isinstance(idx, (np.ndarray, list, torch.Tensor)) else idx]
+    ix = idx.numpy() if isinstance(idx, torch.Tensor) else idx
+    if isinstance(ix, (int, np.integer)):
+        return [seq[ix]]
+    if isinstance(ix, slice):
+        return seq[ix]
+    ix = np.asarray(ix)
+    return [seq[int(i)] for i in (np.nonzero(ix)[0] if ix.dtype == bool else ix)]
+
+
 class Results:
     """One image's predictions (``list[Results]`` is what ``model(frame)`` / ``model.track(frame)`` return)."""
 
@@ -190,6 +208,11 @@ class Results:
         # predict / track / track_cameras(encode=...): bytes, a baseline JFIF stream of the rendered picture (with render=) or of the
         # frame itself, encoded on the GPU; None for any other call
         self.jpeg = None
+        # predict / track / track_cameras(crops=...): crop i is the picture of box i -- a list of uint8 arrays (or CUDA
+        # tensors), or with a fixed size and out="cuda" one CUDA tensor [M, h, w, 3]; crop_jpegs (with encode=): a list of bytes, None
+        # for the crop of an empty rectangle.  None for any other call
+        self.crops = None
+        self.crop_jpegs = None
 
     def plot(self, **spec) -> np.ndarray:
         """``results[0].plot()``: this result drawn into a COPY of its frame -> uint8 [H, W, 3] BGR, rendered on the GPU
@@ -210,6 +233,42 @@ class Results:
             fh.write(self.jpeg)
         return str(filename)
 
+    def save_crop(self, save_dir, file_name="im"):
+        """``results[0].save_crop(dir)``: one JPEG per box, ``save_dir/<class name>/<file_name>.jpg``, ``<file_name>2.jpg``, ... (the
+        layout of Ultralytics' ``save_one_box`` under ``increment_path``) -> the paths.  Writes ``crop_jpegs`` when the call made them
+        (``crops=..., encode=...`` or ``save_crop=True``); otherwise cuts native crops out of ``orig_img`` and encodes them now, on the
+        GPU the engine lives on.  The crop of an empty rectangle (a box outside the frame) has no file."""
+        import os
+        streams = self.crop_jpegs
+        if streams is None:
+            from . import ops
+            from .crops import crop_rects
+            if self.orig_img is None:
+                raise ValueError("this Results holds no image (its frames were on the GPU, or YUV planes) and no crop streams: ask for them "
+                                 "at call time, predict / track / track_cameras(..., save_crop=True)")
+            streams = []
+            if len(self):
+                rects = crop_rects(self.boxes.xyxy.numpy() if isinstance(self.boxes.xyxy, torch.Tensor) else self.boxes.xyxy, self.orig_shape)
+                cut = ops.crop_resize(np.asarray(self.orig_img), rects, device=self._render_device, out="cuda")
+                live = [c for c in cut if c.numel()]
+                enc = iter(ops.jpeg_encode(live, device=self._render_device) if live else [])
+                streams = [next(enc) if c.numel() else None for c in cut]
+        paths = []
+        cls = self.boxes.cls.tolist() if len(self) else []
+        for b, c in zip(streams, cls):
+            if b is None:
+                continue
+            d = os.path.join(str(save_dir), str(self.names[int(c)]))
+            os.makedirs(d, exist_ok=True)
+            path, k = os.path.join(d, f"{file_name}.jpg"), 1
+            while os.path.exists(path):
+                k += 1
+                path = os.path.join(d, f"{file_name}{k}.jpg")
+            with open(path, "wb") as fh:
+                fh.write(b)
+            paths.append(path)
+        return paths
+
     def __len__(self):
         return len(self.boxes) if self.boxes is not None else 0
 
@@ -228,6 +287,7 @@ class Results:
         r.tiles = self.tiles
         r.motion = self.motion
         r.rendered, r._render_device, r.jpeg = self.rendered, self._render_device, self.jpeg
+        r.crops, r.crop_jpegs = _rows_of(self.crops, idx), _rows_of(self.crop_jpegs, idx)      # aligned with the boxes, like feats
         return r
 
     def update(self, boxes=None):
@@ -248,4 +308,5 @@ class Results:
         r.tile_idx, r.tiles = self.tile_idx, self.tiles
         r.motion = self.motion
         r.rendered, r._render_device, r.jpeg = self.rendered, self._render_device, self.jpeg
+        r.crops, r.crop_jpegs = self.crops, self.crop_jpegs
         return r

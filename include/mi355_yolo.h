@@ -664,6 +664,41 @@ int  mi355_yolo_render(mi355_yolo* h, const mi355_render_frame* frames, int n, c
                        const mi355_render_out* outs, float* launch_ms);
 int  mi355_yolo_last_frames(mi355_yolo* h, mi355_render_frame* frames_out, int cap, int* n);
 
+/* ---- person crops: rectangles cut out of BGR frames, copied or resampled to one size ----------------------------------
+ * Integer arithmetic on the device (csrc/crop_resize.h; the kernel of csrc/crop_kernels.hip and its host twin give the same bytes).
+ * rects[i] = n_rects[i] host records of four int32 (x1, y1, x2, y2) in pixels of frames[i]: the crop is frame[y1:y2, x1:x2].
+ * 0 <= x1, x2 <= width and 0 <= y1, y2 <= height; x2 <= x1 or y2 <= y1 is an EMPTY rectangle, which is legal.
+ *   spec->height == 0 and spec->width == 0   native: crop k is a plain copy, (y2 - y1) x (x2 - x1) pixels; an empty rectangle writes
+ *            nothing (its output pointer may be NULL).
+ *   spec->height, spec->width > 0            every crop has that size.  MI355_CROP_STRETCH: cv2.resize(crop, (width, height),
+ *            INTER_LINEAR) in OpenCV's 11-bit fixed point, the taps clamped at the CROP's edges.  MI355_CROP_PAD: the crop is scaled by
+ *            r = min(height / ch, width / cw) to round-half-even(side * r) (at least 1) and centred as Ultralytics' LetterBox(auto=False)
+ *            centres it, the rest is spec->fill.  An empty rectangle gives a crop of spec->fill.
+ * outs: one record per rectangle, all frames' rectangles in frame order (n_rects[0] + ... + n_rects[n - 1] records), host memory or
+ * memory of the call's GPU; of an output only the crop's pixel bytes are written.
+ *   mi355_crops   device >= 0: that GPU; -1: the host twin (host memory only), which touches no GPU.  frames[i]: host memory (the rows
+ *            its rectangles span are uploaded, once) or memory of that GPU (on_device = 1, read in place).  All crops of a call, whatever
+ *            their frames and sizes, take ONE launch on `stream`; the call returns when it and the copies have finished.  Nothing
+ *            outside a rectangle is read.  launch_ms (or NULL): the launch's device time.
+ *   mi355_yolo_crops   the same on an engine handle: its stream, scratch kept between calls; frames = NULL cuts the frames of the
+ *            handle's last blocking infer call where that call left them (mi355_yolo_render's rules on which copies are alive).
+ * A null pointer, a rectangle with a negative coordinate or one beyond its frame, a size that is not positive (other than 0 x 0), an
+ * unknown fit, a fill outside 0 .. 255, a frame or output of 2 GiB or more, or device memory with device = -1 is MI355_EINVAL with a
+ * message naming the argument, before a byte of any output is written. */
+#define MI355_CROP_STRETCH 0
+#define MI355_CROP_PAD     1
+#define MI355_CROP_MAX_RECTS 65536      /* per call */
+typedef struct mi355_crop_spec {
+    int struct_size;                    /* sizeof(mi355_crop_spec) */
+    int height, width;                  /* 0, 0: native */
+    int fit;                            /* MI355_CROP_* */
+    int fill;                           /* 0 .. 255, every channel */
+} mi355_crop_spec;
+int  mi355_crops(int device, const mi355_render_frame* frames, int n, const int32_t* const* rects, const int* n_rects,
+                 const mi355_crop_spec* spec, const mi355_render_out* outs, void* stream, float* launch_ms);
+int  mi355_yolo_crops(mi355_yolo* h, const mi355_render_frame* frames, int n, const int32_t* const* rects, const int* n_rects,
+                      const mi355_crop_spec* spec, const mi355_render_out* outs, float* launch_ms);
+
 /* ---- evidence frames as JPEG: a BGR frame in, a baseline JFIF stream out ------------------------------------------------
  * Integer arithmetic throughout (csrc/jpeg_codec.h; the kernels of csrc/jpeg_kernels.hip and their host twin give the same bytes).
  * The stream: SOI, APP0 (JFIF 1.01, no thumbnail), DQT (luminance), DQT (chrominance), SOF0, DHT x 4 (DC 0, AC 0, DC 1, AC 1), DRI, SOS,
