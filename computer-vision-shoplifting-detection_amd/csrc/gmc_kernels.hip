@@ -475,6 +475,16 @@ PyrGeom pyr_geometry(int h0, int w0, int max_level, int win) {
     for (int l = 0; l < q.levels; ++l) { q.off[l] = q.bytes; q.bytes += al((size_t)q.hs[l] * q.ws[l]); }
     return q;
 }
+// would the same rule without the kMaxLevels bound (the host routine's) build more planes than a pyramid here holds?
+bool pyr_too_deep(int h0, int w0, int max_level, int win) {
+    int h = h0, w = w0, planes = 1;
+    for (int l = 0; l < max_level && planes <= kMaxLevels; ++l) {
+        h = (h + 1) / 2; w = (w + 1) / 2;
+        if (h <= win || w <= win) break;
+        ++planes;
+    }
+    return planes > kMaxLevels;
+}
 
 // level l - 1 -> level l of `count` pyramids that lie `stride` bytes apart
 void enqueue_pyr_down(hipStream_t s, int count, uint8_t* pyr, size_t stride, const PyrGeom& q, int l) {
@@ -638,12 +648,15 @@ int one_shot_ctx(int device, GmcCtx** out) {
 
 }  // namespace
 
-// Same contract as mi355_gmc_pyr_lk (gmc_host.cpp) with the work done on GPU `device`: 0 = ok, -1 = bad argument, -2 = HIP error.
+// Same contract as mi355_gmc_pyr_lk (gmc_host.cpp) with the work done on GPU `device`: 0 = ok, -1 = bad argument (win > 21 and a pyramid of
+// more than kMaxLevels planes among them), -2 = HIP error.
 extern "C" int mi355_gmc_pyr_lk_device(int device, const uint8_t* prev, const uint8_t* cur, int height, int width, const float* pts, int n,
                                        int win, int max_level, int max_iters, double eps, double min_eig, float* next_pts, uint8_t* status) {
     if (!prev || !cur || height <= 0 || width <= 0 || n < 0 || (n > 0 && (!pts || !next_pts || !status)) || win < 3 || !(win & 1) || win > 21 ||
         device < 0 || device >= 16 || max_level < 0)
         return -1;
+    // a pyramid the host routine would build deeper than kMaxLevels planes is refused, not tracked from a lower top level
+    if (pyr_too_deep(height, width, max_level, win)) return -1;
     if (n == 0) return 0;
     std::lock_guard<std::mutex> lock(g_mu);
     GmcCtx* ctx = nullptr;

@@ -97,7 +97,10 @@ def calc_optical_flow_pyr_lk(prev: np.ndarray, cur: np.ndarray, pts: np.ndarray,
     """cv2.calcOpticalFlowPyrLK as the product runs it.  ``device=None``: the host C++ loops of csrc/gmc_host.cpp (the numpy
     statement of the algorithm is oracle/gmc_oracle.py:calc_optical_flow_pyr_lk, its cross-check in the tests).
     ``device=k``: the HIP kernels of csrc/gmc_kernels.hip on GPU k (one wavefront per point; what ``model.track`` uses: on the
-    host the 1000-corner budget costs 10-27 ms per frame, thirty times the detector pass)."""
+    host the 1000-corner budget costs 10-27 ms per frame, thirty times the detector pass).  The device routine takes windows up
+    to 21 x 21 and pyramids of at most 8 planes (the frame and 7 halvings): a larger window, or ``levels`` and a plane for which
+    the host routine would build a deeper pyramid (each halving still larger than the window), raise ``ValueError`` -- the host
+    routine takes both."""
     import ctypes as C
     from . import _lib
     prev, cur = np.ascontiguousarray(prev, dtype=np.uint8), np.ascontiguousarray(cur, dtype=np.uint8)
@@ -116,7 +119,7 @@ def calc_optical_flow_pyr_lk(prev: np.ndarray, cur: np.ndarray, pts: np.ndarray,
     if rc == -2:
         raise RuntimeError(f"mi355_gmc_pyr_lk_device: HIP error on device {device} (no GPU? the host routine is device=None)")
     if rc != 0:
-        raise ValueError("mi355_gmc_pyr_lk: bad argument")
+        raise ValueError("mi355_gmc_pyr_lk: bad argument" + (" (the device routine: win <= 21, at most 8 pyramid planes)" if device is not None else ""))
     return nxt, status.astype(bool)
 
 
